@@ -13,7 +13,7 @@ timed region (image decode/encode excluded).  Pages are independ
 its own pages, no data-path collective; the only collective is the start-up weight broadcast over RCCL
 (outside the timed region).  Weights are seeded random (no checkpoints offline) with the real architectures.
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -138,13 +138,20 @@ def parse():
                          "or nunchaku, whose loader wraps the pipeline in the first-block cache (reference model_manager.py:1159-1162) with --residual-diff-threshold")
     ap.add_argument("--residual-diff-threshold", type=float, default=0.15, help="first-block cache threshold (reference core/config.py:150), used with --kontext-backend nunchaku")
     ap.add_argument("--no-extra", action="store_true",
-                    help="default command only (config 4, one GPU): skip the child runs that put BASELINE configs 5 and 2 and the first-block-cache figure "
+                    help="--full on the default command only (config 4, one GPU): skip the child runs that put BASELINE configs 5 and 2 and the first-block-cache figure "
                          "under `extra` of the same JSON line (after the timed region; ~2 minutes)")
     ap.add_argument("--extra-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--time-ops", default="auto", choices=["auto", "difference", "stamp"],
                     help="in-context kernel timing of the roofline objects: hipGraph with minus hipGraph without the ops (HIP events), "
                          "or device wall-clock stamps around the ops inside one graph (mtx_plan_time_ops, MTX_TIME_OPS=stamp); auto = "
                          "both, stamps reported when they pass a sanity band around the difference figure")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take everything that is not the headline figure: the stage-by-stage wall clock of one more page, "
+                         "per-stage GPU times, rooflines, the counter child (unless --no-traffic), the other BASELINE configs under `extra` (unless "
+                         "--no-extra) and the CPU baseline (unless --no-cpu-baseline).  Default: set up, warm up, time --steps pages, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned for its last step as DIR/<name>.npy (float32; arrays above a fixed size as a fixed, "
+                         "seeded sample of their elements; 64 MB at most in all)")
     a = ap.parse_args()
     preset = {1: "detect,clean", 2: "detect,segment", 3: "detect,segment,inpaint", 4: "detect,segment,inpaint,upscale", 5: "detect,segment,inpaint,upscale"}
     if a.stages is None or a.stages == "all":
@@ -594,11 +601,12 @@ def main():
 
     def run_steps(n):
         """n pages; with overlap, page i+1's front half runs on a worker thread beside page i's back half (a page still goes through its
-        stages in order, and every page does all of its work inside the region that is timed)"""
+        stages in order, and every page does all of its work inside the region that is timed).  Returns the last page's stage results."""
+        last = None
         if not overlap or n < 2:
             for i in range(n):
-                step(i)
-            return
+                last = step(i)
+            return last
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=n_front) as ex:
@@ -609,7 +617,8 @@ def main():
                 if nxt < n:
                     futs.append(ex.submit(stage_a, nxt))
                     nxt += 1
-                stage_b(i, work_)
+                last = stage_b(i, work_)
+        return last
 
     def barrier():
         torch.cuda.synchronize()
@@ -623,7 +632,7 @@ def main():
     run_steps(args.warmup)
     barrier()
     t0, cpu0 = time.perf_counter(), time.process_time()
-    run_steps(args.steps)
+    last_outs = run_steps(args.steps)
     barrier()
     dt = time.perf_counter() - t0
     host_cpu_ms_per_page = 1e3 * (time.process_time() - cpu0) / max(1, args.steps)      # CPU time of every thread of this process over the timed region
@@ -631,7 +640,9 @@ def main():
         want_calls = (setup_pages + args.warmup + args.steps) * args.regions
         assert flux.calls == want_calls, f"expected {want_calls} FLUX calls, saw {flux.calls}"
         assert flux.completed == want_calls, f"{want_calls - flux.completed} of {want_calls} FLUX calls raised (the OSB stage turns those into flat fills)"
-    if rank == 0:               # informational: wall clock of each stage of one more page, synchronised stage by stage
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_outs, Path(args.dump_outputs))
+    if rank == 0 and args.full:     # informational: wall clock of each stage of one more page, synchronised stage by stage
         stage_wall["_on"] = True
         step(0)
         stage_wall.pop("_on")
@@ -783,7 +794,7 @@ def main():
                                      "note": "seeded random weights: how often the probe passes says nothing about a trained model; parity with nunchaku unpinned"} if on_
                                     else {"state": f"off (backend {args.kontext_backend}: every step runs every block)", "steps_skipped": st_["skipped"]})
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- per-stage GPU time (HIP events on the launch stream), outside the timed region ---------------
         if sam is not None:
             pre, enc, dec, post = sam.plans(args.boxes, H_, W_)
@@ -956,6 +967,7 @@ def main():
             result["extra"] = run_extra_children()
         if not args.no_cpu_baseline and world == 1:          # the CPU leg is a single-GPU-run item (rank 0 at N = 1 only)
             result["cpu_baseline"] = cpu_baseline(stages, rcan_sd, W_, H_, args, cfg.get("inpaint"), flux.transformer.cfg if (klein and flux is not None) else None)
+    if rank == 0:
         print(json.dumps(result))
     if dist is not None:
         dist.barrier()
@@ -971,7 +983,7 @@ def run_extra_children():
       first_block_cache  3 pages of config 3 with the OSB stage configured for the reference's nunchaku backend (first-block cache on)
       upscale_model_lite_assumed_shape  the upscale stage alone with the reference's CLI-default upscaler, shape assumed (VERDICT r05 missing #3)"""
     import subprocess
-    me = [sys.executable, str(Path(__file__).resolve()), "--no-cpu-baseline", "--no-traffic", "--extra-child"]
+    me = [sys.executable, str(Path(__file__).resolve()), "--full", "--no-cpu-baseline", "--no-traffic", "--extra-child"]
     jobs = {"config5": ["--config", "5", "--steps", "8", "--warmup", "2"],
             "config2": ["--config", "2", "--steps", "64", "--warmup", "4"],
             "first_block_cache": ["--config", "3", "--steps", "3", "--warmup", "1", "--kontext-backend", "nunchaku"],
@@ -1021,8 +1033,8 @@ def measure_traffic(kernel_desc: str):
     if shutil.which("rocprofv3") is None:
         return None, {"error": "rocprofv3 not on PATH"}
     want = "attn_mma32" if kernel_desc.startswith("attn") else ("conv3x3_c64" if kernel_desc.startswith("conv") else "gemm256")
-    base = [a_ for a_ in sys.argv[1:] if a_ not in ("--with-traffic", "--no-traffic")]
-    for flag in ("--steps", "--warmup", "--stages", "--inpaint-steps", "--batch-io"):
+    base = [a_ for a_ in sys.argv[1:] if a_ not in ("--with-traffic", "--no-traffic") and not a_.startswith("--dump-outputs=")]
+    for flag in ("--steps", "--warmup", "--stages", "--inpaint-steps", "--batch-io", "--dump-outputs"):
         if flag in base:
             i_ = base.index(flag)
             del base[i_:i_ + 2]
@@ -1072,6 +1084,52 @@ def measure_traffic(kernel_desc: str):
     detail.update(launches=launches, read_bytes_per_launch=round(rd), write_bytes_per_launch=round(wr),
                   note="fabric-side bytes (Infinity-Cache hits counted), mean over every launch of the group in one page")
     return rd + wr, detail
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 1 << 20       # larger arrays are stored as this many elements at fixed, seeded positions (the same ones for the same size)
+
+
+def _output_arrays(obj, name, out):
+    """flatten a stage result into named arrays: tensors, numpy arrays, PIL images, numbers, and the detector results' boxes / masks"""
+    from PIL import Image
+    if obj is None:
+        return
+    if isinstance(obj, torch.Tensor):
+        out[name] = obj.detach().float().cpu().numpy()
+    elif isinstance(obj, np.ndarray):
+        out[name] = obj
+    elif isinstance(obj, Image.Image):
+        out[name] = np.asarray(obj)
+    elif isinstance(obj, (bool, int, float, np.number)) or (isinstance(obj, (list, tuple)) and obj and all(isinstance(v, (bool, int, float, np.number)) for v in obj)):
+        out[name] = np.asarray(obj)          # a number, or a colour / box given as a tuple of numbers
+    elif isinstance(obj, (list, tuple)):      # e.g. the cleaning stage: one tuple (or None) per bubble
+        for i, v in enumerate(obj):
+            _output_arrays(v, f"{name}_{i}", out)
+    elif hasattr(obj, "boxes"):          # a detector's Results: (N, 6) rows of x0, y0, x1, y1, conf, cls, and the instance masks where there are any
+        b = obj.boxes                    # (None when nothing passed the threshold)
+        out[name + "_boxes"] = (np.zeros((0, 6)) if b is None else
+                                torch.cat([b.xyxy.float().reshape(-1, 4), b.conf.float().reshape(-1, 1), b.cls.float().reshape(-1, 1)], 1).cpu().numpy())
+        if getattr(obj, "masks", None) is not None:
+            out[name + "_masks"] = obj.masks.data.float().cpu().numpy()
+
+
+def dump_outputs(outs, out_dir: Path):
+    """DIR/<stage>[_<part>].npy, float32, of one page's stage results; an array of more than DUMP_MAX_ELEMS elements keeps a sorted, seeded
+    sample of them (seed and positions depend only on the array's size, so two runs / builds sample the same elements).  A result with no
+    elements (a detector that found nothing on the page) has nothing to compare and is not written."""
+    arrays = {}
+    for k in sorted(outs or {}):
+        _output_arrays(outs[k], k, arrays)
+    arrays = {name: a for name, a in arrays.items() if np.asarray(a).size > 0}
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cap = max(1, min(DUMP_MAX_ELEMS, (DUMP_BUDGET_BYTES // max(1, len(arrays)) - 1024) // 4))      # (1 KB per file for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def dtype_string(stages, fp8_linears, fp8_attention=None):

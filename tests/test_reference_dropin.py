@@ -2,6 +2,7 @@
 reference, the reference's own `core` / `core.pipeline` imported on top of it, and the reference's `translate_and_render` run in
 cleaning-only mode — compared with `process_page_vision` on the same page.  Skipped where /root/reference does not exist (GPU box)."""
 import json
+import os
 import subprocess
 import sys
 from pathlib import Path
@@ -11,7 +12,7 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 
 
-@pytest.mark.skipif(not Path("/root/reference/core/pipeline.py").exists(), reason="the reference checkout only exists in the build container")
+@pytest.mark.skipif(not os.path.exists("/root/reference/core/pipeline.py"), reason="the reference checkout only exists in the build container")
 def test_reference_runs_on_top_of_this_package(emu_lib):
     r = subprocess.run([sys.executable, str(ROOT / "tests" / "dropin_runner.py")], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     line = [l for l in r.stdout.splitlines() if l.startswith("DROPIN_REPORT ")]

@@ -36,7 +36,7 @@ extern "C" {
 #define MTX_API
 #endif
 
-#define MTX_ABI_VERSION 8
+#define MTX_ABI_VERSION 9
 
 typedef enum mtx_status {
   MTX_OK = 0,
@@ -440,10 +440,45 @@ typedef struct mtx_tail_args {
   unsigned long long* sums; const float* params;
 } mtx_tail_args;
 
+/* ---- rendered-text colour probe of the outside-speech-bubble stage (csrc/textcolor.hip; reference core/outside_text_processor.py:1096-1165):
+ * per text region, the Lab distance of every crop pixel to the background colour, a contrast mask from its 95th percentile, the median
+ * RGB under the cleaned mask.  All N regions of a page go through every launch (grid row = region); region i is the rectangle rois[i] =
+ * (x0, y0, w, h) in page coordinates and owns the pixels offsets[i] .. + w * h of the planes.  Crop pixels outside the page read as black
+ * (what PIL's crop pads with).  The page is interleaved 8-bit RGB, read in place.
+ *  MTX_TC_DIST  d2[o] = dL^2 + da^2 + db^2 (OpenCV fixed-point 8-bit Lab, <= 195 075) against bg_lab[i]; then, exactly, the order statistics
+ *               of d2 at the MTX_TC_RANKS ascending ranks ranks[i][..] (0-based, < w * h) -> stats[i][MTX_TC_STAT_ORDER ..]: a 768-bin histogram
+ *               of d2 >> 8, the bins that hold the ranks, a 256-bin histogram of the low byte inside each of them (two passes over the pixels).
+ *  MTX_TC_MASK  mask[o] = 255 where (d2 > cutoff[i]) survives a 3x3 close and a 2x2 erode with anchor (1, 1), else 0; pixels outside the
+ *               crop never win a maximum / minimum (OpenCV's default morphology border).
+ *  MTX_TC_HIST  hist[i][c][v] = number of crop pixels with mask[o] != 0 (the caller's filled mask) and channel c == v.
+ * stats ([N][MTX_TC_STATS]) and hist ([N][768]) are zeroed by the call that fills them.  gamma_tab / cbrt_tab / lab_coef: as mtx_tail_args. */
+typedef enum mtx_textcolor_phase { MTX_TC_DIST = 0, MTX_TC_MASK = 1, MTX_TC_HIST = 2 } mtx_textcolor_phase;
+#define MTX_TC_RANKS 4
+#define MTX_TC_STAT_COARSE 0       /* [768] */
+#define MTX_TC_STAT_SEL 768        /* [MTX_TC_RANKS][2]: coarse bin, rank inside the bin */
+#define MTX_TC_STAT_FINE 776       /* [MTX_TC_RANKS][256] */
+#define MTX_TC_STAT_ORDER 1800     /* [MTX_TC_RANKS]: the order statistics */
+#define MTX_TC_STATS 1808
+typedef struct mtx_textcolor_args {
+  int32_t phase;
+  const void* page_rgb;                 /* u8 [H][W][3] */
+  const int32_t* rois;                  /* [N][4] */
+  const int64_t* offsets;               /* [N] */
+  const int32_t* bg_lab;                /* [N][3]                      (DIST) */
+  const int32_t* ranks;                 /* [N][MTX_TC_RANKS]           (DIST) */
+  const int32_t* cutoff;                /* [N]                         (MASK) */
+  int32_t* d2;                          /* i32 plane                   (DIST out, MASK in) */
+  uint8_t* mask;                        /* u8 plane                    (MASK out, HIST in) */
+  int32_t* stats;                       /* [N][MTX_TC_STATS]           (DIST out) */
+  int32_t* hist;                        /* [N][3][256]                 (HIST out) */
+  const int32_t* gamma_tab; const int32_t* cbrt_tab; const int32_t* lab_coef; int32_t cbrt_n;
+  int32_t n, page_h, page_w, max_pixels;   /* max_pixels = largest crop area */
+} mtx_textcolor_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
-  MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16
+  MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -459,7 +494,7 @@ typedef struct mtx_op {
   union {
     mtx_conv2d_args conv; mtx_gemm_args gemm; mtx_attn_args attn; mtx_norm_args norm;
     mtx_groupnorm_args gn; mtx_ew_args ew; mtx_ca_args ca; mtx_img_args img;
-    mtx_resize_thresh_args rt; mtx_memset_args ms; mtx_mask_select_args sel; mtx_preproc_args pre; mtx_yolo_decode_args yd; mtx_detr_args detr; mtx_quant_args quant; mtx_tail_args tail;
+    mtx_resize_thresh_args rt; mtx_memset_args ms; mtx_mask_select_args sel; mtx_preproc_args pre; mtx_yolo_decode_args yd; mtx_detr_args detr; mtx_quant_args quant; mtx_tail_args tail; mtx_textcolor_args tc;
   } u;
 } mtx_op;
 
@@ -491,6 +526,7 @@ MTX_API int mtx_bubble_clean(const mtx_clean_args* a, void* stream);
 MTX_API int mtx_detr(const mtx_detr_args* a, void* stream);
 MTX_API int mtx_quantize_mx(const mtx_quant_args* a, void* stream);
 MTX_API int mtx_page_tail(const mtx_tail_args* a, void* stream);
+MTX_API int mtx_text_color(const mtx_textcolor_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */
@@ -503,6 +539,9 @@ MTX_API int mtx_host_text_mask(const uint8_t* thr, const uint8_t* eroded, int w,
  * centre — what ultralytics exposes as `results.masks[i].xy[0]` (reference core/image/detection.py:525-556 reads it when SAM gave no
  * mask).  Writes up to `cap` (x, y) pairs, returns the outline's point count (call again if it exceeds cap), 0 for an empty mask. */
 MTX_API int mtx_host_mask_outline(const uint8_t* mask, int w, int h, int* xy, int cap);
+/* the contour step of the text-colour probe (reference core/outside_text_processor.py:1133-1144) on one [h][w] crop mask: external contours of
+ * the 8-connected blobs, those with contourArea >= min_area drawn FILLED (each on its own) into out (0 / 255).  Returns the number drawn. */
+MTX_API int mtx_host_fill_components(const uint8_t* mask, int w, int h, double min_area, uint8_t* out);
 
 /* host side: PNG writer of the batch harness (csrc/host_png.cpp; replaces Pillow + oxipng of reference core/image/image_utils.py:140-150):
  * uint8 [h][w][channels] (1 = L, 2 = LA, 3 = RGB, 4 = RGBA) -> a PNG file image in `out`.  reduce != 0: lossless colour-type reductions

@@ -345,7 +345,7 @@ def apply_pre_upscale_if_needed(image, config, verbose: bool = False):
     return upscale_image(image, factor, model_type=model_type, verbose=verbose), factor
 
 
-def process_page_vision(page, config, image_path="page.png", image_format: Optional[str] = None, verbose: bool = False):
+def process_page_vision(page, config, image_path="page.png", image_format: Optional[str] = None, verbose: bool = False, osb_payload: bool = False):
     """One page through the hot path in the reference's stage order: detect speech bubbles (+ SAM masks) -> OSB text stage (regions
     to FLUX or flat fill) -> bubble cleaning -> optional final upscale -> target mode.  `page` is the decoded PIL page already in its
     target mode (`load_page`); the result is what the reference hands to `save_image_with_compression` in `cleaning_only` mode.
@@ -354,11 +354,14 @@ def process_page_vision(page, config, image_path="page.png", image_format: Optio
     model leaves panels = None, the reference's own failure path.
     Returns `(page_out, info)` with the detections, the per-bubble cleaning records and the processing scale.
     = `process_page_vision_back(process_page_vision_front(...))`: the two halves exist so that a batch can keep two pages in flight
-    (`batch_process_images(process_front=, process_back=)`)."""
-    return process_page_vision_back(process_page_vision_front(page, config, image_path, image_format, verbose))
+    (`batch_process_images(process_front=, process_back=)`).
+    `osb_payload=True`: the OSB stage also builds the translation payload of its text boxes (crops, text colours; reference
+    `_build_outside_text_data`), returned under `info["outside_text"]`."""
+    return process_page_vision_back(process_page_vision_front(page, config, image_path, image_format, verbose, osb_payload=osb_payload))
 
 
-def process_page_vision_front(page, config, image_path="page.png", image_format: Optional[str] = None, verbose: bool = False) -> Dict:
+def process_page_vision_front(page, config, image_path="page.png", image_format: Optional[str] = None, verbose: bool = False,
+                              osb_payload: bool = False) -> Dict:
     """Front half of a page: target mode, optional initial upscale, stage-memo page switch, bubble detection (+ SAM masks), panels, and the
     OSB stage's PREPARE part (outside-text detection, masks, region grouping, the FLUX / flat-fill decision) — the stages whose host share is
     large and whose GPU work is small graphs on the models' own streams.  Returns the state `process_page_vision_back` finishes."""
@@ -371,7 +374,8 @@ def process_page_vision_front(page, config, image_path="page.png", image_format:
     if page.mode != target_mode:
         page = page.convert(target_mode)
     info = {"bubbles": [], "text_free_boxes": [], "cleaned": [], "processing_scale": 1.0}
-    state = {"config": config, "image_path": image_path, "verbose": verbose, "target_mode": target_mode, "info": info, "done": None, "work": None, "osb_error": None}
+    state = {"config": config, "image_path": image_path, "verbose": verbose, "target_mode": target_mode, "info": info, "done": None, "work": None, "osb_error": None,
+             "osb_payload": bool(osb_payload)}
     page, info["pre_upscale_factor"] = apply_pre_upscale_if_needed(page, config, verbose)      # :718-720, before anything looks at the page
     if getattr(config, "upscaling_only", False):
         out = page
@@ -413,7 +417,7 @@ def process_page_vision_front(page, config, image_path="page.png", image_format:
     info["panels"] = panels
     try:
         state["work"] = prepare_outside_text_work(page, config, image_path, image_format, verbose=verbose, bubble_data=bubbles,
-                                                  text_free_boxes=text_free, panels=panels)
+                                                  text_free_boxes=text_free, panels=panels, **({"build_payload": True} if osb_payload else {}))
     except Exception as e:      # noqa: BLE001 — raised again where `process_outside_text` would have raised it: in the back half
         state["osb_error"] = e
     state.update(page=page, scale=scale)
@@ -436,7 +440,9 @@ def process_page_vision_back(state: Dict):
         raise state["osb_error"]
     page, scale, det, bubbles = state["page"], state["scale"], config.detection, info["bubbles"]
     if state["work"] is not None:
-        page, _osb = finish_outside_text_work(state["work"])
+        page, osb_data = finish_outside_text_work(state["work"])
+        if state.get("osb_payload"):
+            info["outside_text"] = osb_data
     if bubbles:
         cl = config.cleaning
         try:

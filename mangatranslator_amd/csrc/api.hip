@@ -30,6 +30,7 @@ int clean_launch(const mtx_clean_args*, void*, const char**);
 int detr_launch(const mtx_detr_args*, void*, const char**);
 int quant_launch(const mtx_quant_args*, void*, const char**);
 int tail_launch(const mtx_tail_args*, void*, const char**);
+int textcolor_launch(const mtx_textcolor_args*, void*, const char**);
 
 static thread_local std::string g_err;
 
@@ -76,6 +77,7 @@ static int run_op(const mtx_op& op, void* stream) {
     case MTX_OP_DETR: rc = detr_launch(&op.u.detr, stream, &err); break;
     case MTX_OP_QUANT: rc = quant_launch(&op.u.quant, stream, &err); break;
     case MTX_OP_TAIL: rc = tail_launch(&op.u.tail, stream, &err); break;
+    case MTX_OP_TEXTCOLOR: rc = textcolor_launch(&op.u.tc, stream, &err); break;
     case MTX_OP_MEMSET:
       if (op.u.ms.bytes < 0 || (!op.u.ms.ptr && op.u.ms.bytes > 0)) { rc = MTX_ERR_INVALID; err = "memset: null pointer or negative size"; break; }
       fill_bytes_async(op.u.ms.ptr, op.u.ms.value, (size_t)op.u.ms.bytes, stream);        // a kernel: a captured hipMemsetAsync (memset node) did not always clear (mtx_device.h)
@@ -172,6 +174,7 @@ size_t mtx_abi_sizeof(int kind) {
     case MTX_OP_DETR: return sizeof(mtx_detr_args);
     case MTX_OP_QUANT: return sizeof(mtx_quant_args);
     case MTX_OP_TAIL: return sizeof(mtx_tail_args);
+    case MTX_OP_TEXTCOLOR: return sizeof(mtx_textcolor_args);
     case 100: return sizeof(mtx_clean_args);       /* op-level only (not a plan op) */
     default: return 0;
   }
@@ -235,6 +238,7 @@ MTX_OP_ENTRY(mtx_bubble_clean, mtx_clean_args, clean_launch)
 MTX_OP_ENTRY(mtx_detr, mtx_detr_args, detr_launch)
 MTX_OP_ENTRY(mtx_quantize_mx, mtx_quant_args, quant_launch)
 MTX_OP_ENTRY(mtx_page_tail, mtx_tail_args, tail_launch)
+MTX_OP_ENTRY(mtx_text_color, mtx_textcolor_args, textcolor_launch)
 
 
 int mtx_gemm_last_split(int* whole_tiles, int* k_slices, int* tail_pieces) {

@@ -232,4 +232,22 @@ MTX_API int mtx_host_mask_outline(const uint8_t* mask, int w, int h, int* xy, in
   return n;
 }
 
+// Contour step of the text-colour probe (reference core/outside_text_processor.py:1133-1144): cv2.findContours(RETR_EXTERNAL) ->
+// contourArea >= min_area -> cv2.drawContours(FILLED), one contour at a time, so the fills are OR-ed (no even-odd across contours).
+MTX_API int mtx_host_fill_components(const uint8_t* mask, int w, int h, double min_area, uint8_t* out) {
+  if (!mask || !out || w < 1 || h < 1) return MTX_ERR_INVALID;
+  std::memset(out, 0, (size_t)w * h);
+  std::vector<Blob> blobs;
+  external_contours(mask, w, h, blobs);
+  std::vector<uint8_t> inside;
+  int drawn = 0;
+  for (const Blob& b : blobs) {
+    if (!(b.area >= min_area)) continue;
+    ++drawn;
+    fill_inside(b.poly, w, h, inside);
+    for (size_t i = 0; i < inside.size(); ++i) if (inside[i]) out[i] = 255;
+  }
+  return drawn;
+}
+
 }  // extern "C"

@@ -15,6 +15,7 @@
 //   EDT_COLS / EDT_ROWS    the feathered composite weight: exact Euclidean distance to the mask inside a window of the blur radius.
 // All HBM-bound byte work: one thread per output pixel, coalesced rows; nothing here is reshaped into a GEMM.
 #include "mtx_device.h"
+#include "lab8.h"
 
 namespace mtx {
 
@@ -94,19 +95,7 @@ __global__ __launch_bounds__(256) void tail_composite_kernel(mtx_tail_args p) {
 
 // ---- OpenCV 8-bit RGB -> Lab (fixed point), shared by the two Lab kernels ------------------------------------------------------
 __device__ __forceinline__ void rgb_to_lab8(const mtx_tail_args& p, const uint8_t* px, int& L, int& A, int& B) {
-  const int r = p.gamma_tab[px[0]], g = p.gamma_tab[px[1]], b = p.gamma_tab[px[2]];
-  int f[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    int xyz = (r * p.lab_coef[c * 3] + g * p.lab_coef[c * 3 + 1] + b * p.lab_coef[c * 3 + 2] + (1 << 11)) >> 12;
-    xyz = xyz < 0 ? 0 : (xyz > p.cbrt_n - 1 ? p.cbrt_n - 1 : xyz);
-    f[c] = p.cbrt_tab[xyz];
-  }
-  const int lshift = -((16 * 255 * (1 << 15) + 50) / 100), h2 = 1 << 14;
-  L = (((116 * 255 + 50) / 100) * f[1] + lshift + h2) >> 15;
-  A = (500 * (f[0] - f[1]) + 128 * (1 << 15) + h2) >> 15;
-  B = (200 * (f[1] - f[2]) + 128 * (1 << 15) + h2) >> 15;
-  L = L < 0 ? 0 : (L > 255 ? 255 : L); A = A < 0 ? 0 : (A > 255 ? 255 : A); B = B < 0 ? 0 : (B > 255 ? 255 : B);
+  rgb_to_lab8(Lab8Tables{p.gamma_tab, p.cbrt_tab, p.lab_coef, p.cbrt_n}, px[0], px[1], px[2], L, A, B);      // lab8.h
 }
 
 // sums over the CONTEXT pixels (mask == 0) of both images: [n, L, L^2, a, b] of `src` (the generated patch) then [L, L^2, a, b] of

@@ -47,10 +47,12 @@ class MtxLibrary:
                         ("mtx_resize_threshold", abi.ResizeThreshArgs),
                         ("mtx_mask_select", abi.MaskSelectArgs), ("mtx_preprocess", abi.PreprocArgs),
                         ("mtx_yolo_decode", abi.YoloDecodeArgs), ("mtx_bubble_clean", abi.CleanArgs), ("mtx_detr", abi.DetrArgs),
-                        ("mtx_quantize_mx", abi.QuantArgs), ("mtx_page_tail", abi.TailArgs)):
+                        ("mtx_quantize_mx", abi.QuantArgs), ("mtx_page_tail", abi.TailArgs),
+                        ("mtx_text_color", abi.TextColorArgs)):
             getattr(d, name).argtypes = [C.POINTER(t), C.c_void_p]
         d.mtx_host_text_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.c_void_p, C.POINTER(C.c_int)]
+        d.mtx_host_fill_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         d.mtx_host_chamfer_l2_5x5.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         d.mtx_host_mask_outline.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         d.mtx_host_png_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]

@@ -47,10 +47,13 @@ def pin_rank_to_gpu_cpus() -> dict:
     return pin_host_threads_to_gpu(int(os.environ.get("LOCAL_RANK", "0")), n_devices=torch.cuda.device_count())
 
 
-def install(include_caching: bool = True, share_utils: bool = True, hardware_queues: "int | None" = None) -> list:
+def install(include_caching: bool = True, share_utils: bool = True, hardware_queues: "int | None" = None, osb_payload: bool = False) -> list:
     """-> the list of `core.*` module names now served by this package.  `include_caching=False` keeps the reference's own stage memo
     (needed when its translation / manga-ocr key builders are in use: this build restates the vision-side keys only).
-    `hardware_queues=16`: see `set_hardware_queues` (detect / segment / clean services; makes `batch_vision_images` pick two front workers)."""
+    `hardware_queues=16`: see `set_hardware_queues` (detect / segment / clean services; makes `batch_vision_images` pick two front workers).
+    `osb_payload=True`: the served `core.outside_text_processor` builds the translation payload of the outside-bubble text (crops, text
+    colours, `needs_text_background`) for the reference's unchanged `process_outside_text` call; off, it returns `(page, [])` and the OSB
+    text is removed from the page without being translated."""
     if hardware_queues is not None:
         set_hardware_queues(hardware_queues)
     if "core" in sys.modules and getattr(sys.modules["core"], "__file__", None):
@@ -78,4 +81,5 @@ def install(include_caching: bool = True, share_utils: bool = True, hardware_que
             continue
         sys.modules[f"core.{name}"] = importlib.import_module(f"mangatranslator_amd.core.{name}")
         served.append(f"core.{name}")
+    sys.modules["core.outside_text_processor"].set_default_build_payload(osb_payload)
     return served

@@ -12,7 +12,13 @@ wrapper per detector.
   collect(t)     ... or when the first of its tickets is collected (a page never waits for pages that may not come).  Each ticket then runs
                  the model's own per-image second half (`_finish`: candidates, NMS, page coordinates) on its slice of the decoded rows.
 
-Two buffer sets alternate, so the next batch fills while the previous one is collected.  Every kernel of a batched plan treats the images
+Nothing a model does per page is restated here: page intake and the letterbox plan are `YoloSegHip._page_in / _page_plan / _load_page`, RT-DETR's resize,
+query selection + decoder, post-processing and result object are `RTDetrHip._resized / _decode / _post / _result` — the one-page calls are compositions
+of the same methods.  `DetectorBatcher.submit` / `collect` hold the one slot / launch / ticket lifecycle; a model kind supplies `_new_set`, `_prepare`,
+`_upload`, `_run` and `_result`.
+
+Two buffer sets alternate, so the next batch fills while the previous one is collected; the sets of the four most recent page sizes are kept, and
+a size whose sets still hold a page is never the one that goes (the cache exceeds its bound until they drain).  Every kernel of a batched plan treats the images
 independently — same tiles, same arithmetic per image as the one-image plan — so a page's boxes do not depend on what else was in its batch
 (`tests/test_yolo11_sim.py`, `tests/test_yolo11_gpu.py`: byte-identical to the one-image call)."""
 import threading
@@ -21,7 +27,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from mangatranslator_amd.hip.plan import PlanBuilder, PlanCache, result_tensors
+from mangatranslator_amd.hip.plan import Act, PlanCache, result_tensors
 
 from .yolo import letterbox_params
 
@@ -29,19 +35,13 @@ from .yolo import letterbox_params
 class _Batch:
     """one buffer set: the batched network plan, a page buffer + letterbox plan per slot, and the bookkeeping of a fill / launch / collect cycle"""
 
-    def __init__(self, model, key, lp, size):
-        h0, w0, _ = key
+    def __init__(self, model, key, size):
+        h0, w0, imgsz = key
+        self.lp = lp = letterbox_params(h0, w0, imgsz)
         self.plan = model._build(lp, batch=size)
-        self.pre = []
-        for b in range(size):
-            pre = PlanBuilder(model.lib, model.device, model.dtype)
-            page = pre.buf((h0, w0, 3), torch.uint8)
-            slot = type(self.plan.img)(self.plan.img.t[b:b + 1], 1, self.plan.img.h, self.plan.img.w, self.plan.img.c, self.plan.img.c0)
-            pre.letterbox(page, slot, h0, w0, lp["nh"], lp["nw"], lp["top"], lp["left"])
-            pp = pre.build()
-            pp.page = page
-            self.pre.append(pp)
-        self.size, self.lp = size, lp
+        img = self.plan.img
+        self.pre = [model._page_plan(Act(img.t[b:b + 1], 1, img.h, img.w, img.c, img.c0), h0, w0, lp) for b in range(size)]
+        self.size = size
         self.filled = self.collected = 0
         self.launched = False
         # the first graph replay of a plan CAPTURES it, and a capture must not run beside other threads' GPU work (another front half's allocation or
@@ -101,9 +101,15 @@ class DetectorBatcher:
         self.names = model.names
         self._lane = model._lane
         self._cv = threading.Condition()
-        self._sets = PlanCache(4)           # (h0, w0, imgsz) -> [_Batch, _Batch]
-        self._filling = {}                  # key -> the _Batch that is taking slots
+        self._sets = PlanCache(4, may_evict=self._idle)      # (h0, w0, imgsz) -> [buffer set, buffer set]
+        self._filling = {}                  # key -> the buffer set that is taking slots
         self.stats = dict(pages=0, launches=0)
+
+    def close(self):
+        """destroys every buffer set (plans, graphs, activation buffers), in use or not: for the owner that drops the wrapper"""
+        with self._cv:
+            self._filling.clear()
+            self._sets.clear()
 
     # ---- the reference's call shape ----------------------------------------------------------------------------------------------------
     def __call__(self, image_bgr, conf=0.25, device=None, verbose=False, imgsz=640, iou=0.7, max_det=300, **_kw):
@@ -115,23 +121,15 @@ class DetectorBatcher:
         return self.collect(ticket)
 
     @torch.no_grad()
-    def submit(self, image_bgr, conf=0.25, imgsz=640, iou=0.7, max_det=300, **_kw):
-        m = self.model
-        on_device = torch.is_tensor(image_bgr) and image_bgr.device.type == m.device.type and m.device.type != "cpu"
-        img = image_bgr[..., :3] if on_device else np.ascontiguousarray(np.asarray(image_bgr)[..., :3])
-        h0, w0 = int(img.shape[0]), int(img.shape[1])
-        key = (h0, w0, imgsz)
+    def submit(self, page, **kw):
+        key, item, fields = self._prepare(page, **kw)
         with self._cv:
-            b = self._take_slot(key, letterbox_params(h0, w0, imgsz))
+            b = self._take_slot(key)
             slot = b.filled
             b.filled += 1
             try:
-                if on_device:
-                    self._lane.adopt(image_bgr)
                 with self._lane.enter():
-                    pp = b.pre[slot]
-                    pp.page.copy_(img if on_device else torch.from_numpy(img).to(m.device, non_blocking=True))
-                    pp.run()
+                    self._upload(b, slot, item)
                     if b.filled == b.size:
                         self._launch(b, key)
             except BaseException:
@@ -139,7 +137,7 @@ class DetectorBatcher:
                 raise
             self.stats["pages"] += 1
             self._cv.notify_all()
-        return BatchTicket(self, b, slot, key=key, hw=(h0, w0), conf=conf, iou=iou, max_det=max_det)
+        return BatchTicket(self, b, slot, key=key, **fields)
 
     @torch.no_grad()
     def collect(self, ticket):
@@ -150,20 +148,42 @@ class DetectorBatcher:
                     with self._lane.enter():
                         self._launch(b, ticket["key"])
             with self._lane.resume():
-                view = SimpleNamespace(decoded=b.plan.decoded[ticket.slot] if b.size > 1 else b.plan.decoded, proto=None)      # (a one-image plan has no image axis)
-                res = self.model._finish(view, b.lp, ticket["hw"], ticket["conf"], ticket["iou"], ticket["max_det"])
+                res = self._result(b, ticket)
             self._lane.hand_over(*result_tensors(res))
             return res
         finally:
             ticket.close()
 
+    # ---- what differs between the model kinds ------------------------------------------------------------------------------------------------
+    def _new_set(self, key):
+        return _Batch(self.model, key, self.batch)
+
+    def _prepare(self, image_bgr, conf=0.25, imgsz=640, iou=0.7, max_det=300, **_kw):
+        """host side of a submit, before the lock is taken -> (key of the buffer sets, what `_upload` gets, the ticket's fields)"""
+        img, on_device, h0, w0 = self.model._page_in(image_bgr)
+        return (h0, w0, imgsz), (image_bgr, img, on_device), dict(hw=(h0, w0), conf=conf, iou=iou, max_det=max_det)
+
+    def _upload(self, b, slot, item):
+        """on the wrapper's stream: the page into its slot of set `b`"""
+        image_bgr, img, on_device = item
+        if on_device:
+            self._lane.adopt(image_bgr)
+        self.model._load_page(b.pre[slot], img, on_device)
+
+    def _run(self, b):
+        b.plan.run(graph=self.model._graph)
+
+    def _result(self, b, ticket):
+        view = SimpleNamespace(decoded=b.plan.decoded[ticket.slot] if b.size > 1 else b.plan.decoded, proto=None)      # (a one-image plan has no image axis)
+        return self.model._finish(view, b.lp, ticket["hw"], ticket["conf"], ticket["iou"], ticket["max_det"])
+
     # ---- internals (called with the condition held) ---------------------------------------------------------------------------------------
-    def _take_slot(self, key, lp):
+    def _take_slot(self, key):
         b = self._filling.get(key)
         if b is not None and not b.launched and b.filled < b.size:
             return b
         if key not in self._sets:
-            self._sets[key] = [self._new_set(key, lp), self._new_set(key, lp)]
+            self._sets[key] = [self._new_set(key), self._new_set(key)]
         sets = self._sets[key]
         ok = self._cv.wait_for(lambda: any(s.filled == 0 for s in sets), timeout=self.WAIT_S)
         if not ok:
@@ -172,8 +192,12 @@ class DetectorBatcher:
         self._filling[key] = b
         return b
 
-    def _new_set(self, key, lp):
-        return _Batch(self.model, key, lp, self.batch)
+    def _idle(self, key, sets):
+        """may the cache close the sets of `key`?  Not while a page holds a slot: its ticket would collect from a destroyed plan"""
+        if any(s.filled for s in sets):
+            return False
+        self._filling.pop(key, None)
+        return True
 
     def _launch(self, b, key):
         self._run(b)
@@ -182,13 +206,12 @@ class DetectorBatcher:
         if self._filling.get(key) is b:
             del self._filling[key]
 
-    def _run(self, b):
-        b.plan.run(graph=self.model._graph)
-
     def _slot_done(self, b):
         with self._cv:
             b.collected += 1
             if b.collected >= b.filled:          # every page that took a slot has its results (or dropped its ticket): the buffer set is free again
+                if not b.launched:               # (all of them dropped before a launch: the next page of this size takes a free set afresh)
+                    self._filling = {k: s for k, s in self._filling.items() if s is not b}
                 b.filled = b.collected = 0
                 b.launched = False
                 self._cv.notify_all()
@@ -222,87 +245,26 @@ class _RTDetrBatch:
 class RTDetrBatcher(DetectorBatcher):
     """The same sharing for the RT-DETR-v2 secondary detector (`core/ml/rtdetr.py`): the backbone + hybrid encoder — two thirds of its GPU time, all
     small convolutions — runs once for the pages of a batch (`RTDetrHip._build(H, W, batch=B)`); query selection and the six decoder layers then
-    follow image by image on the same stream with the model's own arithmetic (`_enqueue`'s second half), so each page's boxes are the one-page call's."""
+    follow image by image on the same stream through the model's own `_decode` and `_post`, so each page's boxes are the one-page call's."""
 
-    def __init__(self, model, batch: int = 4, peers: int = 1):
-        super().__init__(model, batch, peers)
-
-    @torch.no_grad()
-    def submit(self, source, conf: float = 0.35, imgsz=None, **_kw):
-        from PIL import Image
-        m = self.model
-        if isinstance(source, Image.Image):
-            pil = source.convert("RGB") if source.mode != "RGB" else source
-        elif isinstance(source, np.ndarray):
-            arr = source
-            if arr.ndim == 2:
-                arr = np.stack([arr] * 3, -1)
-            pil = Image.fromarray(np.ascontiguousarray(arr[..., :3][..., ::-1]))      # cv2 BGR -> RGB, as the adapter does
-        else:
-            pil = Image.open(source).convert("RGB")
-        ow, oh = pil.size
-        size = int(imgsz) if imgsz is not None else 640
-        img = np.asarray(pil.resize((size, size), resample=Image.Resampling.BILINEAR))        # RTDetrImageProcessor: resize + 1/255 (host side, like the model's own submit)
-        key = (size, size, "rtdetr")
-        with self._cv:
-            b = self._take_slot(key, None)
-            slot = b.filled
-            b.filled += 1
-            b.meta[slot] = (oh, ow, float(conf))
-            try:
-                with self._lane.enter():
-                    b.enc.src[slot].copy_(torch.from_numpy(np.array(img, dtype=np.uint8)).to(m.device, non_blocking=True))
-                    if b.filled == b.size:
-                        self._launch(b, key)
-            except BaseException:
-                self._slot_done(b)
-                raise
-            self.stats["pages"] += 1
-            self._cv.notify_all()
-        return BatchTicket(self, b, slot, key=key)
-
-    @torch.no_grad()
-    def collect(self, ticket):
-        from .rtdetr import _Boxes
-        b = ticket.batch
-        try:
-            with self._cv:
-                if not b.launched:
-                    with self._lane.enter():
-                        self._launch(b, ticket["key"])
-            with self._lane.resume():
-                t = b.out[ticket.slot]
-                keep = t["keep"]
-                res = [SimpleNamespace(boxes=_Boxes(t["xyxy"][keep].float(), t["top_s"][keep].float(), t["labels"][keep].float()), names=self.model.names,
-                                       orig_shape=t["hw"], masks=None)]
-            self._lane.hand_over(*result_tensors(res))
-            return res
-        finally:
-            ticket.close()
-
-    def _new_set(self, key, lp):
+    def _new_set(self, key):
         return _RTDetrBatch(self.model, self.batch, key[:2])
 
+    def _prepare(self, source, conf: float = 0.35, imgsz=None, **_kw):
+        img, oh, ow = self.model._resized(source, imgsz)          # (host side, like the model's own submit)
+        return (img.shape[0], img.shape[1], "rtdetr"), (img, oh, ow, float(conf)), {}
+
+    def _upload(self, b, slot, item):
+        img, oh, ow, conf = item
+        b.meta[slot] = (oh, ow, conf)
+        b.enc.src[slot].copy_(torch.from_numpy(np.array(img, dtype=np.uint8)).to(self.model.device, non_blocking=True))
+
     def _run(self, b):
-        """on the wrapper's stream: the batched encoder graph, then per filled slot what `RTDetrHip._enqueue` / `submit` queue for one image"""
-        m, a, d = self.model, b.enc, b.dec
-        cfg = m.cfg
-        nc, Q, S = cfg.num_labels, cfg.num_queries, a.S
-        a.run(graph=m._graph)
+        """the batched encoder graph, then per filled slot what `RTDetrHip.submit` queues for one image"""
+        m = self.model
+        b.enc.run(graph=m._graph)
         for slot in range(b.filled):
-            rows = slice(slot * S, (slot + 1) * S)
-            top = a.scores[rows, :nc].max(-1).values.topk(Q, dim=0).indices
-            d.mem.copy_(a.mem[rows])
-            d.h0.copy_(a.om[rows].index_select(0, top))
-            d.ref_logit.copy_((a.boxes[rows] + a.anchors).index_select(0, top))
-            d.run(graph=m._graph)
-            logits, boxes = d.logits[:, :nc].clone(), d.boxes[:, :4].clone()
-            oh, ow, conf = b.meta[slot]
-            scores = logits.sigmoid()
-            k = min(Q, scores.numel())
-            top_s, idx = scores.flatten().topk(k)
-            labels, qi = idx % nc, idx // nc
-            cx, cy, w, h = boxes[qi].unbind(-1)
-            scale = torch.tensor([ow, oh, ow, oh], dtype=boxes.dtype).to(boxes.device, non_blocking=True)
-            xyxy = torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1) * scale
-            b.out[slot] = dict(xyxy=xyxy, top_s=top_s, labels=labels, keep=top_s > conf, hw=(oh, ow), logits=logits, boxes=boxes)
+            b.out[slot] = m._post(*m._decode(b.enc, b.dec, slice(slot * b.enc.S, (slot + 1) * b.enc.S)), *b.meta[slot])
+
+    def _result(self, b, ticket):
+        return self.model._result(**b.out[ticket.slot])

@@ -323,6 +323,8 @@ class ModelManager:
             return model
         w = self._batchers.get(slot)
         if w is None or w.model is not model or w.batch != self.detector_batch:
+            if w is not None:
+                w.close()                # the plans and graphs of the wrapper this one replaces
             w = self._batchers[slot] = cls(model, self.detector_batch, peers=self.detector_batch)
         return w
 
@@ -354,6 +356,9 @@ class ModelManager:
             self.models[model_type] = None
             for key in replicas:
                 del self.models[key]
+            w = self._batchers.pop(model_type, None)          # its batching wrapper (_maybe_batched) holds the model and batch-sized plans + graphs
+            if w is not None:
+                w.close()
             if force_gc:
                 empty_cache(self.device)
 
@@ -576,6 +581,8 @@ class ModelManager:
                     del self.models[model_type]
                 else:
                     self.models[model_type] = None
+            while self._batchers:
+                self._batchers.popitem()[1].close()
         self.clear_cache()
         log_message("All models unloaded.", verbose=verbose)
 

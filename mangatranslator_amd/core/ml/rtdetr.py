@@ -26,6 +26,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, AsyncLane, LaneTicket, PlanBuilder, PlanCache, result_tensors
 from ...utils.exceptions import ModelError
+from .yolo import _Boxes
 
 
 def _fold(w, bn, eps):
@@ -371,25 +372,14 @@ class RTDetrHip:
         H, W = img_u8.shape[:2]
         if H % 32 or W % 32:
             raise ModelError("RT-DETR input must be a multiple of 32")
-        cfg = self.cfg
         a, b = self.plans(H, W)
         a.src.copy_(torch.from_numpy(np.array(img_u8, dtype=np.uint8)).to(self.device).view(1, H, W, 3))
         a.run(graph=self._graph)
-        nc, Q = cfg.num_labels, cfg.num_queries
-        top = a.scores[:, :nc].max(-1).values.topk(Q, dim=0).indices
-        b.mem.copy_(a.mem)
-        b.h0.copy_(a.om.index_select(0, top))
-        b.ref_logit.copy_((a.boxes + a.anchors).index_select(0, top))
-        b.run(graph=self._graph)
-        return b.logits[:, :nc].clone(), b.boxes[:, :4].clone()
+        return self._decode(a, b, slice(None))
 
-    def __call__(self, source, conf: float = 0.35, device=None, verbose: bool = False, imgsz=None, **_kw):
-        return self.collect(self.submit(source, conf=conf, imgsz=imgsz))
-
-    @torch.no_grad()
-    def submit(self, source, conf: float = 0.35, imgsz=None, **_kw):
-        """first half of a call (see hip/plan.py `AsyncLane`): the host-side resize, then upload, backbone + encoder graph, query
-        selection and decoder graph queued on this model's own stream; nothing here waits for the GPU"""
+    # ---- the per-image steps: `submit` / `collect` below and the cross-page batches of core/ml/detector_batch.py are compositions of these ----
+    def _resized(self, source, imgsz=None):
+        """a page (PIL image, cv2 BGR array or path) -> (RGB uint8 [size, size, 3] on the host, original height, width)"""
         if isinstance(source, Image.Image):
             pil = source.convert("RGB") if source.mode != "RGB" else source
         elif isinstance(source, np.ndarray):
@@ -401,43 +391,57 @@ class RTDetrHip:
             pil = Image.open(source).convert("RGB")
         ow, oh = pil.size
         size = int(imgsz) if imgsz is not None else 640
-        img = np.asarray(pil.resize((size, size), resample=Image.Resampling.BILINEAR))        # RTDetrImageProcessor: resize + 1/255
+        return np.asarray(pil.resize((size, size), resample=Image.Resampling.BILINEAR)), oh, ow        # RTDetrImageProcessor: resize + 1/255
+
+    def _decode(self, a, b, rows):
+        """query selection and the decoder for ONE image of encoder plan `a`, whose tokens are `rows` of its outputs (`slice(None)`: the one-image
+        plan), through decoder plan `b` -> (logits [Q, C] fp32, boxes cxcywh [Q, 4] fp32 in 0..1)"""
+        nc, Q = self.cfg.num_labels, self.cfg.num_queries
+        top = a.scores[rows, :nc].max(-1).values.topk(Q, dim=0).indices
+        b.mem.copy_(a.mem[rows])
+        b.h0.copy_(a.om[rows].index_select(0, top))
+        b.ref_logit.copy_((a.boxes[rows] + a.anchors).index_select(0, top))
+        b.run(graph=self._graph)
+        return b.logits[:, :nc].clone(), b.boxes[:, :4].clone()
+
+    def _post(self, logits, boxes, oh, ow, conf):
+        """HF `post_process_object_detection`: sigmoid, top-k over queries x classes, boxes in page pixels -> the fields of a ticket"""
+        nc = self.cfg.num_labels
+        scores = logits.sigmoid()
+        k = min(self.cfg.num_queries, scores.numel())
+        top_s, idx = scores.flatten().topk(k)
+        labels, qi = idx % nc, idx // nc
+        cx, cy, w, h = boxes[qi].unbind(-1)
+        scale = torch.tensor([ow, oh, ow, oh], dtype=boxes.dtype).to(boxes.device, non_blocking=True)
+        xyxy = torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1) * scale
+        return dict(xyxy=xyxy, top_s=top_s, labels=labels, keep=top_s > float(conf), hw=(oh, ow))
+
+    def _result(self, xyxy, top_s, labels, keep, hw):
+        return [SimpleNamespace(boxes=_Boxes(xyxy[keep].float(), top_s[keep].float(), labels[keep].float()), names=self.names, orig_shape=hw, masks=None)]
+
+    def __call__(self, source, conf: float = 0.35, device=None, verbose: bool = False, imgsz=None, **_kw):
+        return self.collect(self.submit(source, conf=conf, imgsz=imgsz))
+
+    @torch.no_grad()
+    def submit(self, source, conf: float = 0.35, imgsz=None, **_kw):
+        """first half of a call (see hip/plan.py `AsyncLane`): the host-side resize, then upload, backbone + encoder graph, query
+        selection and decoder graph queued on this model's own stream; nothing here waits for the GPU"""
+        img, oh, ow = self._resized(source, imgsz)
         self._lane.acquire()
         try:
             with self._lane.enter():
-                logits, boxes = self._enqueue(img)
-                nc = self.cfg.num_labels
-                scores = logits.sigmoid()
-                k = min(self.cfg.num_queries, scores.numel())
-                top_s, idx = scores.flatten().topk(k)
-                labels, qi = idx % nc, idx // nc
-                cx, cy, w, h = boxes[qi].unbind(-1)
-                scale = torch.tensor([ow, oh, ow, oh], dtype=boxes.dtype).to(boxes.device, non_blocking=True)
-                xyxy = torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1) * scale
-                keep = top_s > float(conf)
+                fields = self._post(*self._enqueue(img), oh, ow, conf)
         except BaseException:
             self._lane.release()
             raise
-        return LaneTicket(self._lane, xyxy=xyxy, top_s=top_s, labels=labels, keep=keep, hw=(oh, ow))
+        return LaneTicket(self._lane, **fields)
 
     @torch.no_grad()
     def collect(self, t):
         try:
             with self._lane.resume():
-                keep = t["keep"]
-                res = [SimpleNamespace(boxes=_Boxes(t["xyxy"][keep].float(), t["top_s"][keep].float(), t["labels"][keep].float()), names=self.names,
-                                       orig_shape=t["hw"], masks=None)]
+                res = self._result(**t)
             self._lane.hand_over(*result_tensors(res))
             return res
         finally:
             t.close() if isinstance(t, LaneTicket) else self._lane.release()
-
-
-class _Boxes:
-    """the slice of ultralytics `Boxes` the detection operator reads (reference core/ml/rtdetr_adapter.py:18-30)"""
-
-    def __init__(self, xyxy, conf, cls):
-        self.xyxy, self.conf, self.cls = xyxy, conf, cls
-
-    def __len__(self):
-        return int(self.xyxy.shape[0])

@@ -106,19 +106,23 @@ class YoloSegHip:
         return derive_arch(sd)
 
     # ---- weights ------------------------------------------------------------------------------------
+    COUT_ROUND = 1          # packed output channels are rounded up to a multiple of this (Yolo11Hip: 8)
+
+    def _put(self, name, w, b, cout_pad=0, cin_pad=0):
+        """conv weight [co, ci, kh, kw] -> self.W[name] = (taps [co_p, kh * kw, ci_p] zero-padded, bias [co_p], co_p, kh)"""
+        co, ci, kh, kw = w.shape
+        ci_p = max((ci + 7) // 8 * 8, cin_pad)
+        r = self.COUT_ROUND
+        co_p = max((co + r - 1) // r * r, cout_pad)
+        wt = torch.zeros(co_p, kh * kw, ci_p)
+        wt[:co, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
+        bt = torch.zeros(co_p)
+        bt[:co] = b
+        self.W[name] = (wt.to(self.device, self.tdt).contiguous(), bt.to(self.device).contiguous(), co_p, kh)
+
     def _pack(self, sd):
         self.W = {}
-
-        def put(name, w, b, cout_pad=0, cin_pad=0):
-            co, ci, kh, kw = w.shape
-            ci_p = max((ci + 7) // 8 * 8, cin_pad)
-            co_p = max(co, cout_pad)
-            wt = torch.zeros(co_p, kh * kw, ci_p)
-            wt[:co, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-            bt = torch.zeros(co_p)
-            bt[:co] = b
-            self.W[name] = (wt.to(self.device, self.tdt).contiguous(), bt.to(self.device).contiguous(), co_p, kh)
-
+        put = self._put
         for k in sd:
             if k.endswith(".conv.weight"):
                 base = k[:-len(".conv.weight")]
@@ -246,15 +250,32 @@ class YoloSegHip:
     def __call__(self, image_bgr, conf=0.25, device=None, verbose=False, imgsz=640, retina_masks=True, iou=0.7, max_det=300):
         return self.collect(self.submit(image_bgr, conf=conf, imgsz=imgsz, iou=iou, max_det=max_det))
 
+    # ---- page intake: shared with the cross-page batches of core/ml/detector_batch.py ---------------------------------
+    def _page_in(self, image_bgr):
+        """-> (img, on_device, h0, w0).  A page that is already on the device (uint8 [H, W, 3] BGR tensor: the caller uploaded it once for all
+        of its detectors) is used in place; a host image is uploaded by `_load_page`"""
+        on_device = torch.is_tensor(image_bgr) and image_bgr.device.type == self.device.type and self.device.type != "cpu"
+        img = image_bgr[..., :3] if on_device else np.ascontiguousarray(np.asarray(image_bgr)[..., :3])
+        return img, on_device, int(img.shape[0]), int(img.shape[1])
+
+    def _page_plan(self, dst, h0, w0, lp):
+        """a page buffer (`.page`) and the plan that letterboxes it into `dst`, the network's image `Act` (one image of it for a batched plan)"""
+        pre = PlanBuilder(self.lib, self.device, self.dtype)
+        page = pre.buf((h0, w0, 3), torch.uint8)
+        pre.letterbox(page, dst, h0, w0, lp["nh"], lp["nw"], lp["top"], lp["left"])
+        pp = pre.build()
+        pp.page = page
+        return pp
+
+    def _load_page(self, pp, img, on_device):
+        pp.page.copy_(img if on_device else torch.from_numpy(img).to(self.device, non_blocking=True))
+        pp.run()
+
     @torch.no_grad()
     def submit(self, image_bgr, conf=0.25, imgsz=640, iou=0.7, max_det=300, **_kw):
         """first half of a call: upload, letterbox and the network's graph replay are queued on this model's own stream (`AsyncLane`)
         and the call returns at once with a ticket for `collect`.  The model stays busy until the ticket is collected."""
-        # a page that is already on the device (uint8 [H, W, 3] BGR tensor: the caller uploaded it once for all of its detectors) is
-        # used in place; a host image is uploaded here
-        on_device = torch.is_tensor(image_bgr) and image_bgr.device.type == self.device.type and self.device.type != "cpu"
-        img = image_bgr[..., :3] if on_device else np.ascontiguousarray(np.asarray(image_bgr)[..., :3])
-        h0, w0 = int(img.shape[0]), int(img.shape[1])
+        img, on_device, h0, w0 = self._page_in(image_bgr)
         lp = letterbox_params(h0, w0, imgsz)
         key = (h0, w0, imgsz)
         self._lane.acquire()
@@ -264,15 +285,9 @@ class YoloSegHip:
             with self._lane.enter():
                 if key not in self._plans:
                     plan = self._build(lp)
-                    pre = PlanBuilder(self.lib, self.device, self.dtype)
-                    page = pre.buf((h0, w0, 3), torch.uint8)
-                    pre.letterbox(page, plan.img, h0, w0, lp["nh"], lp["nw"], lp["top"], lp["left"])
-                    pp = pre.build()
-                    pp.page = page
-                    self._plans[key] = (plan, pp)
+                    self._plans[key] = (plan, self._page_plan(plan.img, h0, w0, lp))
                 plan, pp = self._plans[key]
-                pp.page.copy_(img if on_device else torch.from_numpy(img).to(self.device, non_blocking=True))
-                pp.run()
+                self._load_page(pp, img, on_device)
                 plan.run(graph=self._graph)
         except BaseException:
             self._lane.release()

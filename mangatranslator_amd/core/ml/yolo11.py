@@ -47,19 +47,12 @@ class Yolo11Hip(YoloSegHip):
         return dict(family=family, head=hi, c=c, nc=nc, nm=nm, seg=seg, reg_max=reg_max)
 
     # ---- weights ------------------------------------------------------------------------------------------------------
+    COUT_ROUND = 8
+
     def _pack(self, sd):
         self.W, self.DW, self.sd_shapes = {}, {}, {k: tuple(v.shape) for k, v in sd.items()}
         hi = self.a["head"]
-
-        def put(name, w, b, cout_pad=0, cin_pad=0):
-            co, ci, kh, kw = w.shape
-            ci_p = max((ci + 7) // 8 * 8, cin_pad)
-            co_p = max((co + 7) // 8 * 8, cout_pad)
-            wt = torch.zeros(co_p, kh * kw, ci_p)
-            wt[:co, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-            bt = torch.zeros(co_p)
-            bt[:co] = b
-            self.W[name] = (wt.to(self.device, self.tdt).contiguous(), bt.to(self.device).contiguous(), co_p, kh)
+        put = self._put
 
         def put_dw(name, w, b):          # depthwise [C, 1, k, k] -> taps [k*k, C]
             c, _, kh, kw = w.shape

@@ -138,11 +138,12 @@ class Plan:
 
 class PlanCache:
     """shape-keyed plans with a bound: every plan pins its own activation buffers, and bubble crops / intermediate upscale passes come in
-    arbitrary sizes, so an unbounded dict grows device memory with every new size.  Least recently used plans are destroyed."""
+    arbitrary sizes, so an unbounded dict grows device memory with every new size.  Least recently used plans are destroyed — where the owner
+    gave `may_evict(key, value)`, only entries it releases: the cache stays over its bound while the others are in use."""
 
-    def __init__(self, capacity: int = 8):
+    def __init__(self, capacity: int = 8, may_evict=None):
         from collections import OrderedDict
-        self.capacity, self._d = max(1, int(capacity)), OrderedDict()
+        self.capacity, self.may_evict, self._d = max(1, int(capacity)), may_evict, OrderedDict()
 
     def __contains__(self, key):
         return key in self._d
@@ -157,11 +158,17 @@ class PlanCache:
     def __setitem__(self, key, value):
         self._d[key] = value
         self._d.move_to_end(key)
-        while len(self._d) > self.capacity:
-            _, old = self._d.popitem(last=False)
-            for p in (old if isinstance(old, (tuple, list)) else (old,)):
-                if hasattr(p, "close"):
-                    p.close()
+        for k in list(self._d)[:-1]:           # oldest first; never the entry that was just set
+            if len(self._d) <= self.capacity:
+                break
+            if self.may_evict is None or self.may_evict(k, self._d[k]):
+                self._close(self._d.pop(k))
+
+    @staticmethod
+    def _close(old):
+        for p in (old if isinstance(old, (tuple, list)) else (old,)):
+            if hasattr(p, "close"):
+                p.close()
 
     def get(self, key, default=None):
         return self[key] if key in self._d else default
@@ -174,10 +181,7 @@ class PlanCache:
 
     def clear(self):
         while self._d:
-            _, old = self._d.popitem(last=False)
-            for p in (old if isinstance(old, (tuple, list)) else (old,)):
-                if hasattr(p, "close"):
-                    p.close()
+            self._close(self._d.popitem(last=False)[1])
 
 
 class PlanBuilder:

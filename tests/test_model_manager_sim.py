@@ -231,6 +231,36 @@ def test_front_replicas_are_separate_instances_of_the_same_checkpoint(manager):
     assert all(not isinstance(k, tuple) for k in manager.models)
 
 
+def test_unload_closes_the_batching_wrapper(manager):
+    """`detector_batch` > 1: the panel detector is handed out behind a DetectorBatcher that holds the model and batch-sized plans; unloading the
+    type drops the wrapper and destroys its buffer sets, and a wrapper that is replaced (another batch size) is closed first"""
+    from oracle import yolo11_ref as y11
+    from mangatranslator_amd.core.ml.detector_batch import DetectorBatcher
+    from mangatranslator_amd.core.ml.model_manager import ModelType
+    net = y11.make_model("11", "n", 2, False, seed=1)
+    path = manager.model_paths[ModelType.YOLO_PANEL]
+    path.parent.mkdir(parents=True, exist_ok=True)
+    save_file({k: v.contiguous() for k, v in net.state_dict().items()}, str(path), metadata={"names": repr({0: "body", 1: "frame"})})
+    page = (np.random.default_rng(0).random((32, 64, 3)) * 255).astype(np.uint8)
+    manager.detector_batch = 2
+    try:
+        first = manager.load_yolo_panel()
+        assert isinstance(first, DetectorBatcher) and manager._batchers[ModelType.YOLO_PANEL] is first
+        first(page, conf=0.0, imgsz=64, max_det=5)
+        first_sets = list(first._sets[(32, 64, 64)])
+        manager.detector_batch = 3
+        wrapper = manager.load_yolo_panel()
+        assert wrapper is not first and wrapper.batch == 3 and len(first._sets) == 0 and all(not s.plan._h for s in first_sets), "the replaced wrapper was closed"
+        assert len(wrapper(page, conf=0.0, imgsz=64, max_det=5)[0].boxes) == 5
+        sets = list(wrapper._sets[(32, 64, 64)])
+        assert all(s.plan._h for s in sets)
+        manager.unload_model(ModelType.YOLO_PANEL)
+        assert ModelType.YOLO_PANEL not in manager._batchers and not manager.is_loaded(ModelType.YOLO_PANEL)
+        assert len(wrapper._sets) == 0 and all(not s.plan._h and not any(p._h for p in s.pre) for s in sets), "the wrapper's buffer sets were destroyed"
+    finally:
+        manager.detector_batch = 1
+
+
 def test_preload_order_worker_thread_reads_and_legacy_names(manager, monkeypatch):
     """(1) `preload_for_config` asks the loaders in one fixed order whatever fails on the way; (2) inside `thread_local_reads` a
     loader reads its checkpoint itself — no status / tensor broadcast, even with a process group up (the order of worker threads' calls is

@@ -109,6 +109,39 @@ def check(lib, device, family="11", scale="n", seg=False, h=96, w=64, imgsz=64, 
     return box_err, e_cls
 
 
+def pack_digests(lib):
+    """sha256 of everything `_pack` leaves in `W` (and `DW`) — names, padded weights and biases as stored (f16 / f32 bytes), `cout`, `k`, the qkv
+    geometry — for the seeded YOLOv8n-seg, YOLO11n, YOLO11n-seg and YOLO12n state dicts of the simulator tests.  The recorded values
+    (tests/golden/yolo_pack_digests.json, written by tests/golden/make_yolo_pack_digests.py) pin the packed layout."""
+    import hashlib
+    from mangatranslator_amd.core.ml.yolo import YoloSegHip
+    from oracle import yolo_ref
+
+    def feed(h, v):
+        if torch.is_tensor(v):
+            t = v.detach().cpu().contiguous()
+            h.update(f"{t.dtype}{tuple(t.shape)}".encode())
+            h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+        elif isinstance(v, (tuple, list)):
+            for x in v:
+                feed(h, x)
+        else:
+            h.update(repr(v).encode())
+
+    def digest(model):
+        h = hashlib.sha256()
+        for table in (model.W, getattr(model, "DW", {})):
+            for name in sorted(table):
+                h.update(name.encode())
+                feed(h, table[name])
+        return h.hexdigest()
+
+    out = {"yolov8n-seg": digest(YoloSegHip(yolo_ref.make_model("n", 1, 0).state_dict(), device="cpu", lib=lib))}
+    for tag, (family, seg, seed) in {"yolo11n": ("11", False, 0), "yolo11n-seg": ("11", True, 2), "yolo12n": ("12", False, 3)}.items():
+        out[tag] = digest(Yolo11Hip(yr.make_model(family, "n", 1, seg, seed=seed).state_dict(), device="cpu", lib=lib))
+    return out
+
+
 def check_batched(lib, device, family="11", scale="n", h=96, w=64, imgsz=64, pages=3, batch=4, seed=0, threads=False):
     """core/ml/detector_batch.py: `pages` different pages through ONE batched graph replay (DetectorBatcher) give, page by page, the bytes of the
     one-image call — decoded head rows and final boxes / scores / classes.  threads: every page submitted and collected by its own thread (the

@@ -69,8 +69,18 @@ typedef enum mtx_act {
  *   time) — ldy/ldres then describe the shuffled tensor.
  * chan_sum (optional, fp32 [N][tiles][Cout]): per-tile sums of act(conv(x) + bias) as rounded to the storage type — BEFORE out_scale
  *   and before the residual — for a fused global average pool; tiles = mtx_conv2d_tiles().  Both conv kernels (the 64 -> 64
- *   persistent one and the generic one) sum this same quantity.  With out_scale the 64 -> 64 kernel computes
- *   out_scale * act(..) + res_scale * res in fp32 and rounds once; the generic kernel rounds act(..) to the storage type first.   */
+ *   persistent one and the generic one) sum this same quantity.
+ * Rounding points (round_T = one round-to-nearest-even to the storage type; everything between two of them is fp32; pinned bit for
+ * bit on integer operands by tests/exact_checks.py::check_conv_exact).  With v = conv(x) + bias:
+ *   generic kernel (csrc/conv.hip):   t = round_T(act(v)) ALWAYS comes first — it passes through an LDS tile in the storage type.  Without
+ *       out_scale and res, y = t.  Otherwise y = round_T(out_scale * t + res_scale * res): two roundings.
+ *       act_after_res (with a res): t = round_T(v), y = round_T(act(t + res_scale * res)).
+ *   64 -> 64 kernel (csrc/conv_c64.hip: ksize 3, stride 1, cin <= 64, cout <= 64, no act_after_res, not chan_sum together with res, tensors
+ *       below 4 GB): y = round_T(out_scale * act(v) + res_scale * res), ONE rounding, on interior and border tiles alike, whether or not
+ *       sums are asked for (the sums alone see round_T(act(v))).
+ *   So the bytes of a 64 -> 64 conv with a residual or an out_scale depend on whether chan_sum AND res are both given (that pair runs on
+ *   the generic kernel).  Power-of-two out_scale factors commute with round_T: the two kernels then differ through the residual only.
+ *   Outputs beyond valid_hw are zero and enter no sum on either kernel.   */
 typedef struct mtx_conv2d_args {
   const void* x; const void* w; const float* bias; const void* res; void* y; float* chan_sum;
   int32_t n, h, w_in, cin, cout;
@@ -95,10 +105,21 @@ typedef struct mtx_conv2d_args {
 } mtx_conv2d_args;
 
 /* C[M,N] = epilogue(A[M,K] * W[N,K]^T)   A row stride lda, C row stride ldc (elements).
- *   v = acc + bias[n];  v = act(v);  v = v * (gate ? gate[gate_row(m), n] : 1) ;
+ *   v = alpha * acc + bias[n];  v = act(v);  v = v * (gate ? gate[gate_row(m), n] : 1) ;
  *   v += res ? res[m, n] : 0
  * gate rows: gate_row(m) = m / gate_rows_per (broadcast a per-sample modulation vector).
- * batch > 1: strided batched GEMM (a/w/c advance by *_bstride elements).                    */
+ * batch > 1: strided batched GEMM (a/w/c advance by *_bstride elements).
+ * Rounding points (round_T = one round-to-nearest-even to the 16-bit output type; acc and everything between two roundings is fp32;
+ * pinned bit for bit on integer operands by tests/exact_checks.py::check_gemm_exact):
+ *   16-bit output, every kernel (128-tile, 256-tile, its K-slice tail — whose fp32 partials are added in slice order before the epilogue —
+ *   and the fp8-operand kernel, which shares the 256-tile epilogue; vector and scalar store tails alike):
+ *       t = round_T(act(alpha * acc + bias))                 the tile passes through LDS in the output type
+ *       c = t                                                without gate and res: ONE rounding
+ *       c = round_T(t * gate + res)                          with a gate and / or a residual: TWO roundings (product and sum in fp32, not contracted)
+ *   out_dtype == MTX_F32 (16-bit operands) and dtype == MTX_F32 (which has no gate): no rounding, c = act(alpha * acc + bias) * gate + res in fp32.
+ *   fp8 operands: acc already carries the MX block scales (applied by the matrix instruction per 32 k); the epilogue is the one above.
+ *   The SwiGLU + MX-fp8 epilogue (glu_q): a = round_T(alpha * acc_a), b = round_T(alpha * acc_b), h = round_T(silu(a) * b), then the
+ *   quantiser's rounding of h to e4m3 — the roundings of the two launches it replaces.                    */
 typedef struct mtx_gemm_args {
   const void* a; const void* w; const float* bias; const void* res; const void* gate; void* c;
   int64_t m, n, k;

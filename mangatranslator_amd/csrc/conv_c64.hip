@@ -511,9 +511,9 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(ConvC64Params p) {
               float f[4];
 #pragma unroll
               for (int r = 0; r < 4; ++r) f[r] = apply_act_t<ACT>(acc[i][j][r] + b4[r], p.act, p.act_param);
-              if (want_sum && pix_ok[i] && pix_in[i] && ch_ok) {   // pooled statistics of the values as stored (rounded to T)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { f[r] = to_f32(from_f32<T>(f[r])); csum[j][r] += f[r]; }
+              if (want_sum && pix_ok[i] && pix_in[i] && ch_ok) {   // pooled statistics of act(..) as rounded to T; f itself stays fp32, as on the
+#pragma unroll                                            // interior path: with out_scale the stored value is rounded ONCE on every tile (mtx_hip.h)
+                for (int r = 0; r < 4; ++r) csum[j][r] += to_f32(from_f32<T>(f[r]));
               }
               if (p.out_scale != nullptr) {
 #pragma unroll

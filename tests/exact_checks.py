@@ -1,0 +1,444 @@
+"""Exact-arithmetic checks of the matrix-pipe kernels (GEMM, conv, attention) against float64 references.
+
+On integer-valued operands every product and every fp32 partial sum below 2^24 is exact in ANY summation order, so the result of a
+GEMM or a conv is one known value per element and the only freedom a kernel has left is WHERE it rounds to the 16-bit storage type.
+Those rounding points are a contract (include/mtx_hip.h, mtx_gemm_args / mtx_conv2d_args); here they are restated on a float64
+reference — `.float().to(T)` at each documented point — and the kernel's bytes must equal it: zero differing elements.  A wrong
+rounding mode, a lost or doubled k element, a K-slice merge that loses bits, a tile written twice: each moves at least one element.
+
+Every case asserts its own preconditions FROM THE REFERENCE ALONE before it looks at the kernel, so a shape that stops testing
+anything fails loudly: (a) exactness — the largest possible partial sum is below 2^24; (b) the f16 range — max |ref| < 60000;
+(c) at least 20 % of the outputs lie where T really rounds integers (|v| >= 2^8 for bf16, >= 2^11 for f16).
+
+Attention cannot be exact (a division), but on dyadic operands its numerator and denominator are: what is left is ONE rounding to T
+plus a few fp32 ulp of the reciprocal — the bound is (0.5 + 2^-10) spacings of T at the reference value.
+
+Same layout as op_checks.py: written once, run on the simulator (small shapes) and on the product library (production shapes)."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from mangatranslator_amd.hip import abi
+from mangatranslator_amd.hip.plan import PlanBuilder
+from op_checks import TD, _dev, _run, _sync
+
+EXACT = float(1 << 24)                                   # integers below are exact in fp32, sums of them in any order
+ROUNDS_FROM = {abi.BF16: 256.0, abi.F16: 2048.0}         # T's spacing exceeds 1 from here on: integers really get rounded
+INT_CAP = {abi.BF16: 256, abi.F16: 2048}                 # every integer up to here is representable in T (bias / residual range)
+SIGMA = {abi.BF16: 400.0, abi.F16: 3000.0}               # aimed standard deviation of the accumulators: about half of them beyond ROUNDS_FROM
+F16_LIMIT = 60000.0
+MANT = {abi.BF16: 7, abi.F16: 10}
+MIN_EXP = {abi.BF16: -126, abi.F16: -14}
+
+
+def _ints(g, shape, r):
+    return torch.randint(-r, r + 1, shape, generator=g, device=g.device).double()
+
+
+def _round(v, td):
+    """one rounding to the storage type, of float64 values that are exact in fp32"""
+    return v.float().to(td).double()
+
+
+def _act(v, act, slope):
+    if act == abi.ACT_NONE:
+        return v
+    if act == abi.ACT_RELU:
+        return v.clamp_min(0.0)
+    assert act == abi.ACT_LEAKY and math.log2(slope) == int(math.log2(slope)), "exact cases: NONE, RELU, LEAKY with a power-of-two slope"
+    return torch.where(v > 0, v, v * slope)
+
+
+def operand_range(dtype, k, cap=64, with_alpha=True, spread=1.0):
+    """integer range r ([-r, r], variance r (r + 1) / 3) and power-of-two alpha that put the standard deviation sqrt(k) r (r + 1) / 3 * alpha
+    of a K-long sum of products just above spread * SIGMA[dtype]: the smallest such figure over r <= cap and alpha = 2^j (a conv has no alpha: the smallest r)"""
+    best, target = None, spread * SIGMA[dtype]
+    for r in range(1, cap + 1):
+        s = math.sqrt(k) * r * (r + 1) / 3.0
+        alpha = 1.0
+        if not with_alpha:
+            if s >= target:
+                return r, 1.0
+            continue
+        while s * alpha < target:
+            alpha *= 2.0
+        if best is None or s * alpha < best[0] or (s * alpha == best[0] and alpha < best[2]):
+            best = (s * alpha, r, alpha)
+    return best[1], best[2]
+
+
+def _assert_rounding_share(ref, dtype, what):
+    if dtype == abi.F16:
+        assert float(ref.abs().max()) < F16_LIMIT, f"{what}: precondition (b) — max |ref| {float(ref.abs().max())} leaves the f16 range"
+    share = float((ref.abs() >= ROUNDS_FROM[dtype]).double().mean())
+    assert share >= 0.20, f"{what}: precondition (c) — only {share:.1%} of the outputs lie where the storage type rounds"
+    return share
+
+
+def _assert_equal(got, ref, what):
+    got = got.double()
+    if not torch.equal(got, ref):
+        bad = (got != ref).nonzero()
+        i = tuple(int(v) for v in bad[0])
+        raise AssertionError(f"{what}: {bad.shape[0]} of {ref.numel()} elements differ from the float64 reference with the contract's rounding; "
+                             f"first at {i}: got {float(got[i])}, want {float(ref[i])}")
+
+
+# ---- GEMM ---------------------------------------------------------------------------------------------------------------------------------
+def check_gemm_exact(lib, dtype, m, n, k, act=abi.ACT_NONE, with_bias=True, with_res=False, with_gate=False, out_f32=False, batch=1,
+                     seed=0, flags=0, runs=1, expect_split=None, w_lo=False, res_f32=False, f8=False, slope=0.25):
+    """The contract of the 16-bit and fp8-operand GEMM kernels (include/mtx_hip.h, mtx_gemm_args):
+         t = act(alpha * acc + bias);  16-bit output: t = round_T(t);  with a gate and / or a residual: c = round_T(t * gate + res), else c = t;
+         fp32 output: no rounding at all.
+    f8: the operands go through mtx_quantize_mx first (integers in [-7, 7] survive MX e4m3 exactly: the block scale is a power of two and 7
+    has three significant bits).  w_lo: W = w + w_lo, both halves integer.  Returns the share of outputs beyond T's integer range."""
+    dev, td = _dev(lib), TD[dtype]
+    g = torch.Generator(device=dev).manual_seed(seed)          # operands and the float64 reference live on the device: production shapes stay cheap
+    what = f"gemm {batch}x{m}x{n}x{k}"
+    r, alpha = operand_range(dtype, k * (2 if w_lo else 1), cap=7 if f8 else 64)
+    a, w = _ints(g, (batch, m, k), r), _ints(g, (batch, n, k), r)
+    wl = _ints(g, (batch, n, k), r) if w_lo else None
+    b = _ints(g, (n,), INT_CAP[dtype]) if with_bias else None
+    wsum = w + wl if w_lo else w
+    bound = k * float(a.abs().max()) * float(wsum.abs().max()) * alpha + (float(b.abs().max()) if b is not None else 0.0)
+    assert bound < EXACT, f"{what}: precondition (a) — partial sums up to {bound} are not exact in fp32"
+    t = torch.einsum("bmk,bnk->bmn", a, wsum) * alpha
+    if b is not None:
+        t = t + b
+    t = _act(t, act, slope)
+    if not out_f32:
+        t = _round(t, td)
+    gate = res = None
+    rows_per = max(m // 2, 1)
+    if with_gate:
+        gate = torch.tensor([-2.0, -1.0, 1.0, 2.0], dtype=torch.float64, device=dev)[torch.randint(0, 4, ((m + rows_per - 1) // rows_per, n), generator=g, device=dev)]
+    if with_res:
+        res = _ints(g, (batch, m, n), INT_CAP[dtype])
+    if gate is not None or res is not None:
+        bound = float(t.abs().max()) * (2.0 if gate is not None else 1.0) + (INT_CAP[dtype] if res is not None else 0.0)
+        assert bound < EXACT, f"{what}: precondition (a) — the gate / residual stage reaches {bound}"
+        if gate is not None:
+            t = t * gate.repeat_interleave(rows_per, dim=0)[:m]
+        if res is not None:
+            t = t + res
+        if not out_f32:
+            t = _round(t, td)
+    ref = t
+    share = None if out_f32 else _assert_rounding_share(ref, dtype, what)      # an fp32 output is never rounded: (b) and (c) do not apply
+
+    pb = PlanBuilder(lib, dev, dtype)
+    at, wt = pb.const(a.to(td)), pb.const(w.to(td))
+    kw = {}
+    if f8:
+        assert batch == 1 and not w_lo
+        at, asc, lds_a = pb.quantize(at, m, k)
+        wt, wsc, lds_w = pb.quantize(wt, n, k)
+        kw["f8"] = (asc, lds_a, wsc, lds_w, 0, 0)
+    if w_lo:
+        kw["w_lo"] = pb.const(wl.to(td))
+    rt = None
+    if res is not None:
+        rt = pb.const(res.float() if res_f32 else res.to(td))
+    out = pb.gemm(at, wt, m, n, k, bias=pb.const(b.float()) if b is not None else None, act=act, res=rt, res_f32=res_f32,
+                  gate=pb.const(gate.to(td)) if gate is not None else None, gate_rows_per=rows_per,
+                  alpha=alpha, batch=batch, a_bs=m * k, w_bs=n * k, c_bs=m * n, res_bs=m * n, out_f32=out_f32, flags=flags, **kw)
+    getattr(pb.ops[-1].u, abi.UNION_FIELD[abi.OP_GEMM]).act_param = slope
+    plan = _run(pb)
+    if expect_split is not None:
+        got = lib.gemm_last_split()           # None in expect_split = any value; "sliced" = at least two K slices
+        ok = all(e is None or (e == "sliced" and s >= 2) or e == s for e, s in zip(expect_split, got))
+        assert ok, f"launch split {got} != {tuple(expect_split)}"
+    _assert_equal(out.view(batch, m, n), ref, what)
+    first = out.clone()
+    for _ in range(runs - 1):
+        out.fill_(float("nan"))
+        plan.run()
+        _sync(lib)
+        assert torch.equal(out, first), "a second run of the same plan differs (stale scratch read, or an order-dependent sum)"
+    return share
+
+
+def check_gemm_exact_beyond_4gb(lib, dtype, m, n, k, seed=0):
+    """rows generated on the device; the row blocks at the start, around the 4 GB byte offset and at the end must equal the float64 product"""
+    dev, td = _dev(lib), TD[dtype]
+    g = torch.Generator(device=dev).manual_seed(seed)
+    r, alpha = operand_range(dtype, k)
+    pb = PlanBuilder(lib, dev, dtype)
+    at = pb.buf((m, k), td)
+    step = 1 << 16
+    for r0 in range(0, m, step):
+        at[r0:r0 + step] = torch.randint(-r, r + 1, (min(step, m - r0), k), device=dev, generator=g).to(td)
+    w = _ints(torch.Generator().manual_seed(seed + 1), (n, k), r).to(dev)
+    assert k * r * r * alpha < EXACT
+    out = pb.gemm(at, pb.const(w.to(td)), m, n, k, alpha=alpha)
+    _run(pb)
+    edge = (1 << 32) // (k * at.element_size())        # first row whose bytes start beyond 4 GB
+    assert 300 < edge < m - 517
+    for r0 in (0, edge - 300, m - 517):
+        rows = slice(r0, r0 + 517)
+        ref = _round(at[rows].double() @ w.t() * alpha, td)
+        _assert_rounding_share(ref, dtype, f"gemm rows {r0}..")
+        _assert_equal(out[rows], ref, f"gemm beyond 4 GB, rows {r0}..")
+
+
+def check_gemm_f32_exact(lib, seed=0):
+    """the fp32 GEMM of csrc/f32ops.hip on integer operands: no rounding anywhere, every kernel form check_f32_ops names —
+    the vector-ALU form, the matrix-pipe form (from 256 rows up; aligned and unaligned lda), the forced matrix-pipe form, few rows with a long K"""
+    g = torch.Generator().manual_seed(seed)
+    dev = _dev(lib)
+    pb = PlanBuilder(lib, dev, abi.F32)
+    checks = []
+    for name, m, n, k, ld_extra, bt, flags in (("vector ALU", 203, 77, 50, 0, 1, 0), ("vector ALU, batch", 40, 24, 32, 0, 3, 0),
+                                               ("matrix pipe, unaligned lda", 300, 70, 50, 1, 1, 0), ("matrix pipe", 513, 129, 256, 0, 1, 0),
+                                               ("matrix pipe, batch", 260, 33, 18, 0, 2, 0), ("matrix pipe, forced", 40, 9, 24, 0, 1, abi.GEMM_FORCE_TILE256),
+                                               ("few rows, long K", 37, 50, 1024, 0, 1, 0), ("few rows, long K, batch", 72, 19, 2048, 0, 2, 0)):
+        r = 31
+        a, w = _ints(g, (bt, m, k + ld_extra), r), _ints(g, (n, k), r)
+        b, res = _ints(g, (n,), 4096), _ints(g, (bt, m, n), 4096)
+        assert k * r * r * 0.5 + 4096 + 4096 < EXACT
+        ref = F.relu(torch.einsum("bmk,nk->bmn", a[..., :k], w) * 0.5 + b) + res
+        out = pb.gemm(pb.const(a.float()), pb.const(w.float()), m, n, k, lda=k + ld_extra, bias=pb.const(b.float()), act=abi.ACT_RELU,
+                      res=pb.const(res.float()), batch=bt, a_bs=m * (k + ld_extra), c_bs=m * n, res_bs=m * n, alpha=0.5, flags=flags)
+        checks.append((name, out, ref, (bt, m, n)))
+    _run(pb)
+    for name, out, ref, shape in checks:
+        _assert_equal(out.cpu().view(shape), ref, f"fp32 gemm ({name})")
+
+
+# ---- conv ---------------------------------------------------------------------------------------------------------------------------------
+def conv_runs_on_c64_kernel(cin, cout, ksize, stride, with_res, with_sum, act_after_res):
+    """the dispatch rule of csrc/conv_c64.hip (conv_c64_applicable) for tensors below 4 GB: which kernel — hence which rounding contract — a conv gets"""
+    return ksize == 3 and stride == 1 and cin <= 64 and cout <= 64 and not act_after_res and not (with_sum and with_res)
+
+
+def check_conv_exact(lib, dtype, n, h, w, cin, cout, ksize, stride, act=abi.ACT_NONE, with_res=False, pixel_shuffle=0, with_sum=False,
+                     ldx_extra=0, seed=0, with_scale=False, scales=(0.5, 1.0, 2.0), spread=1.0, pad_mode=0, act_after_res=False, res_broadcast=False,
+                     canvas=None, expect_c64=None, slope=0.125):
+    """The contract of the two conv kernels (include/mtx_hip.h, mtx_conv2d_args), v = conv(x) + bias in fp32, res_scale = 0.5:
+         generic kernel:   t = round_T(act(v));  y = t, or with out_scale / a residual y = round_T(out_scale * t + res_scale * res)
+                           (act_after_res: t = round_T(v), y = round_T(act(t + res_scale * res)))
+         64 -> 64 kernel:  y = round_T(out_scale * act(v) + res_scale * res): ONE rounding
+         chan_sum on both: the sums of round_T(act(v)), exact because integer sums below 2^24 are.
+    canvas = (H, W): the image is the top-left h x w of a zero canvas and the size comes from a device-side valid_hw: zeros beyond the image.
+    scales: the per-channel out_scale factors are drawn from these (products with integers must stay exact: powers of two, small integers).
+    spread: widens the operand range (RELU and factors below 1 both take outputs out of the range where T rounds)."""
+    g = torch.Generator().manual_seed(seed)
+    dev, td = _dev(lib), TD[dtype]
+    what = f"conv {n}x{h}x{w} {cin}->{cout} k{ksize} s{stride}"
+    c64 = conv_runs_on_c64_kernel(cin, cout, ksize, stride, with_res, with_sum, act_after_res)
+    if expect_c64 is not None:
+        assert c64 == expect_c64, f"{what}: the case is meant for the {'64 -> 64' if expect_c64 else 'generic'} kernel"
+    kk = cin * ksize * ksize
+    r, _ = operand_range(dtype, kk, with_alpha=False, spread=spread)
+    H, W = canvas if canvas else (h, w)
+    x = torch.zeros(n, H, W, cin, dtype=torch.float64)
+    x[:, :h, :w] = _ints(g, (n, h, w, cin), r)
+    wt = _ints(g, (cout, cin, ksize, ksize), r)
+    b = _ints(g, (cout,), INT_CAP[dtype])
+    assert kk * r * r + INT_CAP[dtype] < EXACT, f"{what}: precondition (a)"
+    xi = x[:, :h, :w].permute(0, 3, 1, 2)                                         # the image alone: its own zero padding
+    if pad_mode == 1:
+        assert stride == 2 and ksize == 3
+        v = F.conv2d(F.pad(xi, (0, 1, 0, 1)), wt, b, stride=2, padding=0)
+    else:
+        v = F.conv2d(xi, wt, b, stride=stride, padding=ksize // 2)
+    v = v.permute(0, 2, 3, 1)                                                     # [n, ho, wo, cout]
+    ho, wo = v.shape[1], v.shape[2]
+    osc = None
+    if with_scale:
+        osc = torch.tensor(scales, dtype=torch.float64)[torch.randint(0, len(scales), (n, cout), generator=g)]
+
+    def shuffled(t_):                                                             # channel (dy * 2 + dx) * cout / 4 + c -> pixel (2 oy + dy, 2 ox + dx), channel c
+        if not pixel_shuffle:
+            return t_
+        cps = cout // 4
+        return t_.reshape(n, ho, wo, 2, 2, cps).permute(0, 1, 3, 2, 4, 5).reshape(n, 2 * ho, 2 * wo, cps)
+
+    res = None
+    if with_res:
+        rs = (1 if res_broadcast else n, (2 if pixel_shuffle else 1) * (ho if not canvas else H), (2 if pixel_shuffle else 1) * (wo if not canvas else W),
+              cout // 4 if pixel_shuffle else cout)
+        res = _ints(g, rs, INT_CAP[dtype])
+    res_img = res[:, :shuffled(v).shape[1], :shuffled(v).shape[2]] if res is not None else None
+    post = with_scale or with_res
+    if c64:
+        pre = _act(v, act, slope)
+        summed = _round(pre, td)
+    else:
+        pre = summed = _round(v if (act_after_res and with_res) else _act(v, act, slope), td)
+    if post:
+        f = pre * osc[:, None, None, :] if with_scale else pre
+        f = shuffled(f)
+        if with_res:
+            f = f + 0.5 * res_img
+            if act_after_res:
+                f = _act(f, act, slope)
+        assert float(f.abs().max()) * 4 < EXACT                                   # (quarter steps from res_scale and the factors included)
+        ref = _round(f, td)
+    else:
+        ref = shuffled(summed)
+    _assert_rounding_share(ref, dtype, what)
+    if with_sum:
+        assert not (act_after_res and with_res)
+        reach = float(summed.abs().sum(dim=(1, 2)).max()) if c64 else float(summed.abs().max()) * 256        # any split of an image / one 16 x 16 tile per row
+        assert reach < EXACT, f"{what}: precondition (a) — a partial channel sum may reach {reach}"
+        want_sum = summed.sum(dim=(1, 2))
+
+    pb = PlanBuilder(lib, dev, dtype)
+    xb = pb.act(n, H, W, cin, ld=cin + ldx_extra)
+    xb.t[..., :cin] = x.to(td)
+    if ldx_extra:
+        xb.t[..., cin:] = 7.0   # garbage in the unused channels must not leak
+    wpk = pb.const(wt.permute(0, 2, 3, 1).reshape(cout, ksize * ksize, cin), td)
+    bias = pb.const(b, torch.float32)
+    rb = None
+    if with_res:
+        rb = pb.act(*res.shape)
+        rb.t.copy_(res.to(td))
+    valid = None
+    if canvas:
+        assert stride == 1 and not pixel_shuffle
+        valid = pb.buf((2,), torch.int32)
+        valid.copy_(torch.tensor([h, w], dtype=torch.int32))
+    cs = None
+    if with_sum:
+        tiles = pb.conv_tiles(xb, ksize, stride, cout=cout, with_res=with_res, with_scale=with_scale, act=act, pixel_shuffle=pixel_shuffle)
+        cs = pb.buf((n, tiles, cout), torch.float32, zero=True)
+        cs.fill_(777.0)          # the conv owns every row: stale values must not survive a launch
+    y = pb.conv2d(xb, wpk, bias, cout, ksize, stride, act=act, act_param=slope, res=rb, res_scale=0.5, pixel_shuffle=pixel_shuffle, chan_sum=cs,
+                  out_scale=pb.const(osc, torch.float32) if with_scale else None, pad_mode=pad_mode, act_after_res=act_after_res,
+                  res_broadcast=res_broadcast, valid_hw=valid)
+    _run(pb)
+    out = y.torch().cpu()
+    oh, ow = ref.shape[1], ref.shape[2]
+    _assert_equal(out[:, :oh, :ow], ref, what)
+    if canvas:
+        assert float(out[:, oh:].abs().max()) == 0.0 and float(out[:, :, ow:].abs().max()) == 0.0, f"{what}: nonzero output beyond the image"
+    if with_sum:
+        _assert_equal(cs.cpu().double().sum(dim=1), want_sum, what + " chan_sum")
+
+
+# ---- attention ----------------------------------------------------------------------------------------------------------------------------
+def _spacing(ref, dtype):
+    """distance between neighbouring values of T at |ref| (float64 tensor)"""
+    e = torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** MIN_EXP[dtype]))).clamp_min(MIN_EXP[dtype])
+    return torch.exp2(e - MANT[dtype])
+
+
+def _assert_one_rounding(got, ref, dtype, what):
+    """|got - ref| <= (0.5 + 2^-10) spacings of T at |ref|: one rounding to T, plus the fp32 reciprocal and exp2 at integer arguments (each a few
+    fp32 ulp, i.e. 2^-15 or less of a bf16 spacing and 2^-12 of an f16 one)"""
+    ratio = (got.double() - ref).abs() / _spacing(ref, dtype)
+    worst = float(ratio.max())
+    assert worst <= 0.5 + 2.0 ** -10, f"{what}: off by {worst:.4f} spacings of the storage type at {int(ratio.argmax())} ({int((ratio > 0.5 + 2.0 ** -10).sum())} elements beyond the bound)"
+    return worst
+
+
+def _launch_attention(lib, dtype, q, k, v, f8_scores, prescaled):
+    """q [b, sq, heads, d], k / v [b, sk, heads, d] (float64 on the device, values exact in T and, with f8_scores, in e4m3) -> the kernel's output"""
+    dev, td = _dev(lib), TD[dtype]
+    batch, sq, heads, d = q.shape
+    sk = k.shape[1]
+    D = heads * d
+    pb = PlanBuilder(lib, dev, dtype)
+    o = pb.buf((batch, sq, heads, d), td, zero=True)
+    if f8_scores:
+        assert batch == 1 and d == 128 and prescaled
+        rows = max(sq, sk)
+        packed = torch.zeros(rows, 2 * D, dtype=torch.uint8)                              # [row][q bytes | k bytes]: the layout the rotary kernel leaves
+        packed[:sq, :D] = q[0].cpu().float().to(torch.float8_e4m3fn).view(torch.uint8).reshape(sq, D)
+        packed[:sk, D:] = k[0].cpu().float().to(torch.float8_e4m3fn).view(torch.uint8).reshape(sk, D)
+        unused = pb.buf((1, rows, heads, d), td, zero=True)                              # q / k are not read in this form
+        pb.attention(unused, unused, pb.const(v.to(td)), o, 1, heads, sq, sk, d, (rows * D, D, d), (rows * D, D, d), (sk * D, D, d), (sq * D, D, d),
+                     1.0, q_prescaled=True, qk_f8=(pb.const(packed), 0, D, 2 * D, 0))
+    else:
+        pb.attention(pb.const(q.to(td)), pb.const(k.to(td)), pb.const(v.to(td)), o, batch, heads, sq, sk, d,
+                     (sq * D, D, d), (sk * D, D, d), (sk * D, D, d), (sq * D, D, d), 1.0 / math.sqrt(d), q_prescaled=prescaled)
+    _run(pb)
+    return o
+
+
+def check_attention_census(lib, dtype, batch, heads, sq, sk, d, prescaled=False, f8_scores=False, seed=0):
+    """Key census: q = 0, so every score is 0 and every probability 1; v[j, :, c] = 64 where c = hash(j) and 0 elsewhere.  Every output row is
+    then 64 * count_c / sk: a key dropped or counted twice moves one channel by 64 / sk — about 128 / sk of its value, far above the rounding.
+    Two hashes, j % d and (j // d) % d, so that every key is told apart from its neighbours and from the keys d away."""
+    g = torch.Generator().manual_seed(seed)
+    dev = _dev(lib)
+    worst = 0.0
+    for hashed in (lambda j: j % d, lambda j: (j // d) % d):
+        q = torch.zeros(batch, sq, heads, d, dtype=torch.float64, device=dev)
+        k = _ints(g, (batch, sk, heads, d), 3).to(dev)
+        j = torch.arange(sk)
+        v = torch.zeros(batch, sk, heads, d, dtype=torch.float64)
+        v[:, j, :, hashed(j)] = 64.0
+        count = torch.bincount(hashed(j), minlength=d).double()
+        ref = (64.0 * count / sk).to(dev).expand(batch, sq, heads, d)
+        o = _launch_attention(lib, dtype, q, k, v.to(dev), f8_scores, prescaled)
+        worst = max(worst, _assert_one_rounding(o, ref, dtype, f"attention census {batch}x{heads}x{sq}x{sk} d{d}"))
+    return worst
+
+
+def check_attention_dyadic(lib, dtype, batch, heads, sq, sk, d, f8_scores=False, late_max=False, seed=0):
+    """Dyadic softmax (MTX_ATTN_Q_PRESCALED; with f8_scores the e4m3 score path at qk_f8_exp = 0): q rows are +-one-hot, k holds integers in
+    [-3, 3], v integers in [-4, 4].  The base-2 logits are then integers, every probability is a power of two whatever maximum the kernel
+    subtracts, and numerator and denominator are exact in fp32 (sk * 4 * 2^6 < 2^24).  late_max: the first three quarters of the keys are clamped
+    to [-1, 1], so the running maximum has to move late."""
+    g = torch.Generator().manual_seed(seed)
+    dev = _dev(lib)
+    assert sk * 4 * 64 < EXACT
+    hot = torch.randint(0, d, (batch, sq, heads), generator=g)
+    sign = torch.randint(0, 2, (batch, sq, heads), generator=g).double() * 2 - 1
+    q = torch.zeros(batch, sq, heads, d, dtype=torch.float64)
+    q.scatter_(3, hot[..., None], sign[..., None])
+    k = _ints(g, (batch, sk, heads, d), 3)
+    if late_max:
+        k[:, :sk * 3 // 4].clamp_(-1, 1)
+    v = _ints(g, (batch, sk, heads, d), 4)
+    q, k, v = q.to(dev), k.to(dev), v.to(dev)
+    o = _launch_attention(lib, dtype, q, k, v, f8_scores, True)
+    worst = 0.0
+    for bi in range(batch):
+        for hd in range(heads):                                                          # head by head: the float64 score matrix of 24 heads would not fit
+            logits = q[bi, :, hd] @ k[bi, :, hd].t()
+            p = torch.exp2(logits - logits.amax(dim=1, keepdim=True))
+            ref = (p @ v[bi, :, hd]) / p.sum(dim=1, keepdim=True)
+            worst = max(worst, _assert_one_rounding(o[bi, :, hd], ref, dtype, f"dyadic attention {sq}x{sk} d{d}, batch {bi} head {hd}"))
+    return worst
+
+
+# ---- the conv cases of both tiers (the GPU tier adds the page-scale shapes) -------------------------------------------------------------
+CONV_CASES = [
+    # the configurations of test_conv (SiLU has no exact form: LEAKY with a power-of-two slope or RELU in its place)
+    dict(n=1, h=20, w=19, cin=64, cout=64, ksize=3, stride=1, act=abi.ACT_RELU),
+    dict(n=2, h=9, w=33, cin=16, cout=24, ksize=3, stride=1, with_res=True),
+    dict(n=1, h=17, w=18, cin=72, cout=136, ksize=3, stride=1, act=abi.ACT_LEAKY, ldx_extra=8),
+    dict(n=1, h=21, w=35, cin=48, cout=96, ksize=3, stride=2, act=abi.ACT_LEAKY),
+    dict(n=1, h=16, w=16, cin=128, cout=64, ksize=1, stride=1, act=abi.ACT_LEAKY),
+    dict(n=1, h=10, w=18, cin=32, cout=128, ksize=3, stride=1, pixel_shuffle=2, with_res=True),
+    dict(n=2, h=18, w=20, cin=64, cout=64, ksize=3, stride=1, with_sum=True, act=abi.ACT_RELU),
+    dict(n=2, h=52, w=50, cin=64, cout=64, ksize=3, stride=1, with_sum=True, act=abi.ACT_RELU),
+    dict(n=1, h=50, w=67, cin=40, cout=64, ksize=3, stride=1, ldx_extra=8),
+    dict(n=1, h=40, w=24, cin=64, cout=64, ksize=3, stride=1, with_res=True, with_sum=True),
+    # the 64 -> 64 persistent kernel (ONE rounding), border tiles only and with interior tiles
+    dict(n=2, h=21, w=19, cin=64, cout=64, ksize=3, stride=1, with_res=True, expect_c64=True),
+    dict(n=1, h=52, w=50, cin=64, cout=64, ksize=3, stride=1, with_res=True, act=abi.ACT_RELU, expect_c64=True),
+    dict(n=2, h=21, w=19, cin=64, cout=64, ksize=3, stride=1, act=abi.ACT_RELU, with_sum=True, with_scale=True, spread=1.5, expect_c64=True),
+    dict(n=2, h=52, w=50, cin=64, cout=64, ksize=3, stride=1, with_res=True, with_scale=True, expect_c64=True),
+    dict(n=2, h=52, w=50, cin=64, cout=64, ksize=3, stride=1, with_sum=True, with_scale=True, scales=(0.5, 1.0, 3.0), expect_c64=True),   # 3 v != 3 round(v): one rounding on interior AND border tiles
+    dict(n=3, h=20, w=36, cin=64, cout=64, ksize=3, stride=1, with_res=True, res_broadcast=True, expect_c64=True),
+    dict(n=1, h=21, w=40, cin=64, cout=64, ksize=3, stride=1, with_res=True, with_scale=True, canvas=(64, 64), expect_c64=True),
+    dict(n=1, h=20, w=34, cin=64, cout=64, ksize=3, stride=1, pixel_shuffle=2, with_res=True, expect_c64=True),
+    dict(n=1, h=20, w=34, cin=32, cout=64, ksize=3, stride=1, ldx_extra=8, act=abi.ACT_LEAKY, expect_c64=True),
+    # the generic kernel (rounds act(..) first)
+    dict(n=2, h=21, w=19, cin=64, cout=64, ksize=3, stride=1, act=abi.ACT_RELU, with_sum=True, with_scale=True, with_res=True, spread=1.5, expect_c64=False),
+    dict(n=1, h=17, w=23, cin=32, cout=72, ksize=3, stride=1, act=abi.ACT_LEAKY, with_sum=True, with_scale=True, scales=(0.5, 1.0, 3.0), expect_c64=False),
+    dict(n=2, h=21, w=35, cin=48, cout=96, ksize=3, stride=2, pad_mode=1, expect_c64=False),
+    dict(n=1, h=20, w=36, cin=32, cout=72, ksize=3, stride=2, pad_mode=1, act=abi.ACT_RELU, with_res=True, expect_c64=False),
+    dict(n=2, h=19, w=22, cin=64, cout=64, ksize=3, stride=1, act=abi.ACT_RELU, with_res=True, act_after_res=True, expect_c64=False),
+    dict(n=1, h=16, w=24, cin=96, cout=32, ksize=1, stride=1, act=abi.ACT_LEAKY, with_res=True, act_after_res=True, expect_c64=False),
+    dict(n=3, h=18, w=20, cin=24, cout=72, ksize=3, stride=1, with_res=True, res_broadcast=True, expect_c64=False),
+    dict(n=2, h=10, w=18, cin=32, cout=128, ksize=3, stride=1, pixel_shuffle=2, with_res=True, res_broadcast=True, expect_c64=False),
+    dict(n=2, h=21, w=40, cin=32, cout=48, ksize=3, stride=1, act=abi.ACT_RELU, with_sum=True, with_res=True, canvas=(48, 64), expect_c64=False),
+    dict(n=1, h=13, w=30, cin=128, cout=64, ksize=1, stride=1, with_sum=True, canvas=(32, 32), expect_c64=False),
+]

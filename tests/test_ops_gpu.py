@@ -1,6 +1,7 @@
 """GPU tier: op-level parity of libmtx_hip.so (through the C ABI) against torch fp32 on MI355X."""
 import pytest
 
+import exact_checks as ec
 import op_checks as oc
 from mangatranslator_amd.hip import abi
 
@@ -254,3 +255,87 @@ def test_attention_mx_fp8_output(hip_lib, cfg):
 
 def test_memset_op(hip_lib):
     oc.check_memset(hip_lib)
+
+
+# ---- exact arithmetic (exact_checks.py): integer operands, float64 references with the rounding contract of include/mtx_hip.h, zero differing elements
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", [
+    dict(m=130, n=136, k=72, act=abi.ACT_RELU),
+    dict(m=64, n=20, k=144, with_res=True, with_gate=True),
+    dict(m=200, n=260, k=200, act=abi.ACT_LEAKY, out_f32=True),
+    dict(m=40, n=48, k=64, batch=3, with_bias=False, with_res=True),
+    dict(m=129, n=7, k=8, with_res=True, with_gate=True),
+    dict(m=300, n=96, k=144, w_lo=True, with_res=True, res_f32=True, out_f32=True),
+    dict(m=4096, n=1728, k=576, act=abi.ACT_RELU, with_res=True),
+    dict(m=8704, n=3072, k=3072, with_gate=True, with_res=True),
+    dict(m=65536, n=432, k=144),
+    dict(m=1000, n=512, k=1024),
+    # the shapes of test_gemm_256_tile_kernel
+    dict(m=8652, n=3072, k=3072, with_res=True, with_gate=True),
+    dict(m=4100, n=9216, k=1024, act=abi.ACT_LEAKY),
+    dict(m=2048, n=5000 // 8 * 8, k=320, act=abi.ACT_RELU, with_bias=False, with_res=True),
+])
+def test_gemm_exact(hip_lib, dtype, cfg):
+    ec.check_gemm_exact(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_gemm_exact_k_slice_tail(hip_lib, dtype):
+    """the K-slice tail's fp32 partials and their last-arriver merge lose no bit at FLUX shapes on 256 CUs"""
+    ec.check_gemm_exact(hip_lib, dtype, m=512, n=3072, k=12288, with_res=True, with_gate=True, runs=3, expect_split=(0, "sliced", None))
+    ec.check_gemm_exact(hip_lib, dtype, m=8624, n=3072, k=15360, with_res=True, with_gate=True, runs=2, expect_split=(256, "sliced", None))
+    ec.check_gemm_exact(hip_lib, dtype, m=8812, n=3072, k=15360, with_res=True, with_gate=True, expect_split=(256, "sliced", None))
+    ec.check_gemm_exact(hip_lib, dtype, m=8112, n=3072, k=12288, expect_split=(256, "sliced", None))
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", [dict(m=8652, n=3072, k=3072, with_res=True, with_gate=True), dict(m=4100, n=9216, k=1024, act=abi.ACT_LEAKY),
+                                 dict(m=2048, n=5000 // 8 * 8, k=384, act=abi.ACT_RELU, with_bias=False, with_res=True),
+                                 dict(m=8704, n=3072, k=12288, with_gate=True, with_res=True), dict(m=300, n=264, k=128, flags=abi.GEMM_FORCE_TILE256)])
+def test_gemm_exact_fp8(hip_lib, dtype, cfg):
+    ec.check_gemm_exact(hip_lib, dtype, f8=True, **cfg)
+
+
+def test_gemm_exact_f32(hip_lib):
+    ec.check_gemm_f32_exact(hip_lib)
+
+
+def test_gemm_exact_beyond_4gb(hip_lib):
+    ec.check_gemm_exact_beyond_4gb(hip_lib, abi.BF16, m=1050000, n=256, k=2304)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", ec.CONV_CASES + [
+    # page-scale shapes
+    dict(n=1, h=384, w=256, cin=64, cout=64, ksize=3, stride=1, with_res=True, with_sum=True),
+    dict(n=1, h=200, w=136, cin=192, cout=384, ksize=3, stride=2, act=abi.ACT_LEAKY),
+    dict(n=1, h=100, w=68, cin=576, cout=192, ksize=1, stride=1, act=abi.ACT_LEAKY),
+])
+def test_conv_exact(hip_lib, dtype, cfg):
+    ec.check_conv_exact(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_attention_census(hip_lib, dtype):
+    """every key counted exactly once, up to the FLUX shape (24 heads, key-split tail) and Klein's with fp8 scores"""
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=2, sq=70, sk=150, d=72)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=3, sq=9, sk=100, d=16)
+    ec.check_attention_census(hip_lib, dtype, batch=2, heads=2, sq=300, sk=200, d=64, prescaled=True)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=2, sq=1030, sk=330, d=128)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=2, sq=1100, sk=449, d=128, prescaled=True)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, prescaled=True)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, prescaled=True)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_attention_dyadic_softmax(hip_lib, dtype):
+    """integer base-2 logits: exact numerator and denominator, one rounding left (pre-scaled q; fp8 scores with exponent 0)"""
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=70, sk=150, d=72)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=3, sq=9, sk=100, d=16)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=2, heads=2, sq=300, sk=200, d=64)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1030, sk=330, d=128)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1100, sk=449, d=128, seed=1)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1024, sk=2100, d=128, late_max=True)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1024, sk=2100, d=128, late_max=True, f8_scores=True, seed=1)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, seed=2)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, seed=3)

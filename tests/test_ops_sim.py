@@ -4,6 +4,7 @@ maps, epilogues) where no GPU exists; the same checks run on hardware in test_op
 import pytest
 import torch
 
+import exact_checks as ec
 import op_checks as oc
 from mangatranslator_amd.hip import abi
 
@@ -256,3 +257,90 @@ def test_norm_f32_row_to_16_bit_operand(emu_lib):
 def test_hi_lo_weight_pairs(emu_lib):
     e_fast, e_high = oc.check_hi_lo_weights(emu_lib)
     assert e_fast > 1e-5            # the weights' rounding is what the fast form is left with
+
+
+# ---- exact arithmetic (exact_checks.py): integer operands, float64 references with the rounding contract of include/mtx_hip.h, zero differing elements
+F256 = abi.GEMM_FORCE_TILE256
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", [
+    dict(m=130, n=136, k=72, act=abi.ACT_RELU),
+    dict(m=64, n=20, k=144, with_res=True, with_gate=True),
+    dict(m=200, n=260, k=200, act=abi.ACT_LEAKY, out_f32=True),
+    dict(m=40, n=48, k=64, batch=3, with_bias=False, with_res=True),
+    dict(m=129, n=7, k=8, with_res=True, with_gate=True),                    # n % 8 != 0: the scalar-store tail
+    dict(m=1, n=1, k=8),
+    dict(m=300, n=96, k=144, w_lo=True, act=abi.ACT_RELU),                   # W = w + w_lo, both halves integer
+    dict(m=300, n=96, k=144, w_lo=True, with_res=True, res_f32=True, out_f32=True),
+    dict(m=96, n=72, k=96, with_res=True, res_f32=True, out_f32=True),
+])
+def test_gemm_exact(emu_lib, dtype, cfg):
+    ec.check_gemm_exact(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_gemm_exact_256_tile_kernel(emu_lib, dtype):
+    ec.check_gemm_exact(emu_lib, dtype, m=300, n=264, k=128, act=abi.ACT_LEAKY, with_res=True, with_gate=True, flags=F256)
+    ec.check_gemm_exact(emu_lib, dtype, m=260, n=248, k=448, with_res=True, flags=F256)
+    ec.check_gemm_exact(emu_lib, dtype, m=256, n=512, k=64, batch=2, with_bias=False, flags=F256)
+
+
+def test_gemm_exact_256_tile_map_strips(emu_lib, monkeypatch):
+    for st in (0, 1, 2, 4, 8):
+        monkeypatch.setenv("MTX_GEMM_STRIPS", str(st))
+        ec.check_gemm_exact(emu_lib, abi.BF16, m=700, n=1200, k=128, with_res=True, flags=F256)
+        ec.check_gemm_exact(emu_lib, abi.F16, m=1100, n=600, k=64, act=abi.ACT_RELU, flags=F256, seed=st)
+
+
+def test_gemm_exact_k_slice_tail(emu_lib):
+    """the K-slice tail's fp32 partials and their merge lose no bit; the whole problem as K slices"""
+    ec.check_gemm_exact(emu_lib, abi.BF16, m=1024, n=256, k=4096, act=abi.ACT_RELU, with_res=True, with_gate=True, flags=F256, runs=3, expect_split=(3, 3, 3))
+    ec.check_gemm_exact(emu_lib, abi.F16, m=1700, n=200, k=3072, with_bias=False, flags=F256, runs=2, expect_split=(6, "sliced", None))
+    ec.check_gemm_exact(emu_lib, abi.BF16, m=256, n=200, k=8192, with_res=True, with_gate=True, runs=2, expect_split=(0, "sliced", None))
+    ec.check_gemm_exact(emu_lib, abi.F16, m=256, n=200, k=8192, with_res=True, with_gate=True, expect_split=(0, "sliced", None))
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_gemm_exact_fp8(emu_lib, dtype):
+    """the MX e4m3 kernel shares the 256-tile epilogue, hence its rounding contract; 16 tiles on 3 CUs: one left over -> tail + merge"""
+    ec.check_gemm_exact(emu_lib, dtype, m=300, n=264, k=128, f8=True, act=abi.ACT_RELU, with_res=True, with_gate=True, flags=F256)
+    ec.check_gemm_exact(emu_lib, dtype, m=260, n=248, k=640, f8=True, with_res=True, flags=F256)
+    ec.check_gemm_exact(emu_lib, dtype, m=1024, n=1024, k=512, f8=True, with_gate=True, flags=F256)
+
+
+def test_gemm_exact_f32(emu_lib):
+    ec.check_gemm_f32_exact(emu_lib)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", ec.CONV_CASES)
+def test_conv_exact(emu_lib, dtype, cfg):
+    ec.check_conv_exact(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_attention_census(emu_lib, dtype):
+    """every key counted exactly once: the short kernel, the long kernel with its ragged last tile and its key-split tail"""
+    ec.check_attention_census(emu_lib, dtype, batch=1, heads=2, sq=70, sk=150, d=72)
+    ec.check_attention_census(emu_lib, dtype, batch=1, heads=3, sq=9, sk=100, d=16)
+    ec.check_attention_census(emu_lib, dtype, batch=2, heads=2, sq=300, sk=200, d=64, prescaled=True)
+    ec.check_attention_census(emu_lib, dtype, batch=1, heads=2, sq=1030, sk=330, d=128)
+    ec.check_attention_census(emu_lib, dtype, batch=1, heads=1, sq=1100, sk=449, d=128, prescaled=True)
+    ec.check_attention_census(emu_lib, dtype, batch=1, heads=1, sq=1030, sk=330, d=128, f8_scores=True, prescaled=True)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_attention_dyadic_softmax(emu_lib, dtype):
+    """integer base-2 logits: exact numerator and denominator, one rounding left (pre-scaled q; fp8 scores with exponent 0)"""
+    ec.check_attention_dyadic(emu_lib, dtype, batch=1, heads=2, sq=70, sk=150, d=72)
+    ec.check_attention_dyadic(emu_lib, dtype, batch=1, heads=3, sq=9, sk=100, d=16)
+    ec.check_attention_dyadic(emu_lib, dtype, batch=2, heads=2, sq=300, sk=200, d=64)
+    ec.check_attention_dyadic(emu_lib, dtype, batch=1, heads=2, sq=1030, sk=330, d=128)
+    ec.check_attention_dyadic(emu_lib, dtype, batch=1, heads=1, sq=1100, sk=449, d=128, seed=1)
+    ec.check_attention_dyadic(emu_lib, dtype, batch=1, heads=1, sq=1030, sk=330, d=128, f8_scores=True, seed=2)
+
+
+def test_attention_dyadic_softmax_late_maximum(emu_lib):
+    ec.check_attention_dyadic(emu_lib, abi.BF16, batch=1, heads=1, sq=1024, sk=2100, d=128, late_max=True)
+    ec.check_attention_dyadic(emu_lib, abi.F16, batch=1, heads=1, sq=1024, sk=2100, d=128, late_max=True, f8_scores=True, seed=1)

@@ -797,19 +797,6 @@ __global__ __launch_bounds__(256) void attn_merge_q8_kernel(AttnParams p) {
   }
 }
 
-static int attn_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-#ifdef MTX_EMU
-    cus = 3;
-#else
-    int dev = 0; hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-#endif
-  }
-  return cus;
-}
-
 template <typename T>
 static int launch_attn_t(const AttnParams& p0, void* stream) {
   AttnParams p = p0;
@@ -818,7 +805,7 @@ static int launch_attn_t(const AttnParams& p0, void* stream) {
     const unsigned total = (unsigned)(p.batch * p.heads) * p.qblocks;
     // one workgroup per CU at a time: a partial last wave of `rem` query blocks leaves most of the chip idle for a
     // whole block time, so cut those blocks into `split` key ranges (fp32 partials in the caller's scratch) + merge
-    const unsigned cus = (unsigned)attn_num_cus(), rem = total % cus;
+    const unsigned cus = (unsigned)num_cus_or(256), rem = total % cus;
     const unsigned ntiles = (unsigned)((p.sk + AB_KV - 1) / AB_KV);
     unsigned split = (rem > 0 && total > cus) ? cus / rem : 1;
     if (split > 8) split = 8;
@@ -830,27 +817,15 @@ static int launch_attn_t(const AttnParams& p0, void* stream) {
     // round 5): half-tile staggered wave groups, an S^T-pipelined LDS-DMA ring, 4 waves x 64 rows, two 128-query workgroups per CU, K / V by
     // LDS-DMA (-17 %), row sums on the matrix pipe (-6.7 %), a half-tile pipelined softmax (does not fit 256 registers).  What stayed: fragment
     // reads four steps ahead of the MFMAs (order pinned with sched_group_barrier; +1.5 ... 2.5 %) and 16-byte row stores (+0.3 %), identical bytes.
-    if (p.kf8 != nullptr) {                      // fp8 scores (validated in attn_launch: pre-scaled q; a 16-bit output needs 16-byte rows)
-      if (p.vf8 != nullptr) MTX_LAUNCH((attn_mma32_k8v8q_kernel<T, 128, true>), dim3(g), dim3(512), 0, stream, p);      // (validated: comes with q8)
-      else if (p.q8 != nullptr) MTX_LAUNCH((attn_mma32_k8q_kernel<T, 128, true>), dim3(g), dim3(512), 0, stream, p);
-      else MTX_LAUNCH((attn_mma32_k8_kernel<T, 128, true>), dim3(g), dim3(512), 0, stream, p);
-      if (p.split > 1) {
-        if (p.q8 != nullptr) MTX_LAUNCH((attn_merge_q8_kernel<T, 128>), dim3((total - p.n_full) * 8), dim3(256), 0, stream, p);
-        else MTX_LAUNCH((attn_merge_kernel<T, 128>), dim3((total - p.n_full) * 8), dim3(256), 0, stream, p);
-      }
-      return MTX_OK;
-    }
-    if (p.q8 != nullptr) {
-      if (p.prescaled) MTX_LAUNCH((attn_mma32_q8d_kernel<T, 128, true>), dim3(g), dim3(512), 0, stream, p);
-      else MTX_LAUNCH((attn_mma32_q8_kernel<T, 128, false>), dim3(g), dim3(512), 0, stream, p);
-      if (p.split > 1) MTX_LAUNCH((attn_merge_q8_kernel<T, 128>), dim3((total - p.n_full) * 8), dim3(256), 0, stream, p);
-      return MTX_OK;
-    }
     const bool wide_ok = p.o_ss % 8 == 0 && p.o_hs % 8 == 0 && p.o_bs % 8 == 0 && ((size_t)p.o & 15) == 0;
-    if (p.prescaled && wide_ok) MTX_LAUNCH((attn_mma32_d_kernel<T, 128, true>), dim3(g), dim3(512), 0, stream, p);      // the FLUX graphs' form
-    else if (p.prescaled) MTX_LAUNCH((attn_mma32_kernel<T, 128, true>), dim3(g), dim3(512), 0, stream, p);
-    else MTX_LAUNCH((attn_mma32_kernel<T, 128, false>), dim3(g), dim3(512), 0, stream, p);
-    if (p.split > 1) MTX_LAUNCH((attn_merge_kernel<T, 128>), dim3((total - p.n_full) * 8), dim3(256), 0, stream, p);
+    void (*kernel)(AttnParams);
+    if (p.kf8 != nullptr)                        // fp8 scores (validated in attn_launch: pre-scaled q; a 16-bit output needs 16-byte rows; v_f8t comes with q8)
+      kernel = p.vf8 != nullptr ? attn_mma32_k8v8q_kernel<T, 128, true> : p.q8 != nullptr ? attn_mma32_k8q_kernel<T, 128, true> : attn_mma32_k8_kernel<T, 128, true>;
+    else if (p.q8 != nullptr) kernel = p.prescaled ? attn_mma32_q8d_kernel<T, 128, true> : attn_mma32_q8_kernel<T, 128, false>;
+    else if (p.prescaled) kernel = wide_ok ? attn_mma32_d_kernel<T, 128, true> : attn_mma32_kernel<T, 128, true>;      // wide_ok: the FLUX graphs' form
+    else kernel = attn_mma32_kernel<T, 128, false>;
+    MTX_LAUNCH(kernel, dim3(g), dim3(512), 0, stream, p);
+    if (p.split > 1) MTX_LAUNCH((p.q8 != nullptr ? attn_merge_q8_kernel<T, 128> : attn_merge_kernel<T, 128>), dim3((total - p.n_full) * 8), dim3(256), 0, stream, p);
     return MTX_OK;
   }
   if (p.q8 != nullptr || p.kf8 != nullptr) return MTX_ERR_UNSUPPORTED;
@@ -897,10 +872,9 @@ int attn_launch(const mtx_attn_args* a, void* stream, const char** err) {
     p.part_o = reinterpret_cast<float*>(a->workspace);
     p.part_ml = p.part_o + (size_t)256 * AB_QB * 128;
   }
-  if (a->dtype == MTX_BF16) return launch_attn_t<__bf16>(p, stream);
-  if (a->dtype == MTX_F16) return launch_attn_t<_Float16>(p, stream);
-  *err = "attention: dtype must be bf16 or f16";
-  return MTX_ERR_INVALID;
+  int rc = MTX_OK;
+  if (!with_storage_type(a->dtype, [&](auto t) { rc = launch_attn_t<typename decltype(t)::type>(p, stream); })) { *err = "attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  return rc;
 }
 
 }  // namespace mtx

@@ -349,10 +349,8 @@ int conv2d_launch(const mtx_conv2d_args* a, void* stream, const char** err) {
   p.act = a->act; p.act_param = a->act_param; p.res_scale = a->res_scale; p.act_after = (a->act_after_res && a->res != nullptr) ? 1 : 0; p.ps = a->pixel_shuffle; p.res_bcast = a->res_broadcast_n;
   p.valid_hw = a->stride == 1 ? a->valid_hw : nullptr;
   p.out_scale = a->out_scale;
-  int rc;
-  if (a->dtype == MTX_BF16) rc = launch_conv_t<__bf16>(a, p, stream, tiles);
-  else if (a->dtype == MTX_F16) rc = launch_conv_t<_Float16>(a, p, stream, tiles);
-  else { *err = "conv2d: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  int rc = MTX_OK;
+  if (!with_storage_type(a->dtype, [&](auto t) { rc = launch_conv_t<typename decltype(t)::type>(a, p, stream, tiles); })) { *err = "conv2d: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   if (rc != MTX_OK) *err = "conv2d: unsupported kernel/stride";
   return rc;
 }

@@ -555,32 +555,16 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(ConvC64Params p) {
   }
 }
 
-static int g_num_cus = 0;
-
-static int c64_num_cus(const char** err) {
-  if (g_num_cus == 0) {
-#ifdef MTX_EMU
-    g_num_cus = 3;
-#else
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { if (err) *err = "conv2d: device query failed"; return -1; }
-    g_num_cus = prop.multiProcessorCount;
-#endif
-  }
-  return g_num_cus;
-}
-
 static unsigned c64_grid(int n, int h, int w) {
   const long total = (long)((w + C64_T - 1) / C64_T) * ((h + C64_T - 1) / C64_T) * n;
   const long npairs = (total + 1) / 2;
-  const int cus = c64_num_cus(nullptr);
+  const int cus = num_cus();
   return (unsigned)(npairs < cus ? npairs : cus);
 }
 
 // rows of the chan_sum buffer per image = one partial per wave of the persistent launch
 int conv_c64_tiles(int n, int h, int w) {
-  if (c64_num_cus(nullptr) < 0) return -1;
+  if (num_cus() < 0) return -1;
   return (int)c64_grid(n, h, w) * 8;
 }
 
@@ -614,16 +598,16 @@ int conv_c64_launch(const mtx_conv2d_args* a, void* stream, const char** err) {
   }
   p.tiles_x = (a->w_in + C64_T - 1) / C64_T;
   p.tiles_y = (a->h + C64_T - 1) / C64_T;
-  if (c64_num_cus(err) < 0) return MTX_ERR_HIP;
+  if (num_cus() < 0) { *err = "conv2d: device query failed"; return MTX_ERR_HIP; }
   const unsigned grid = c64_grid(a->n, a->h, a->w_in);
 #define C64_GO(TT, AB, AC, SM, RS) MTX_LAUNCH((conv3x3_c64_kernel<TT, AB, AC, SM, RS>), dim3(grid), dim3(512), 0, stream, p)
 #define C64_ACT(TT, SM, RS) do { if (a->act == MTX_ACT_NONE) C64_GO(TT, 0, MTX_ACT_NONE, SM, RS); else if (a->act == MTX_ACT_RELU) C64_GO(TT, 0, MTX_ACT_RELU, SM, RS); \
                                  else C64_GO(TT, 0, -1, SM, RS); } while (0)
-#define C64_VAR(TT) do { if (sum) C64_ACT(TT, true, false); else if (a->res != nullptr) C64_ACT(TT, false, true); else C64_ACT(TT, false, false); } while (0)
   const bool sum = a->chan_sum != nullptr;
-  if (a->dtype == MTX_BF16) C64_VAR(__bf16);
-  else if (a->dtype == MTX_F16) C64_VAR(_Float16);
-  else { *err = "conv2d: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!with_storage_type(a->dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        if (sum) C64_ACT(T, true, false); else if (a->res != nullptr) C64_ACT(T, false, true); else C64_ACT(T, false, false);
+      })) { *err = "conv2d: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 

@@ -93,15 +93,13 @@ int detr_launch(const mtx_detr_args* a, void* stream, const char** err) {
     if (a->d % 8 || a->levels < 1 || a->levels > 4 || a->points < 1 || a->ld_value % 8 || a->ld_out % 8) { *err = "detr: bad deformable-attention layout"; return MTX_ERR_INVALID; }
     const long total = (long)a->rows * a->heads * (a->d / 8);
     long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((deform_attn_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-    else MTX_LAUNCH((deform_attn_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
+    MTX_LAUNCH_T(a->dtype, deform_attn_kernel, dim3((unsigned)blocks), dim3(256), stream, *a);      // dtype checked above
     return MTX_OK;
   }
   if (a->kind == 1 || a->kind == 2) {
     if (!a->ref || !a->ref_out || (a->kind == 1 && !a->delta)) { *err = "detr: null operand"; return MTX_ERR_INVALID; }
     const dim3 grid((unsigned)((a->rows + 255) / 256));
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((box_refine_kernel<__bf16>), grid, dim3(256), 0, stream, *a);
-    else MTX_LAUNCH((box_refine_kernel<_Float16>), grid, dim3(256), 0, stream, *a);
+    MTX_LAUNCH_T(a->dtype, box_refine_kernel, grid, dim3(256), stream, *a);      // dtype checked above
     return MTX_OK;
   }
   *err = "detr: unknown kind";

@@ -365,25 +365,19 @@ int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
     if (!a->a || !a->y || a->c % 8 || a->lda % 8 || a->ldy % 8) { *err = "softmax_rows: bad layout"; return MTX_ERR_INVALID; }
     const long rows = a->n * a->h * a->w;
     if (rows < 1) return MTX_OK;
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((softmax_rows_kernel<__bf16>), dim3((unsigned)rows), dim3(256), 0, stream, *a);
-    else if (a->dtype == MTX_F16) MTX_LAUNCH((softmax_rows_kernel<_Float16>), dim3((unsigned)rows), dim3(256), 0, stream, *a);
-    else { *err = "softmax_rows: dtype"; return MTX_ERR_INVALID; }
+    if (!MTX_LAUNCH_T(a->dtype, softmax_rows_kernel, dim3((unsigned)rows), dim3(256), stream, *a)) { *err = "softmax_rows: dtype"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
   if (a->kind == MTX_EW_RESIDUAL_DIST) {
     if (!a->a || !a->b || !a->s || !a->y || a->c % 8 || a->lda % 8 || a->ldb % 8 || a->lds % 8) { *err = "residual_dist: needs a, b, s (16-bit, strides % 8 == 0) and y (fp32 [2 * MTX_RESDIST_PARTS])"; return MTX_ERR_INVALID; }
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((residual_dist_kernel<__bf16>), dim3(MTX_RESDIST_PARTS), dim3(256), 0, stream, *a);
-    else if (a->dtype == MTX_F16) MTX_LAUNCH((residual_dist_kernel<_Float16>), dim3(MTX_RESDIST_PARTS), dim3(256), 0, stream, *a);
-    else { *err = "residual_dist: dtype"; return MTX_ERR_INVALID; }
+    if (!MTX_LAUNCH_T(a->dtype, residual_dist_kernel, dim3(MTX_RESDIST_PARTS), dim3(256), stream, *a)) { *err = "residual_dist: dtype"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
   if (a->kind == MTX_EW_TRANSPOSE) {
     if (!a->a || !a->y) { *err = "transpose: null operand"; return MTX_ERR_INVALID; }
     const long rows = a->h * a->w;
     dim3 grid((unsigned)((a->c + 63) / 64), (unsigned)((rows + 63) / 64), (unsigned)a->n);
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((transpose_kernel<__bf16>), grid, dim3(256), 0, stream, *a);
-    else if (a->dtype == MTX_F16) MTX_LAUNCH((transpose_kernel<_Float16>), grid, dim3(256), 0, stream, *a);
-    else { *err = "transpose: dtype"; return MTX_ERR_INVALID; }
+    if (!MTX_LAUNCH_T(a->dtype, transpose_kernel, grid, dim3(256), stream, *a)) { *err = "transpose: dtype"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
   if (a->kind == MTX_EW_V_F8T) {
@@ -392,9 +386,7 @@ int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
       *err = "v_f8t: c must be heads * 128, lda % 8 == 0, ldy8 a multiple of 64 that covers the rows, y8 16-byte aligned"; return MTX_ERR_INVALID; }
     if (rows < 1) return MTX_OK;
     const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)(a->c / 128));
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((v_f8t_kernel<__bf16>), grid, dim3(256), 0, stream, *a);
-    else if (a->dtype == MTX_F16) MTX_LAUNCH((v_f8t_kernel<_Float16>), grid, dim3(256), 0, stream, *a);
-    else { *err = "v_f8t: dtype"; return MTX_ERR_INVALID; }
+    if (!MTX_LAUNCH_T(a->dtype, v_f8t_kernel, grid, dim3(256), stream, *a)) { *err = "v_f8t: dtype"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
   if (a->kind == MTX_EW_QK_NORM_ROPE) {
@@ -407,9 +399,7 @@ int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
     const unsigned gx = (unsigned)((a->c / 8 + 255) / 256);
     long gy = (rows + QR_U - 1) / QR_U; if (gy > 4096) gy = 4096;
     const dim3 grid(gx, (unsigned)gy);
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((qk_norm_rope_kernel<__bf16>), grid, dim3(256), 0, stream, *a);
-    else if (a->dtype == MTX_F16) MTX_LAUNCH((qk_norm_rope_kernel<_Float16>), grid, dim3(256), 0, stream, *a);
-    else { *err = "qk_norm_rope: dtype"; return MTX_ERR_INVALID; }
+    if (!MTX_LAUNCH_T(a->dtype, qk_norm_rope_kernel, grid, dim3(256), stream, *a)) { *err = "qk_norm_rope: dtype"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
   if (!a->a || !a->y) { *err = "elementwise: null operand"; return MTX_ERR_INVALID; }
@@ -432,9 +422,7 @@ int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
   if (total <= 0) return MTX_OK;
   long blocks = (total + 255) / 256;
   if (blocks > 2048 * 4) blocks = 2048 * 4;
-  if (a->dtype == MTX_BF16) MTX_LAUNCH((ew_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else if (a->dtype == MTX_F16) MTX_LAUNCH((ew_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else { *err = "elementwise: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!MTX_LAUNCH_T(a->dtype, ew_kernel, dim3((unsigned)blocks), dim3(256), stream, *a)) { *err = "elementwise: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 
@@ -788,14 +776,10 @@ int ca_launch(const mtx_ca_args* a, void* stream, const char** err) {
     if (!a->conv_w || a->c > 64 || a->c % 8 || a->ldt % 8 || a->h < 1 || a->w < 1) { *err = "channel_attention (pool before the conv): needs conv_w, C <= 64 in multiples of 8, ldt % 8 == 0"; return MTX_ERR_INVALID; }
     if (a->scratch != nullptr && a->c * a->cr <= 1024) {
       const dim3 grid((unsigned)a->n, MTX_CA_SPLIT);
-      if (a->dtype == MTX_BF16) MTX_LAUNCH(ca_split_kernel<__bf16>, grid, dim3(1024), 0, stream, *a);
-      else if (a->dtype == MTX_F16) MTX_LAUNCH(ca_split_kernel<_Float16>, grid, dim3(1024), 0, stream, *a);
-      else { *err = "channel_attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+      if (!MTX_LAUNCH_T(a->dtype, ca_split_kernel, grid, dim3(1024), stream, *a)) { *err = "channel_attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
       return MTX_OK;
     }
-    if (a->dtype == MTX_BF16) MTX_LAUNCH(ca_kernel<__bf16>, dim3((unsigned)a->n), dim3(1024), 0, stream, *a);
-    else if (a->dtype == MTX_F16) MTX_LAUNCH(ca_kernel<_Float16>, dim3((unsigned)a->n), dim3(1024), 0, stream, *a);
-    else { *err = "channel_attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+    if (!MTX_LAUNCH_T(a->dtype, ca_kernel, dim3((unsigned)a->n), dim3(1024), stream, *a)) { *err = "channel_attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
   MTX_LAUNCH(ca_kernel<_Float16>, dim3((unsigned)a->n), dim3(1024), 0, stream, *a);
@@ -860,9 +844,7 @@ int img_launch(const mtx_img_args* a, void* stream, const char** err) {
   long blocks = (total + 255) / 256;
   if (blocks < 1) return MTX_OK;
   if (blocks > 8192) blocks = 8192;
-  if (a->dtype == MTX_BF16) MTX_LAUNCH((img_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else if (a->dtype == MTX_F16) MTX_LAUNCH((img_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else { *err = "image_convert: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!MTX_LAUNCH_T(a->dtype, img_kernel, dim3((unsigned)blocks), dim3(256), stream, *a)) { *err = "image_convert: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 
@@ -905,9 +887,7 @@ int resize_thresh_launch(const mtx_resize_thresh_args* a, void* stream, const ch
   if (blocks < 1) return MTX_OK;
   if (blocks > 8192) blocks = 8192;
   if (a->dtype == MTX_F32) MTX_LAUNCH((resize_thresh_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else if (a->dtype == MTX_BF16) MTX_LAUNCH((resize_thresh_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else if (a->dtype == MTX_F16) MTX_LAUNCH((resize_thresh_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else { *err = "resize_threshold: bad dtype"; return MTX_ERR_INVALID; }
+  else if (!MTX_LAUNCH_T(a->dtype, resize_thresh_kernel, dim3((unsigned)blocks), dim3(256), stream, *a)) { *err = "resize_threshold: bad dtype"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 
@@ -1026,9 +1006,7 @@ int preproc_launch(const mtx_preproc_args* a, void* stream, const char** err) {
   if (!a->src || !a->dst) { *err = "preprocess: null operand"; return MTX_ERR_INVALID; }
   if (a->h < 1 || a->w < 1 || a->oh < 1 || a->ow < 1 || a->c_pad < 3) { *err = "preprocess: bad geometry"; return MTX_ERR_INVALID; }
   long blocks = (a->oh * a->ow + 255) / 256; if (blocks > 8192) blocks = 8192;
-  if (a->dtype == MTX_BF16) MTX_LAUNCH((preproc_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else if (a->dtype == MTX_F16) MTX_LAUNCH((preproc_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else { *err = "preprocess: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!MTX_LAUNCH_T(a->dtype, preproc_kernel, dim3((unsigned)blocks), dim3(256), stream, *a)) { *err = "preprocess: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 
@@ -1065,9 +1043,7 @@ int yolo_decode_launch(const mtx_yolo_decode_args* a, void* stream, const char**
   for (int l = 0; l < a->n_levels; ++l) { if (!a->level[l]) { *err = "yolo_decode: null level"; return MTX_ERR_INVALID; } total += a->lh[l] * a->lw[l]; }
   if (total == 0) return MTX_OK;
   const unsigned blocks = (unsigned)((total + 255) / 256);
-  if (a->dtype == MTX_BF16) MTX_LAUNCH((yolo_decode_kernel<__bf16>), dim3(blocks), dim3(256), 0, stream, *a, total);
-  else if (a->dtype == MTX_F16) MTX_LAUNCH((yolo_decode_kernel<_Float16>), dim3(blocks), dim3(256), 0, stream, *a, total);
-  else { *err = "yolo_decode: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!MTX_LAUNCH_T(a->dtype, yolo_decode_kernel, dim3(blocks), dim3(256), stream, *a, total)) { *err = "yolo_decode: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 

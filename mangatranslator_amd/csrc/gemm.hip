@@ -890,35 +890,8 @@ __global__ __launch_bounds__(512) void gemm256_slice_kernel(GemmParams p) {
   gemm256_epilogue<T, ACT>(p, acc, smem, reinterpret_cast<T*>(p.c), m0, n0, 0, wv, lane);
 }
 
-static int gemm_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-#ifdef MTX_EMU
-    cus = 3;
-#else
-    int dev = 0; hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-#endif
-  }
-  return cus;
-}
+// ---- host side: validate, fill GemmParams, choose the kernel family (gemm_route), launch ------------------------------------------------
 
-template <typename T, bool F8>
-static void launch_gemm256_tiles(const GemmParams& p, dim3 grid, void* stream) {
-#define MTX_G256(ACTV) do { if (F8) MTX_LAUNCH((gemm256_f8_kernel<T, ACTV>), grid, dim3(512), 0, stream, p); \
-                            else MTX_LAUNCH((gemm256_kernel<T, ACTV>), grid, dim3(512), 0, stream, p); } while (0)
-  switch (p.act) {
-    case MTX_ACT_NONE: MTX_G256(MTX_ACT_NONE); break;
-    case MTX_ACT_SILU: MTX_G256(MTX_ACT_SILU); break;
-    case MTX_ACT_GELU_TANH: MTX_G256(MTX_ACT_GELU_TANH); break;
-    default: MTX_G256(-1); break;
-  }
-#undef MTX_G256
-}
-
-// measured on MI355X (tools/bench_kernels.py, FLUX shapes, random data): the ping-pong loop with descriptor DMA and the 3/3/2/0
-// piece spread runs 1119-1341 TFLOP/s in bf16; the schedules it replaced (flat-address ping-pong, one-barrier, K = 32 ring, wave
-// specialised DMA) were 2-15 % behind on every shape and are gone (docs/experiments.md keeps the numbers).
 static thread_local int g_last_split[3] = {0, 0, 0};           // whole tiles, K slices, tail pieces of this thread's last 256-tile launch
 void gemm_last_split(int* out) { out[0] = g_last_split[0]; out[1] = g_last_split[1]; out[2] = g_last_split[2]; }
 
@@ -958,22 +931,34 @@ static void gemm256_tickets_ready(unsigned* tickets, void* stream) {
   if (fresh) zero_words_async(tickets, (size_t)G2_TICKET_BYTES, stream);
 }
 
-template <typename T, bool F8>
-static void launch_gemm256_slices(const GemmParams& p, unsigned pieces, void* stream) {
-  gemm256_tickets_ready(p.tickets, stream);
-#define MTX_G256S(ACTV) MTX_LAUNCH((gemm256_slice_kernel<T, F8, ACTV>), dim3(pieces), dim3(512), 0, stream, p)
-  switch (p.act) {
-    case MTX_ACT_NONE: MTX_G256S(MTX_ACT_NONE); break;
-    case MTX_ACT_SILU: MTX_G256S(MTX_ACT_SILU); break;
-    case MTX_ACT_GELU_TANH: MTX_G256S(MTX_ACT_GELU_TANH); break;
-    default: MTX_G256S(-1); break;
+// the 256-tile kernels are compiled for the epilogue activations the hot graphs use; ACT = -1 is the runtime switch for the rest
+template <typename F>
+static void with_gemm256_act(int act, F&& f) {
+  switch (act) {
+    case MTX_ACT_NONE: f(std::integral_constant<int, MTX_ACT_NONE>{}); break;
+    case MTX_ACT_SILU: f(std::integral_constant<int, MTX_ACT_SILU>{}); break;
+    case MTX_ACT_GELU_TANH: f(std::integral_constant<int, MTX_ACT_GELU_TANH>{}); break;
+    default: f(std::integral_constant<int, -1>{}); break;
   }
-#undef MTX_G256S
 }
 
 // measured on MI355X (tools/bench_kernels.py, FLUX shapes, random data): the ping-pong loop with descriptor DMA and the 3/3/2/0
 // piece spread runs 1119-1341 TFLOP/s in bf16; the schedules it replaced (flat-address ping-pong, one-barrier, K = 32 ring, wave
 // specialised DMA) were 2-15 % behind on every shape and are gone (docs/experiments.md keeps the numbers).
+template <typename T, bool F8>
+static void launch_gemm256_tiles(const GemmParams& p, dim3 grid, void* stream) {
+  with_gemm256_act(p.act, [&](auto act) {
+    if constexpr (F8) MTX_LAUNCH((gemm256_f8_kernel<T, decltype(act)::value>), grid, dim3(512), 0, stream, p);
+    else MTX_LAUNCH((gemm256_kernel<T, decltype(act)::value>), grid, dim3(512), 0, stream, p);
+  });
+}
+
+template <typename T, bool F8>
+static void launch_gemm256_slices(const GemmParams& p, unsigned pieces, void* stream) {
+  gemm256_tickets_ready(p.tickets, stream);
+  with_gemm256_act(p.act, [&](auto act) { MTX_LAUNCH((gemm256_slice_kernel<T, F8, decltype(act)::value>), dim3(pieces), dim3(512), 0, stream, p); });
+}
+
 // Strip width of the tile map.  Measured on MI355X (same process, identical bytes: profiles/r06_visit_a / _b logs): with ONE strip every
 // XCD walks all tile columns from column 0 at the same time, i.e. eight L2s pull the same W panel over the fabric at once; two strips put
 // XCDs 0-3 and 4-7 on different halves of W.  The MX-fp8 kernel (half the time per byte of the 16-bit one) gains on the wide problems —
@@ -989,47 +974,54 @@ static unsigned gemm256_choose_strip(unsigned tiles_n, bool f8) {
   return w < 1 ? 1 : w;
 }
 
+// Whole tiles [0, tiles - count) go to the tile kernel, the last `count` tiles run as `s` K slices each; count = 0 is the unsplit launch.
 template <typename T, bool F8>
-static void launch_gemm256(const GemmParams& p0, dim3 grid, void* stream, bool force, bool nosplit, unsigned forced_slices) {
-  GemmParams p = p0;
+static void launch_gemm256(GemmParams p, dim3 grid, void* stream, int flags) {
+  const bool force = (flags & MTX_GEMM_FORCE_TILE256) != 0, nosplit = (flags & MTX_GEMM_NO_SPLIT) != 0;
+  const unsigned forced_slices = ((unsigned)flags >> 8) & 0xffu;
   p.strip_w = gemm256_choose_strip(p.tiles_n, F8);
-  const unsigned tiles = p.tiles_m * p.tiles_n, cus = (unsigned)gemm_num_cus(), rem = tiles % cus;
+  const unsigned tiles = p.tiles_m * p.tiles_n, cus = (unsigned)num_cus_or(256), rem = tiles % cus;
   const long nk = p.k / p.bk;
   const bool can = p.part != nullptr && cus <= 320 && grid.y == 1 && !nosplit;
+  unsigned count = 0, s = 0;
+  // `n` tiles as K slices if that beats `limit` (the cost of running them whole), or if the caller forces a slice count that fits
+  auto try_slices = [&](unsigned n, double limit) {
+    s = gemm256_choose_slices(n, nk, cus, limit);
+    if (forced_slices >= 2 && (long)n * forced_slices <= G2_MAX_PIECES && (long)forced_slices * 2 <= nk) s = forced_slices;
+    if (s) count = n;
+  };
   // left-over tiles of the last wave: K slices when they finish clearly before a whole extra tile time would
-  if (can && tiles > cus && rem > 0 && nk >= (force ? 4 : (F8 ? 32 : 64))) {
-    unsigned s = gemm256_choose_slices(rem, nk, cus, 0.97 * (double)nk);
-    if (forced_slices >= 2 && (long)rem * forced_slices <= G2_MAX_PIECES && (long)forced_slices * 2 <= nk) s = forced_slices;
-    if (s) {
-      p.n_full = tiles - rem; grid.x = p.n_full;
-      launch_gemm256_tiles<T, F8>(p, grid, stream);
-      p.slices = s; p.slice_len = (unsigned)((nk + s - 1) / s);
-      launch_gemm256_slices<T, F8>(p, rem * s, stream);
-      g_last_split[0] = (int)p.n_full; g_last_split[1] = (int)s; g_last_split[2] = (int)(rem * s);
-      return;
-    }
-  }
+  if (can && tiles > cus && rem > 0 && nk >= (force ? 4 : (F8 ? 32 : 64))) try_slices(rem, 0.97 * (double)nk);
   // few tiles but a long K (FLUX text-stream ff2: 24 tiles x 192 iterations): slices over the whole problem
-  if (can && tiles * 2 <= cus && nk >= (F8 ? 64 : 128)) {
-    unsigned s = gemm256_choose_slices(tiles, nk, cus, 0.9 * (double)nk);
-    if (forced_slices >= 2 && (long)tiles * forced_slices <= G2_MAX_PIECES && (long)forced_slices * 2 <= nk) s = forced_slices;
-    if (s) {
-      p.n_full = 0; p.slices = s; p.slice_len = (unsigned)((nk + s - 1) / s);
-      launch_gemm256_slices<T, F8>(p, tiles * s, stream);
-      g_last_split[0] = 0; g_last_split[1] = (int)s; g_last_split[2] = (int)(tiles * s);
-      return;
-    }
+  else if (can && tiles * 2 <= cus && nk >= (F8 ? 64 : 128)) try_slices(tiles, 0.9 * (double)nk);
+  const unsigned whole = tiles - count;
+  if (count) p.n_full = whole;
+  if (whole) { grid.x = whole; launch_gemm256_tiles<T, F8>(p, grid, stream); }
+  if (count) {
+    p.slices = s; p.slice_len = (unsigned)((nk + s - 1) / s);
+    launch_gemm256_slices<T, F8>(p, count * s, stream);
   }
-  launch_gemm256_tiles<T, F8>(p, grid, stream);
-  g_last_split[0] = (int)tiles; g_last_split[1] = 1; g_last_split[2] = 0;
+  g_last_split[0] = (int)whole; g_last_split[1] = count ? (int)s : 1; g_last_split[2] = (int)(count * s);
 }
 
-int gemm_f32_launch(const mtx_gemm_args* a, void* stream, const char** err);      // f32ops.hip
-int gemm_launch(const mtx_gemm_args* a, void* stream, const char** err) {
+static long gemm_batch(const mtx_gemm_args* a) { return a->batch > 0 ? a->batch : 1; }
+static bool gemm_out_f32(const mtx_gemm_args* a) { return a->out_dtype == MTX_F32 && a->dtype != MTX_F32; }
+// every output, residual and gate row is a whole number of 16-byte chunks
+static bool gemm_rows_vec(const mtx_gemm_args* a) {
+  return a->n % 8 == 0 && a->ldc % 8 == 0 && (!a->res || a->ldres % 8 == 0) && (!a->gate || a->ldgate % 8 == 0) && a->c_bstride % 8 == 0;
+}
+// one 256-tile's rows of A and of W under a 32-bit buffer descriptor
+static bool gemm_fits32(const mtx_gemm_args* a) {
+  const size_t esz = a->in_dtype == MTX_F8 ? 1 : 2;
+  return ((size_t)G2_BM * a->lda + a->k) * esz < (1ull << 32) && ((size_t)G2_BN * a->ldw + a->k) * esz < (1ull << 32);
+}
+
+// common checks, then the fp8 kernel's, then its SwiGLU epilogue's; fp32 operands (dtype == MTX_F32) are checked by their own launcher
+static int gemm_validate(const mtx_gemm_args* a, const char** err) {
   if (!a->a || !a->w || !a->c) { *err = "gemm: null operand"; return MTX_ERR_INVALID; }
   if (a->m < 1 || a->n < 1 || a->k < 1) { *err = "gemm: empty problem"; return MTX_ERR_INVALID; }
-  if (a->dtype == MTX_F32) return gemm_f32_launch(a, stream, err);      // fp32 operands: the vector-ALU path (SAM's high-precision mask decoder)
-  const bool f8 = a->in_dtype == MTX_F8;
+  if (a->dtype == MTX_F32) return MTX_OK;
+  const bool f8 = a->in_dtype == MTX_F8, t16 = a->dtype == MTX_BF16 || a->dtype == MTX_F16;
   if (a->glu_q != nullptr && !f8) { *err = "gemm: the SwiGLU epilogue exists on the fp8 kernel only"; return MTX_ERR_INVALID; }
   if (a->in_dtype != 0 && !f8 && a->in_dtype != a->dtype) { *err = "gemm: in_dtype must be 0, dtype or MTX_F8"; return MTX_ERR_INVALID; }
   if (a->k % 8 || a->lda % 8 || a->ldw % 8) { *err = "gemm: K, lda, ldw must be multiples of 8 (16-byte chunks)"; return MTX_ERR_INVALID; }
@@ -1041,7 +1033,23 @@ int gemm_launch(const mtx_gemm_args* a, void* stream, const char** err) {
   if (a->out_dtype != a->dtype && a->out_dtype != MTX_F32) { *err = "gemm: out_dtype must equal dtype or be f32"; return MTX_ERR_INVALID; }
   if (a->res_dtype != 0 && a->res_dtype != a->dtype && !(a->res_dtype == MTX_F32 && a->out_dtype == MTX_F32)) { *err = "gemm: res_dtype must be 0, dtype, or f32 together with an f32 output"; return MTX_ERR_INVALID; }
   if (a->w_lo != nullptr && (f8 || ((size_t)a->w_lo & 15))) { *err = "gemm: w_lo (the low half of a weight pair) needs 16-bit operands and a 16-byte aligned pointer"; return MTX_ERR_INVALID; }
-  GemmParams p;
+  if (!t16) { *err = f8 ? "gemm(fp8): dtype (epilogue / output type) must be bf16 or f16" : "gemm: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!f8) return MTX_OK;
+  if (!a->a_scale || !a->w_scale || a->lds_a < a->m || a->lds_w < a->n) { *err = "gemm(fp8): scale planes missing or lds_a / lds_w shorter than the row count"; return MTX_ERR_INVALID; }
+  if (a->k % 128 || a->lda % 16 || a->ldw % 16 || !gemm_rows_vec(a) || gemm_out_f32(a) || gemm_batch(a) != 1 || !gemm_fits32(a)) { *err = "gemm(fp8): needs K % 128 == 0, lda / ldw % 16 == 0, N / ldc % 8 == 0, 16-bit output, batch 1"; return MTX_ERR_INVALID; }
+  if (a->glu_q != nullptr &&
+      (!a->glu_scale || a->glu_col0 < 0 || a->glu_col0 % G2_BN || a->glu_col0 >= a->n || (a->n - a->glu_col0) % G2_BN || a->glu_ldq % 16 ||
+       ((size_t)a->glu_q & 15) || a->glu_lds < a->m || a->bias || a->gate || a->res || a->act != MTX_ACT_NONE)) {
+    *err = "gemm(fp8, SwiGLU epilogue): needs glu_col0 and n - glu_col0 multiples of 256, glu_ldq % 16 == 0, glu_lds >= m, and no bias / gate / res / act";
+    return MTX_ERR_INVALID;
+  }
+  return MTX_OK;
+}
+
+// everything the kernels read except the tile counts, which belong to the route (gemm_launch)
+static GemmParams gemm_params(const mtx_gemm_args* a) {
+  const bool f8 = a->in_dtype == MTX_F8;
+  GemmParams p{};
   p.a = (const unsigned char*)a->a; p.w = (const unsigned char*)a->w; p.bias = a->bias;
   p.res = (const unsigned char*)a->res; p.gate = (const unsigned char*)a->gate; p.c = (unsigned char*)a->c;
   p.w2 = (const unsigned char*)a->w_lo; p.res_f32 = (a->res != nullptr && a->res_dtype == MTX_F32) ? 1 : 0;
@@ -1050,70 +1058,64 @@ int gemm_launch(const mtx_gemm_args* a, void* stream, const char** err) {
   p.a_bs = a->a_bstride; p.w_bs = a->w_bstride; p.c_bs = a->c_bstride; p.res_bs = a->res_bstride;
   p.gate_rows_per = a->gate_rows_per > 0 ? a->gate_rows_per : 1;
   p.act = a->act; p.act_param = a->act_param; p.alpha = a->alpha == 0.f ? 1.f : a->alpha;
-  p.out_f32 = a->out_dtype == MTX_F32 && a->dtype != MTX_F32;
-  p.n_full = 0; p.slices = 1; p.slice_len = 0;
-  p.part = (a->workspace && a->workspace_bytes >= (int64_t)MTX_GEMM_WORKSPACE_BYTES) ? reinterpret_cast<float*>(a->workspace) : nullptr;
-  p.tickets = p.part ? reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(a->workspace) + MTX_GEMM_WORKSPACE_BYTES - G2_TICKET_BYTES) : nullptr;
+  p.out_f32 = gemm_out_f32(a);
+  p.slices = 1;                                                // n_full = 0, slice_len = 0: no K-slice tail until launch_gemm256 plans one
+  if (a->workspace && a->workspace_bytes >= (int64_t)MTX_GEMM_WORKSPACE_BYTES) {
+    p.part = reinterpret_cast<float*>(a->workspace);
+    p.tickets = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(a->workspace) + MTX_GEMM_WORKSPACE_BYTES - G2_TICKET_BYTES);
+  }
   p.a_scale = reinterpret_cast<const unsigned*>(a->a_scale); p.w_scale = reinterpret_cast<const unsigned*>(a->w_scale);
   p.lds_a = a->lds_a; p.lds_w = a->lds_w;
-  p.glu_q = nullptr; p.glu_scale = nullptr; p.glu_ldq = p.glu_lds = p.glu_col0 = 0;
-  p.strip_w = 0x7fffffffu;
   p.bk = f8 ? 128 : G2_BK;
-  p.tiles_m = (unsigned)((a->m + GBM - 1) / GBM);
-  p.tiles_n = (unsigned)((a->n + GBN - 1) / GBN);
-  const long batch = a->batch > 0 ? a->batch : 1;
-  const bool force = (a->flags & MTX_GEMM_FORCE_TILE256) != 0, nosplit = (a->flags & MTX_GEMM_NO_SPLIT) != 0;
-  const unsigned forced_slices = ((unsigned)a->flags >> 8) & 0xffu;
-  // large, aligned problems: the 256 x 256 LDS-DMA kernel (needs whole K tiles and 16-byte rows everywhere)
-  const long t256 = ((a->m + G2_BM - 1) / G2_BM) * ((a->n + G2_BN - 1) / G2_BN) * batch;
-  const bool vec = a->n % 8 == 0 && a->ldc % 8 == 0 && (!a->res || a->ldres % 8 == 0) && (!a->gate || a->ldgate % 8 == 0) && a->c_bstride % 8 == 0;
-  const size_t esz = f8 ? 1 : 2;
-  const bool fits32 = ((size_t)G2_BM * a->lda + a->k) * esz < (1ull << 32) && ((size_t)G2_BN * a->ldw + a->k) * esz < (1ull << 32);      // one tile's rows under a descriptor
-  if (f8) {
-    if (a->dtype != MTX_BF16 && a->dtype != MTX_F16) { *err = "gemm(fp8): dtype (epilogue / output type) must be bf16 or f16"; return MTX_ERR_INVALID; }
-    if (!a->a_scale || !a->w_scale || a->lds_a < a->m || a->lds_w < a->n) { *err = "gemm(fp8): scale planes missing or lds_a / lds_w shorter than the row count"; return MTX_ERR_INVALID; }
-    if (a->k % 128 || a->lda % 16 || a->ldw % 16 || !vec || p.out_f32 || batch != 1 || !fits32) { *err = "gemm(fp8): needs K % 128 == 0, lda / ldw % 16 == 0, N / ldc % 8 == 0, 16-bit output, batch 1"; return MTX_ERR_INVALID; }
-    p.tiles_m = (unsigned)((a->m + G2_BM - 1) / G2_BM);
-    p.tiles_n = (unsigned)((a->n + G2_BN - 1) / G2_BN);
-    dim3 g2(p.tiles_m * p.tiles_n, 1);
-    if (a->glu_q != nullptr) {
-      if (!a->glu_scale || a->glu_col0 < 0 || a->glu_col0 % G2_BN || a->glu_col0 >= a->n || (a->n - a->glu_col0) % G2_BN || a->glu_ldq % 16 ||
-          ((size_t)a->glu_q & 15) || a->glu_lds < a->m || a->bias || a->gate || a->res || a->act != MTX_ACT_NONE) {
-        *err = "gemm(fp8, SwiGLU epilogue): needs glu_col0 and n - glu_col0 multiples of 256, glu_ldq % 16 == 0, glu_lds >= m, and no bias / gate / res / act";
-        return MTX_ERR_INVALID;
-      }
-      p.glu_q = reinterpret_cast<unsigned char*>(a->glu_q); p.glu_scale = reinterpret_cast<unsigned*>(a->glu_scale);
-      p.glu_ldq = a->glu_ldq; p.glu_lds = a->glu_lds; p.glu_col0 = a->glu_col0;
-      p.strip_w = gemm256_choose_strip(p.tiles_n, true);
-      if (a->dtype == MTX_BF16) MTX_LAUNCH((gemm256_f8_glu_kernel<__bf16>), g2, dim3(512), 0, stream, p);
-      else MTX_LAUNCH((gemm256_f8_glu_kernel<_Float16>), g2, dim3(512), 0, stream, p);
-      return MTX_OK;
-    }
-    if (a->dtype == MTX_BF16) launch_gemm256<__bf16, true>(p, g2, stream, force, nosplit, forced_slices); else launch_gemm256<_Float16, true>(p, g2, stream, force, nosplit, forced_slices);
-    return MTX_OK;
+  if (a->glu_q != nullptr) {
+    p.glu_q = reinterpret_cast<unsigned char*>(a->glu_q); p.glu_scale = reinterpret_cast<unsigned*>(a->glu_scale);
+    p.glu_ldq = a->glu_ldq; p.glu_lds = a->glu_lds; p.glu_col0 = a->glu_col0;
   }
+  p.strip_w = 0x7fffffffu;                                     // one strip; the 256-tile routes choose (gemm256_choose_strip)
+  return p;
+}
+
+enum class GemmRoute { Tile128, Tile128Pair, Tile256, Tile256F8, Tile256F8Glu };
+
+// Which kernel family runs a validated problem on a device of `cus` compute units.  (How a 256-tile launch splits its tail: launch_gemm256.)
+static GemmRoute gemm_route(const mtx_gemm_args* a, int cus) {
+  if (a->in_dtype == MTX_F8) return a->glu_q != nullptr ? GemmRoute::Tile256F8Glu : GemmRoute::Tile256F8;      // fp8 exists as 256 tiles only
+  // large, aligned problems: the 256 x 256 LDS-DMA kernel (needs whole K tiles and 16-byte rows everywhere)
+  const bool can256 = !gemm_out_f32(a) && a->w_lo == nullptr && a->k % G2_BK == 0 && gemm_rows_vec(a) && gemm_fits32(a);
   // with the descriptor-DMA loop the 256-tile kernel wins from ~24 tiles up even though most CUs idle (512x9216x3072: 55 vs 68 us,
   // 1024x4608x1152: 24.5 vs 32.7 us); below that the 128-tile kernel's extra parallelism pays.
   // (short K — SAM's 576-wide stage — keeps the old threshold: the tile prologue / epilogue dominates there, encoder 12.5 vs 11.8 ms)
   // and so do shapes that would pad a 256-tile row or column by more than 10 % (SAM's N = 576: 3 columns for 2.25)
-  const long t256m = (a->m + G2_BM - 1) / G2_BM, t256n = (a->n + G2_BN - 1) / G2_BN;
-  const bool snug = a->m * 10 >= t256m * G2_BM * 9 && a->n * 10 >= t256n * G2_BN * 9;
-  const long min_tiles = force ? 1 : ((a->k >= 1024 && snug) ? 24 : 160);
-  const bool few_long = a->workspace != nullptr && batch == 1 && t256 * 2 <= gemm_num_cus() && a->k / G2_BK >= 128 && a->m >= 256;
-  if (!p.out_f32 && a->w_lo == nullptr && a->k % G2_BK == 0 && vec && fits32 && (t256 >= min_tiles || few_long) && (a->dtype == MTX_BF16 || a->dtype == MTX_F16)) {
-    p.tiles_m = (unsigned)((a->m + G2_BM - 1) / G2_BM);
-    p.tiles_n = (unsigned)((a->n + G2_BN - 1) / G2_BN);
-    dim3 g2(p.tiles_m * p.tiles_n, (unsigned)batch);
-    if (a->dtype == MTX_BF16) launch_gemm256<__bf16, false>(p, g2, stream, force, nosplit, forced_slices); else launch_gemm256<_Float16, false>(p, g2, stream, force, nosplit, forced_slices);
-    return MTX_OK;
-  }
-  dim3 grid(p.tiles_m * p.tiles_n, (unsigned)batch);
-  if (a->dtype != MTX_BF16 && a->dtype != MTX_F16) { *err = "gemm: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
-  if (p.w2 != nullptr) {
-    if (a->dtype == MTX_BF16) MTX_LAUNCH((gemm_kernel<__bf16, true>), grid, dim3(256), 0, stream, p);
-    else MTX_LAUNCH((gemm_kernel<_Float16, true>), grid, dim3(256), 0, stream, p);
-  } else if (a->dtype == MTX_BF16) MTX_LAUNCH((gemm_kernel<__bf16, false>), grid, dim3(256), 0, stream, p);
-  else MTX_LAUNCH((gemm_kernel<_Float16, false>), grid, dim3(256), 0, stream, p);
+  const long tm = (a->m + G2_BM - 1) / G2_BM, tn = (a->n + G2_BN - 1) / G2_BN, batch = gemm_batch(a), t256 = tm * tn * batch;
+  const bool snug = a->m * 10 >= tm * G2_BM * 9 && a->n * 10 >= tn * G2_BN * 9;
+  const long min_tiles = (a->flags & MTX_GEMM_FORCE_TILE256) ? 1 : ((a->k >= 1024 && snug) ? 24 : 160);
+  // fewer tiles than that but a long K and a workspace: launch_gemm256 slices the whole problem over K
+  const bool few_long = a->workspace != nullptr && batch == 1 && t256 * 2 <= cus && a->k / G2_BK >= 128 && a->m >= 256;
+  if (can256 && (t256 >= min_tiles || few_long)) return GemmRoute::Tile256;
+  return a->w_lo != nullptr ? GemmRoute::Tile128Pair : GemmRoute::Tile128;
+}
+
+int gemm_f32_launch(const mtx_gemm_args* a, void* stream, const char** err);      // f32ops.hip
+int gemm_launch(const mtx_gemm_args* a, void* stream, const char** err) {
+  if (const int rc = gemm_validate(a, err)) return rc;
+  if (a->dtype == MTX_F32) return gemm_f32_launch(a, stream, err);      // fp32 operands: the vector-ALU path (SAM's high-precision mask decoder)
+  GemmParams p = gemm_params(a);
+  const GemmRoute route = gemm_route(a, num_cus_or(256));
+  const bool big = route != GemmRoute::Tile128 && route != GemmRoute::Tile128Pair;
+  const long bm = big ? G2_BM : GBM, bn = big ? G2_BN : GBN;
+  p.tiles_m = (unsigned)((a->m + bm - 1) / bm); p.tiles_n = (unsigned)((a->n + bn - 1) / bn);
+  if (route == GemmRoute::Tile256F8Glu) p.strip_w = gemm256_choose_strip(p.tiles_n, true);
+  const dim3 grid(p.tiles_m * p.tiles_n, (unsigned)gemm_batch(a));
+  with_storage_type(a->dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    switch (route) {
+      case GemmRoute::Tile128: MTX_LAUNCH((gemm_kernel<T, false>), grid, dim3(256), 0, stream, p); break;
+      case GemmRoute::Tile128Pair: MTX_LAUNCH((gemm_kernel<T, true>), grid, dim3(256), 0, stream, p); break;
+      case GemmRoute::Tile256: launch_gemm256<T, false>(p, grid, stream, a->flags); break;
+      case GemmRoute::Tile256F8: launch_gemm256<T, true>(p, grid, stream, a->flags); break;
+      case GemmRoute::Tile256F8Glu: MTX_LAUNCH((gemm256_f8_glu_kernel<T>), grid, dim3(512), 0, stream, p); break;
+    }
+  });
   return MTX_OK;
 }
 

@@ -515,4 +515,34 @@ static inline void zero_words_async(void* p, size_t bytes, void* stream) {      
   MTX_LAUNCH(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<unsigned*>(p), n);
 }
 
+// ---- launcher helpers (host) -------------------------------------------------------------------------------------
+// Compute units of the current device, asked once; -1 when the query fails.  The simulator plays a 3-CU device.
+static inline int num_cus() {
+  static int cus = 0;
+  if (cus <= 0) {
+#ifdef MTX_EMU
+    cus = 3;
+#else
+    int dev = 0; hipDeviceProp_t prop;
+    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : -1;
+#endif
+  }
+  return cus;
+}
+// for launchers where the count only shapes a split: a guess is better than refusing the launch
+static inline int num_cus_or(int fallback) { const int cus = num_cus(); return cus > 0 ? cus : fallback; }
+
+// Storage-type dispatch: calls f(TypeTag<T>{}) with T = __bf16 or _Float16 as `dtype` says and returns true; false (f not called) for
+// any other dtype — the error text is the call site's.  In f: `typedef typename decltype(t)::type T;`
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F>
+static inline bool with_storage_type(int dtype, F&& f) {
+  if (dtype == MTX_BF16) { f(TypeTag<__bf16>{}); return true; }
+  if (dtype == MTX_F16) { f(TypeTag<_Float16>{}); return true; }
+  return false;
+}
+// the common case, a kernel templated on the storage type alone: launches kernel<T>, or yields false without launching
+#define MTX_LAUNCH_T(dtype, kernel, grid, block, stream, ...) \
+  mtx::with_storage_type((dtype), [&](auto t_) { MTX_LAUNCH((kernel<typename decltype(t_)::type>), (grid), (block), 0, (stream), __VA_ARGS__); })
+
 }  // namespace mtx

@@ -174,15 +174,16 @@ int norm_launch(const mtx_norm_args* a, void* stream, const char** err) {
   // together with x) or the general one.  Round 5 measured two more forms (modulation after the reductions: 21.6 against 18.8 us; held to 96
   // registers: 23.1) — dropped, profiles/r05_visit_o_*.log.
   const bool full = a->c % 512 == 0 && (per_lane == 2 || per_lane == 4 || per_lane == 6 || per_lane == NORM_MAXCH) && !a->gamma && !a->beta && a->act == MTX_ACT_NONE;
-#define MTX_NORM_T(TT, N) do { if (!full) MTX_LAUNCH((norm_packed_kernel<TT, N, false, false>), dim3(blocks), dim3(256), 0, stream, *a); \
-                               else MTX_LAUNCH((norm_packed_kernel<TT, N, true, true>), dim3(blocks), dim3(256), 0, stream, *a); } while (0)
-#define MTX_NORM(N) do { if (a->dtype == MTX_BF16) MTX_NORM_T(__bf16, N); else MTX_NORM_T(_Float16, N); } while (0)
-  if (per_lane <= 2) MTX_NORM(2);
-  else if (per_lane <= 4) MTX_NORM(4);
-  else if (per_lane <= 6) MTX_NORM(6);
-  else MTX_NORM(NORM_MAXCH);
-#undef MTX_NORM_T
+  with_storage_type(a->dtype, [&](auto t) {      // (dtype checked above)
+    typedef typename decltype(t)::type T;
+#define MTX_NORM(N) do { if (!full) MTX_LAUNCH((norm_packed_kernel<T, N, false, false>), dim3(blocks), dim3(256), 0, stream, *a); \
+                         else MTX_LAUNCH((norm_packed_kernel<T, N, true, true>), dim3(blocks), dim3(256), 0, stream, *a); } while (0)
+    if (per_lane <= 2) MTX_NORM(2);
+    else if (per_lane <= 4) MTX_NORM(4);
+    else if (per_lane <= 6) MTX_NORM(6);
+    else MTX_NORM(NORM_MAXCH);
 #undef MTX_NORM
+  });
   return MTX_OK;
 }
 
@@ -296,15 +297,12 @@ int groupnorm_launch(const mtx_groupnorm_args* a, void* stream, const char** err
   dim3 g1((unsigned)nb, (unsigned)a->n);
   long tot = a->n * a->hw * C8;
   long blocks = (tot + 255) / 256; if (blocks > 8192) blocks = 8192;
-  if (a->dtype == MTX_BF16) {
-    MTX_LAUNCH((gn_stats_kernel<__bf16>), g1, dim3(256), 0, stream, *a, ppb);
-    MTX_LAUNCH(gn_finalize_kernel, dim3((unsigned)(a->n * a->groups)), dim3(256), 0, stream, *a, nb);
-    MTX_LAUNCH((gn_apply_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  } else if (a->dtype == MTX_F16) {
-    MTX_LAUNCH((gn_stats_kernel<_Float16>), g1, dim3(256), 0, stream, *a, ppb);
-    MTX_LAUNCH(gn_finalize_kernel, dim3((unsigned)(a->n * a->groups)), dim3(256), 0, stream, *a, nb);
-    MTX_LAUNCH((gn_apply_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  } else { *err = "groupnorm: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!with_storage_type(a->dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        MTX_LAUNCH((gn_stats_kernel<T>), g1, dim3(256), 0, stream, *a, ppb);
+        MTX_LAUNCH(gn_finalize_kernel, dim3((unsigned)(a->n * a->groups)), dim3(256), 0, stream, *a, nb);
+        MTX_LAUNCH((gn_apply_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
+      })) { *err = "groupnorm: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 

@@ -47,9 +47,7 @@ int quant_launch(const mtx_quant_args* a, void* stream, const char** err) {
   const long total = a->rows * (a->k / 8);
   long blocks = (total + 255) / 256;
   if (blocks > 256 * 64) blocks = 256 * 64;
-  if (a->dtype == MTX_BF16) MTX_LAUNCH((quant_mx_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else if (a->dtype == MTX_F16) MTX_LAUNCH((quant_mx_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
-  else { *err = "quantize_mx: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!MTX_LAUNCH_T(a->dtype, quant_mx_kernel, dim3((unsigned)blocks), dim3(256), stream, *a)) { *err = "quantize_mx: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 

@@ -232,7 +232,8 @@ typedef enum mtx_ew_kind {
   MTX_EW_UPSAMPLE2X = 4,  /* nearest 2x: y[n, 2h+i, 2w+j, c] = a[n, h, w, c] (+ b if given)  */
   MTX_EW_MAXPOOL = 5,     /* k x k, stride s (i0 = k, i1 = s), pad k/2 for odd k, 0 for even k */
   MTX_EW_COPY = 6,        /* strided channel-slice copy                                       */
-  MTX_EW_GATE_RES = 7,    /* y = b + a * g[row / rows_per, c]   (DiT gated residual)         */
+  MTX_EW_GATE_RES = 7,    /* y = b + a * s[n, c], s of the 16-bit type, row stride lds: one gate row per image n of h*w pixels
+                             (a DiT gate per rows_per tokens: n = rows / rows_per, h*w = rows_per; lds = 0: one row for all) */
   MTX_EW_ROW_GATHER = 8,  /* y[r, :] = a[idx[r], :], idx = (const int32_t*)s, r < n*h*w       */
   MTX_EW_IM2COL = 9,      /* y[r, tap*C + c] = a[n, oy*s-pad+ky, ox*s-pad+kx, c] (zero outside);
                              i0 = k, i1 = stride, pad = k/2; optional s = int32 row map

@@ -3,6 +3,7 @@ import pytest
 
 import exact_checks as ec
 import op_checks as oc
+import stream_checks as sc
 from mangatranslator_amd.hip import abi
 
 pytestmark = pytest.mark.gpu
@@ -339,3 +340,31 @@ def test_attention_dyadic_softmax(hip_lib, dtype):
     ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1024, sk=2100, d=128, late_max=True, f8_scores=True, seed=1)
     ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, seed=2)
     ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, seed=3)
+
+
+# ---- exact inputs for the streaming kernels (stream_checks.py): norms within half a spacing of T plus a measured fp32 slack, element-wise kinds with zero differing elements
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", sc.NORM_CASES + sc.NORM_CASES_GPU)
+def test_norm_exact(hip_lib, dtype, cfg):
+    sc.check_norm_exact(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("c", [1024, 3072, 6144])
+def test_norm_forms_give_identical_bytes(hip_lib, dtype, c):
+    """csrc/norm.hip: the straight-line kernel (no affine) and the general one (gamma = 1) on the same modulated rows, LayerNorm and RMSNorm"""
+    sc.check_norm_forms_equal(hip_lib, dtype, rows=7, c=c)
+    sc.check_norm_forms_equal(hip_lib, dtype, rows=6, c=c, kind=1, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", sc.GROUPNORM_CASES)
+def test_groupnorm_exact(hip_lib, dtype, cfg):
+    sc.check_groupnorm_exact(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("check", [sc.check_ew_copy_gather, sc.check_ew_im2col, sc.check_ew_resample, sc.check_ew_dwconv, sc.check_ew_arith,
+                                   sc.check_ew_grid_stride], ids=lambda f: f.__name__[9:])
+def test_elementwise_exact(hip_lib, dtype, check):
+    check(hip_lib, dtype)

@@ -6,6 +6,7 @@ import torch
 
 import exact_checks as ec
 import op_checks as oc
+import stream_checks as sc
 from mangatranslator_amd.hip import abi
 
 
@@ -344,3 +345,31 @@ def test_attention_dyadic_softmax(emu_lib, dtype):
 def test_attention_dyadic_softmax_late_maximum(emu_lib):
     ec.check_attention_dyadic(emu_lib, abi.BF16, batch=1, heads=1, sq=1024, sk=2100, d=128, late_max=True)
     ec.check_attention_dyadic(emu_lib, abi.F16, batch=1, heads=1, sq=1024, sk=2100, d=128, late_max=True, f8_scores=True, seed=1)
+
+
+# ---- exact inputs for the streaming kernels (stream_checks.py): norms within half a spacing of T plus a measured fp32 slack, element-wise kinds with zero differing elements
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", sc.NORM_CASES)
+def test_norm_exact(emu_lib, dtype, cfg):
+    sc.check_norm_exact(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("c", [1024, 3072, 6144])
+def test_norm_forms_give_identical_bytes(emu_lib, dtype, c):
+    """csrc/norm.hip: the straight-line kernel (no affine) and the general one (gamma = 1) on the same modulated rows, LayerNorm and RMSNorm"""
+    sc.check_norm_forms_equal(emu_lib, dtype, rows=7, c=c)
+    sc.check_norm_forms_equal(emu_lib, dtype, rows=6, c=c, kind=1, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", sc.GROUPNORM_CASES)
+def test_groupnorm_exact(emu_lib, dtype, cfg):
+    sc.check_groupnorm_exact(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("check", [sc.check_ew_copy_gather, sc.check_ew_im2col, sc.check_ew_resample, sc.check_ew_dwconv, sc.check_ew_arith,
+                                   sc.check_ew_grid_stride], ids=lambda f: f.__name__[9:])
+def test_elementwise_exact(emu_lib, dtype, check):
+    check(emu_lib, dtype)

@@ -416,7 +416,14 @@ typedef struct mtx_detr_args {
  * (v_mfma_scale_f32_32x32x64_f8f6f4): every 32 consecutive k of a row share one E8M0 scale 2^(e - 127), e chosen so that
  * the block's largest magnitude lands in (224, 448] (never saturates); q = RNE(x * 2^-(e - 127)).  q: [rows][ldq] bytes.
  * scale: one uint32 per (row, 128 k): byte b = e of block 4 * (k / 128) + b, laid out scale[(k / 128) * lds + row] so the
- * 32 rows a GEMM wave reads are contiguous.  K % 128 == 0. */
+ * 32 rows a GEMM wave reads are contiguous.  K % 128 == 0.
+ * The rule every producer of this format follows (quantiser, norm twin, gated GEMM epilogue, attention q8; tests/operand_checks.py holds it
+ * against an integer / table reference): with amax the block's largest magnitude, e is the SMALLEST value with 448 * 2^(e - 127) >= amax,
+ * clamped to [1, 253]; e = 127 when amax = 0.  (The kernels take the exponent field of fl32(amax * fl32(1 / 448)) and add one when its
+ * mantissa is not zero; for every finite bf16 / f16 amax that is the same number — e spans 1 .. 247 for bf16, 95 .. 135 for f16.)  A bf16
+ * block whose amax lies below 448 * 2^-126 is clamped to e = 1: its values are scaled by 2^126 and land below (224, 448].  q is
+ * RNE_e4m3(clamp(x * 2^(127 - e), -448, 448)): ties to the even code, never 0x7F / 0xFF, and the sign bit survives on zero — an input of
+ * -0, or a negative value that underflows, gives 0x80 (which the matrix instruction reads as zero). */
 typedef struct mtx_quant_args {
   const void* x; void* q; void* scale;
   int64_t rows, k, ldx, ldq, lds;

@@ -306,7 +306,8 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ---- OCP fp8 e4m3 ------------------------------------------------------------------------------------------
-// two fp32 -> two e4m3 bytes (RNE) in the low (HI = false) or high half of `old`; callers clamp to +-448 first
+// two fp32 -> two e4m3 bytes (RNE) in the low (HI = false) or high half of `old`; callers clamp to +-448 first: the instruction does not
+// saturate (measured: up to 464 -> 0x7E, beyond -> 0x7F, NaN), and the simulator's conversion does the same
 template <bool HI>
 __device__ __forceinline__ unsigned cvt_pk_fp8(float a, float b, unsigned old) {
 #ifdef MTX_EMU

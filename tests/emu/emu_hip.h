@@ -259,11 +259,13 @@ inline float emu_e4m3_to_f32(unsigned char b) {
   else v = ldexpf(1.0f + (float)m / 8.0f, e - 7);
   return s ? -v : v;
 }
-inline unsigned char emu_f32_to_e4m3(float f) {          // round to nearest even, saturating
+// Round to nearest even WITHOUT saturation, as v_cvt_pk_fp8_f32 behaves in the mode the kernels run in (measured on gfx950: 449 .. 464 -> 0x7E,
+// 464 being the tie towards the even code; 465, 480, 1e6, inf -> 0x7F): what rounds beyond 448 comes out as NaN, so a kernel that forgets its
+// clamp to +-448 fails here as it would on hardware
+inline unsigned char emu_f32_to_e4m3(float f) {
   const unsigned char s = std::signbit(f) ? 0x80 : 0;
   float a = fabsf(f);
-  if (std::isnan(a)) return s | 0x7f;
-  if (a >= 448.f) return s | 0x7e;
+  if (std::isnan(a) || a > 464.f) return s | 0x7f;
   int e;
   (void)frexpf(a, &e);                                   // a = mant * 2^e, mant in [0.5, 1)
   e -= 1;                                                // a in [2^e, 2^(e+1))

@@ -3,6 +3,7 @@ import pytest
 
 import exact_checks as ec
 import op_checks as oc
+import operand_checks as pc
 import stream_checks as sc
 from mangatranslator_amd.hip import abi
 
@@ -368,3 +369,67 @@ def test_groupnorm_exact(hip_lib, dtype, cfg):
                                    sc.check_ew_grid_stride], ids=lambda f: f.__name__[9:])
 def test_elementwise_exact(hip_lib, dtype, check):
     check(hip_lib, dtype)
+
+
+# ---- exact inputs for the fp8 operand producers and the FLUX row kernels (operand_checks.py): e4m3 bytes and E8M0 scale words against a table / integer
+# reference on a census of every finite value of the storage type; the row kernels bit-equal to float64 rounded once
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_quantize_mx_census(hip_lib, dtype):
+    pc.check_quantize_census(hip_lib, dtype)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_per_tensor_e4m3_census(hip_lib, dtype):
+    """the rotary kernel's twin and MTX_EW_V_F8T: clamp and convert, every finite value of the storage type"""
+    pc.check_rope_twin_census(hip_lib, dtype)
+    pc.check_v_f8t_census(hip_lib, dtype)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_fused_quantisers_against_the_reference(hip_lib, dtype):
+    """MTX_QUANT_SWIGLU (and MTX_EW_SWIGLU) at zero blocks and overflowing exponentials; the norm twin on the straight-line and the general kernel"""
+    pc.check_swiglu_producers(hip_lib, dtype)
+    pc.check_norm_twin(hip_lib, dtype, rows=7, c=1024)
+    pc.check_norm_twin(hip_lib, dtype, rows=14, c=1152, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_gemm_fp8_gated_epilogue_against_the_reference(hip_lib, dtype):
+    pc.check_gemm_glu_exact(hip_lib, dtype, m=300, col0=0, hid=128, k=256)
+    pc.check_gemm_glu_exact(hip_lib, dtype, m=260, col0=256, hid=256, k=128, alpha=1.0 / 8, row_off=5, q_col_off=128, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("sk", [320, 256])
+def test_attention_fp8_output_selects_rows(hip_lib, dtype, sk):
+    """10 query blocks: the epilogue of the long-sequence kernel (the merge kernel: test_attention_fp8_output_selects_rows_merge)"""
+    pc.check_attention_selector(hip_lib, dtype, sq=1030, sk=sk)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", pc.ROPE_CASES + pc.ROPE_CASES_GPU, ids=lambda c: f"{c['rows']}x{c['hq']}+{c['hk']}x{c['d']}")
+def test_qk_norm_rope_exact(hip_lib, dtype, cfg):
+    pc.check_rope_exact(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_qk_norm_rope_general(hip_lib, dtype):
+    pc.check_rope_general(hip_lib, dtype, rows=19, hq=2, hk=2, d=128)
+    pc.check_rope_general(hip_lib, dtype, rows=18, hq=3, hk=2, d=64, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_softmax_rows_exact(hip_lib, dtype):
+    pc.check_softmax_exact(hip_lib, dtype)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_residual_dist_exact(hip_lib, dtype):
+    pc.check_residual_dist_exact(hip_lib, dtype, rows=33, c=136, ld_extra=24)
+    pc.check_residual_dist_exact(hip_lib, dtype, rows=700, c=768, ld_extra=8, seed=1, expect_trips=2)      # more chunks than MTX_RESDIST_PARTS * 256 threads
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_attention_fp8_output_selects_rows_merge(hip_lib, dtype):
+    """260 query blocks on 256 CUs: four go through the key-split tail and leave through the quantising merge kernel"""
+    pc.check_attention_selector(hip_lib, dtype, sq=33030, sk=320, seed=1)

@@ -36,7 +36,7 @@ extern "C" {
 #define MTX_API
 #endif
 
-#define MTX_ABI_VERSION 9
+#define MTX_ABI_VERSION 10
 
 typedef enum mtx_status {
   MTX_OK = 0,
@@ -119,7 +119,9 @@ typedef struct mtx_conv2d_args {
  *   out_dtype == MTX_F32 (16-bit operands) and dtype == MTX_F32 (which has no gate): no rounding, c = act(alpha * acc + bias) * gate + res in fp32.
  *   fp8 operands: acc already carries the MX block scales (applied by the matrix instruction per 32 k); the epilogue is the one above.
  *   The SwiGLU + MX-fp8 epilogue (glu_q): a = round_T(alpha * acc_a), b = round_T(alpha * acc_b), h = round_T(silu(a) * b), then the
- *   quantiser's rounding of h to e4m3 — the roundings of the two launches it replaces.                    */
+ *   quantiser's rounding of h to e4m3 — the roundings of the two launches it replaces.
+ *   The activation + MX-fp8 epilogue (actq_q): h = round_T(act(alpha * acc + bias)) — the ONE rounding of a launch without gate and res — then
+ *   the quantiser's rounding of h to e4m3; again the roundings of the two launches it replaces.          */
 typedef struct mtx_gemm_args {
   const void* a; const void* w; const float* bias; const void* res; const void* gate; void* c;
   int64_t m, n, k;
@@ -153,6 +155,15 @@ typedef struct mtx_gemm_args {
    * res_dtype: 0 / dtype = res has the storage type; MTX_F32 (with out_dtype MTX_F32 only) = res is fp32 [.., ldres] — an fp32 residual
    * stream is added inside the GEMM that closes a branch. */
   const void* w_lo; int32_t res_dtype;
+  /* ABI 10.  Activation + MX-fp8 epilogue (in_dtype == MTX_F8 only; FLUX.1-Kontext's Linear -> GELU(tanh) -> Linear MLPs, reference diffusers
+   * FeedForward / FluxSingleTransformerBlock.proj_mlp behind core/image/inpainting.py:877-887): EVERY column leaves the kernel as the MX e4m3
+   * operand of the next linear instead of 16-bit values, c is not written and may be NULL:
+   *   h = round_T(act(alpha * acc + bias))  (what the launch would have stored),  columns 32 u .. 32 u + 31 of row m -> the 32 bytes
+   *   actq_q[m * actq_ldq + 32 u ..] and byte (u & 3) of the scale word actq_scale[(u >> 2) * actq_lds + m] — exactly what mtx_quantize_mx
+   *   makes of the 16-bit output (saturation at +-448, scale byte 127 for an all-zero block).
+   * n % 256 == 0 (whole tiles, never the K-slice tail), bias and any act allowed, no gate / res / glu_q, actq_q 16-byte aligned with
+   * actq_ldq % 16 == 0 and >= n, actq_lds >= m.  Rows at or beyond m are not stored.  NULL actq_q = off. */
+  void* actq_q; void* actq_scale; int64_t actq_ldq, actq_lds;
 } mtx_gemm_args;
 #define MTX_GEMM_FORCE_TILE256 1   /* use the 256-tile LDS-DMA kernel whatever the tile count (small-shape tests of that kernel) */
 #define MTX_GEMM_NO_SPLIT 2        /* never hand left-over tiles to the K-slice tail */

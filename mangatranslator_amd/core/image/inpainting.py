@@ -342,6 +342,11 @@ class FluxKontextInpainter:
         self._tail = get_device_tail(lib, pipe.device)
         return self._tail
 
+    def _fp8_linears(self) -> bool:
+        """whether the DiT's block linears run on the MX fp8 path: what the loaded pipeline was built with, else what the manager would build"""
+        dit = getattr(self.pipeline, "transformer", None)
+        return bool(dit.fp8) if hasattr(dit, "fp8") else bool(getattr(self.manager, "flux_kontext_fp8", False))
+
     def _memo_key(self, crop, mask_crop, seed, bbox, padding, blur, ocr_params, strict_mask_clipping, composite_clip_bbox):
         """Key of the crop-sized patch in the stage memo (reference :781-827): crop pixels, a <= 64x64 bilinear signature of the mask
         (robust to one-pixel jitter of the detections), sampler settings and crop geometry.  None when seed == -1 (fresh noise)."""
@@ -351,6 +356,8 @@ class FluxKontextInpainter:
         if self.backend == "sdcpp":
             params.update(sdcpp_cache=self.sdcpp_cache_mode, sdcpp_diffusion_quant=self.sdcpp_diffusion_quant,
                           sdcpp_text_encoder_quant=self.sdcpp_text_encoder_quant)
+        if self._fp8_linears():                 # this package only (absent = the reference's key): a patch made by the fp8 graph is not served to the bf16 one
+            params["arithmetic"] = "fp8"
         if strict_mask_clipping:
             params["strict_clip"] = True
         if composite_clip_bbox is not None:

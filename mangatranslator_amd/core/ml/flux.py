@@ -19,6 +19,9 @@ Graph design (MI355X-first):
   * the modulation vectors depend only on (timestep, guidance, pooled prompt): they are computed once per
     step of a schedule (M = 1 GEMVs that stream 6.4 GB of weights at full size) and cached, instead of
     every step of every region.
+  * fp8 (`FluxDiTHip(fp8=True)`, opt-in): the block linears run on the MX-scaled fp8 matrix instructions (gemm.hip gemm256_f8_kernel) from
+    weights quantised once at load; the adaLN norms, the joint attention and the MLP-in GEMMs (bias + GELU-tanh + quantisation in the epilogue,
+    mtx_gemm_args.actq_*) write the next linear's e4m3 operand themselves into fp8 twins of the buffers above.  Everything else stays bf16 / fp32.
   * VAE: NHWC 3x3 convs with fused bias / residual, GroupNorm+SiLU kernels, nearest-2x fused into a copy,
     Downsample2D's asymmetric pad as a conv mode; the single-head mid-block attention (d = 512) runs as
     GEMM -> row softmax -> GEMM.
@@ -77,10 +80,29 @@ def image_ids(h2, w2, first) -> np.ndarray:
     return ids.reshape(-1, 3)
 
 
+FP8_ALL = ("qkv", "to_out", "ff1", "ff2", "proj_mlp", "proj_out")      # the block linears by kind (both streams of a double block share a kind)
+
+
+class _W8:
+    """MX fp8 copy of one linear's weight: e4m3 bytes [N, K] + E8M0 scale plane (the 16-bit tensor it replaces is dropped)"""
+
+    def __init__(self, q, scale, lds):
+        self.q, self.scale, self.lds = q, scale, lds
+
+
 class FluxDiTHip:
-    def __init__(self, provider, cfg: dict, device, lib=None, text_stream_on_side_lane: bool = True):
+    def __init__(self, provider, cfg: dict, device, lib=None, text_stream_on_side_lane: bool = True,
+                 fp8=False, fused_quant=True, act_epilogue=True, attn_q8=True):
         """provider(name) -> tensor with diffusers' FluxTransformer2DModel parameter of that name.
-        text_stream_on_side_lane: run the double-stream blocks' text ops beside the image ops (plan lanes); False keeps one lane"""
+        text_stream_on_side_lane: run the double-stream blocks' text ops beside the image ops (plan lanes); False keeps one lane.
+        fp8: False (the bf16 graph), True (= every block linear) or a tuple of kinds out of FP8_ALL: those linears run on the MX-scaled fp8
+        matrix instructions (gemm.hip gemm256_f8_kernel) — weights quantised once here (e4m3 + one E8M0 scale per 32 k, biases stay fp32), activations
+        by the kernel that produces them.  Embedders, modulation GEMVs, norm_out / proj_out and all normalisation / softmax / residual arithmetic
+        stay bf16 / fp32.  The three switches below only choose WHO writes an fp8 operand (same bytes either way; False = a separate
+        mtx_quantize_mx launch behind the producer, for A/Bs):
+        fused_quant: the adaLN norms write it (mtx_norm_args.q);  act_epilogue: ff1 / ff1_ctx / proj_mlp apply bias + GELU(tanh) and write it from
+        the GEMM's registers (mtx_gemm_args.actq_*; needs 4 d % 256 == 0 and the MLP's second linear on fp8 too);  attn_q8: the joint attention
+        writes it (mtx_attn_args.q8; head dim 128 and T >= 1024 only)."""
         self.side_lane = text_stream_on_side_lane
         self.lib = lib if lib is not None else get_library()
         self.device = torch.device(device)
@@ -90,6 +112,14 @@ class FluxDiTHip:
         self.hd = D // H
         if self.hd not in (64, 128) or sum(cfg["axes_dim"]) != self.hd:
             raise ModelError("FLUX DiT: head dim must be 64 or 128 and equal sum(axes_dims_rope)")
+        self.fp8 = FP8_ALL if fp8 is True else tuple(fp8 or ())
+        if any(k not in FP8_ALL for k in self.fp8):
+            raise ModelError(f"FLUX DiT: fp8 kinds must come from {FP8_ALL}, got {self.fp8}")
+        if self.fp8 and D % 128:
+            raise ModelError("FLUX DiT fp8 path: d must be a multiple of 128")
+        self.fused_quant = bool(fused_quant)
+        self.act_epilogue = bool(act_epilogue) and (4 * D) % 256 == 0
+        self.attn_q8 = bool(attn_q8) and self.hd == 128
         g = lambda n, dt=None: provider(n).detach().to(self.device, dt if dt is not None else self.tdt).contiguous()
         f32 = torch.float32
         W = {}
@@ -109,28 +139,39 @@ class FluxDiTHip:
         W["mods"] = (torch.cat(mods_w, 0).contiguous(), torch.cat(mods_b, 0).contiguous())
         self.n_vec = W["mods"][0].shape[0] // D
         self.blocks, self.singles = [], []
-        cat3 = lambda p, names: (torch.cat([g(f"{p}.{n}.weight") for n in names], 0).contiguous(),
-                                 torch.cat([g(f"{p}.{n}.bias", f32) for n in names], 0).contiguous())
+        cat3 = lambda p, names, kind="qkv": (self._weight(torch.cat([g(f"{p}.{n}.weight") for n in names], 0).contiguous(), kind),
+                                             torch.cat([g(f"{p}.{n}.bias", f32) for n in names], 0).contiguous())
+        lin = lambda name, kind: (self._weight(g(name + ".weight"), kind), g(name + ".bias", f32))
         for i in range(cfg["layers"]):
             p = f"transformer_blocks.{i}"
             self.blocks.append(dict(
                 qkv=cat3(p + ".attn", ("to_q", "to_k", "to_v")), cqkv=cat3(p + ".attn", ("add_q_proj", "add_k_proj", "add_v_proj")),
                 nqk=torch.cat([g(p + ".attn.norm_q.weight", f32), g(p + ".attn.norm_k.weight", f32)]).contiguous(),
                 cnqk=torch.cat([g(p + ".attn.norm_added_q.weight", f32), g(p + ".attn.norm_added_k.weight", f32)]).contiguous(),
-                out=(g(p + ".attn.to_out.0.weight"), g(p + ".attn.to_out.0.bias", f32)),
-                cout=(g(p + ".attn.to_add_out.weight"), g(p + ".attn.to_add_out.bias", f32)),
-                ff1=(g(p + ".ff.net.0.proj.weight"), g(p + ".ff.net.0.proj.bias", f32)), ff2=(g(p + ".ff.net.2.weight"), g(p + ".ff.net.2.bias", f32)),
-                cff1=(g(p + ".ff_context.net.0.proj.weight"), g(p + ".ff_context.net.0.proj.bias", f32)),
-                cff2=(g(p + ".ff_context.net.2.weight"), g(p + ".ff_context.net.2.bias", f32))))
+                out=lin(p + ".attn.to_out.0", "to_out"), cout=lin(p + ".attn.to_add_out", "to_out"),
+                ff1=lin(p + ".ff.net.0.proj", "ff1"), ff2=lin(p + ".ff.net.2", "ff2"),
+                cff1=lin(p + ".ff_context.net.0.proj", "ff1"), cff2=lin(p + ".ff_context.net.2", "ff2")))
         for i in range(cfg["single_layers"]):
             p = f"single_transformer_blocks.{i}"
             self.singles.append(dict(qkv=cat3(p + ".attn", ("to_q", "to_k", "to_v")),
                                      nqk=torch.cat([g(p + ".attn.norm_q.weight", f32), g(p + ".attn.norm_k.weight", f32)]).contiguous(),
-                                     mlp=(g(p + ".proj_mlp.weight"), g(p + ".proj_mlp.bias", f32)), out=(g(p + ".proj_out.weight"), g(p + ".proj_out.bias", f32))))
+                                     mlp=lin(p + ".proj_mlp", "proj_mlp"), out=lin(p + ".proj_out", "proj_out")))
         self.W = W
         self._plans = PlanCache(6)           # a DiT plan pins ~T x 15 D bytes of activations: a few crop resolutions only
         self._mod_plan = None
         self._mod_cache = {}
+
+    def _weight(self, w16: torch.Tensor, kind: str):
+        """the 16-bit weight, or — for a kind on the fp8 path — its MX fp8 copy"""
+        if kind not in self.fp8:
+            return w16
+        n, k = w16.shape
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        q, scale, lds = pb.quantize(w16, n, k)
+        pb.build().run()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        return _W8(q, scale, lds)
 
     # ---- modulation vectors of one (timestep, guidance, pooled) ------------------------------------------
     def _build_mod_plan(self):
@@ -201,14 +242,45 @@ class FluxDiTHip:
         cat = pb.buf((T, 5 * D), self.tdt)
         vel = pb.buf((t_noise, cfg["in_channels"]), torch.float32)
         m_ = lambda idx: (mod, idx * D)       # (tensor, element offset) of one modulation row
+        on = lambda *kinds: all(k in self.fp8 for k in kinds)
+        is8 = lambda wb: isinstance(wb[0], _W8)
+        lds = (T + 63) // 64 * 64
+        if self.fp8:      # fp8 twins of the GEMM inputs: e4m3 bytes + scale plane
+            twin = lambda k: (pb.buf((T, k), torch.uint8), pb.buf((k // 128, lds), torch.int32, zero=True))
+            nrm8, o8, hid8, cat8 = twin(D), twin(D), twin(4 * D), twin(5 * D)
+        else:
+            nrm8 = o8 = hid8 = cat8 = None
+        ep_ff, ep_mlp = self.act_epilogue and on("ff1", "ff2"), self.act_epilogue and on("proj_mlp", "proj_out")      # who writes hid8 / cat8[:, D:]
+        aq8_dbl, aq8_sgl = self.attn_q8 and T >= 1024 and on("to_out"), self.attn_q8 and T >= 1024 and on("proj_out")  # who writes o8 / cat8[:, :D]
+
+        def quant(pb, src, k, dst, r0, r1, label):
+            pb.quantize(src, r1 - r0, k, x_off=r0 * k, q=dst[0], scale=dst[1], row_off=r0, lds=lds, label=label)
+
+        def linear(pb, src, src8, wb, r0, r1, n, k, out, ldc=None, c_col=0, label="linear", actq=None, **epi):
+            """out[r0:r1, c_col : c_col + n] = epilogue(src[r0:r1, :k] W^T + bias) on the 16-bit or the fp8 kernel, as the weight says; with actq
+            (fp8 only) the result leaves as the MX fp8 operand of the next linear and `out` is not written"""
+            w, bias = wb
+            m, ldc = r1 - r0, (ldc or n)
+            if isinstance(w, _W8):
+                pb.gemm(src8[0], w.q, m, n, k, out=None if actq is not None else out, ldc=ldc, a_off=r0 * k, c_off=r0 * ldc + c_col, bias=bias,
+                        f8=(src8[1], lds, w.scale, w.lds, r0, 0), label=label + ".f8", actq=actq, **epi)
+            else:
+                pb.gemm(src, w, m, n, k, out=out, ldc=ldc, a_off=r0 * k, c_off=r0 * ldc + c_col, bias=bias, label=label, **epi)
 
         def embed(pb):
             pb.gemm(ctx_in, W["context_embedder"][0], t_txt, D, cfg["joint_dim"], bias=W["context_embedder"][1], out=x, label="context_embedder")
             pb.gemm(lat, W["x_embedder"][0], t_img, D, cfg["in_channels"], bias=W["x_embedder"][1], out=x, c_off=t_txt * D, label="x_embedder")
 
-        def adaln(pb, r0, r1, shift_i, scale_i, label):
-            pb.norm(x, nrm, r1 - r0, D, eps=1e-6, kind=0, mod_scale=mod[scale_i], mod_shift=mod[shift_i], rows_per=r1 - r0, ldmod=D,
-                    x_off=r0 * D, y_off=r0 * D, label=label)
+        def adaln(pb, r0, r1, shift_i, scale_i, label, consumers=()):
+            """adaLN LayerNorm of rows [r0, r1).  With fp8 consumers the kernel writes their MX fp8 operand itself (mtx_norm_args.q: bit-identical
+            to a quantiser pass over its 16-bit output, which is then only written if some consumer still reads 16-bit)"""
+            any8 = any(is8(wb) for wb in consumers)
+            to8 = any8 and self.fused_quant
+            need16 = not to8 or any(not is8(wb) for wb in consumers)
+            pb.norm(x, nrm if need16 else None, r1 - r0, D, eps=1e-6, kind=0, mod_scale=mod[scale_i], mod_shift=mod[shift_i], rows_per=r1 - r0, ldmod=D,
+                    x_off=r0 * D, y_off=r0 * D, label=label, q8=nrm8 if to8 else None, q_row_off=r0, lds_q=lds)
+            if any8 and not to8:
+                quant(pb, nrm, D, nrm8, r0, r1, label + ".q")
 
         def rope(pb, buf, r0, r1, gamma_qk, ld, label):
             """per-head RMSNorm + RoPE over the q AND k column slices (2D columns) of rows [r0, r1) in one launch"""
@@ -220,9 +292,22 @@ class FluxDiTHip:
             e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_NORM_ROPE, 0, 1e-6, hd, H, self.dtype
             pb._add(abi.OP_EW, e, label)
 
-        def attention(pb, out_t, out_ld, label):
-            pb.attention(qkv, qkv, qkv, out_t, 1, H, T, T, hd, (0, 3 * D, hd), (0, 3 * D, hd), (0, 3 * D, hd), (0, out_ld, hd),
-                         1.0 / math.sqrt(hd), k_off=D, v_off=2 * D, label=label, q_prescaled=True)
+        def attention(pb, out_t, out_ld, label, q8=None):
+            """q8: the rows leave as the MX fp8 operand of the projection that follows (mtx_attn_args.q8) and out_t is not written"""
+            pb.attention(qkv, qkv, qkv, None if q8 is not None else out_t, 1, H, T, T, hd, (0, 3 * D, hd), (0, 3 * D, hd), (0, 3 * D, hd), (0, out_ld, hd),
+                         1.0 / math.sqrt(hd), k_off=D, v_off=2 * D, label=label, q_prescaled=True, q8=q8)
+
+        def mlp_in(pb, wb, r0, r1, out, ldc, c_col, dst8, fused, consumer, label):
+            """Linear + bias + GELU(tanh) of rows [r0, r1) of nrm into out[:, c_col : c_col + 4 D].  An fp8 consumer reads the twin dst8 instead: written by
+            this GEMM's epilogue (fused: no 16-bit result exists) or by a quantiser launch behind it"""
+            if fused:
+                linear(pb, nrm, nrm8, wb, r0, r1, 4 * D, D, None, ldc=ldc, c_col=c_col, act=abi.ACT_GELU_TANH, label=label,
+                       actq=(dst8[0], dst8[1], ldc, lds, r0, c_col))
+                return
+            linear(pb, nrm, nrm8, wb, r0, r1, 4 * D, D, out, ldc=ldc, c_col=c_col, act=abi.ACT_GELU_TANH, label=label)
+            if is8(consumer):
+                pb.quantize(out, r1 - r0, 4 * D, ldx=ldc, x_off=r0 * ldc + c_col, q=dst8[0], scale=dst8[1], row_off=r0, lds=lds, ldq=ldc, q_col_off=c_col,
+                            label=label + ".q")
 
         # Double-stream blocks: the text stream's ops (512 rows: GEMMs of 24 - 96 tiles that cannot fill the chip, 4 % of a step when run in
         # line) go to the plan's SIDE lane and run beside the image stream's ops; the lanes meet at the joint attention and at the next block.
@@ -231,37 +316,39 @@ class FluxDiTHip:
             b0 = i * 12
             tag = f"dbl{i}"
             with pb.side():
-                adaln(pb, 0, t_txt, b0 + 6, b0 + 7, tag + ".norm1_ctx")
-                pb.gemm(nrm, B["cqkv"][0], t_txt, 3 * D, D, bias=B["cqkv"][1], out=qkv, label=tag + ".qkv_ctx")
+                adaln(pb, 0, t_txt, b0 + 6, b0 + 7, tag + ".norm1_ctx", (B["cqkv"],))
+                linear(pb, nrm, nrm8, B["cqkv"], 0, t_txt, 3 * D, D, qkv, label=tag + ".qkv_ctx")
                 rope(pb, qkv, 0, t_txt, B["cnqk"], 3 * D, tag + ".rope_qk_ctx")
-            adaln(pb, t_txt, T, b0 + 0, b0 + 1, tag + ".norm1")
-            pb.gemm(nrm, B["qkv"][0], t_img, 3 * D, D, bias=B["qkv"][1], out=qkv, a_off=t_txt * D, c_off=t_txt * 3 * D, label=tag + ".qkv")
+            adaln(pb, t_txt, T, b0 + 0, b0 + 1, tag + ".norm1", (B["qkv"],))
+            linear(pb, nrm, nrm8, B["qkv"], t_txt, T, 3 * D, D, qkv, label=tag + ".qkv")
             rope(pb, qkv, t_txt, T, B["nqk"], 3 * D, tag + ".rope_qk")
             pb.join()
-            attention(pb, o, D, tag + ".attn")
+            attention(pb, o, D, tag + ".attn", q8=(o8[0], o8[1], D, lds, 0) if aq8_dbl else None)
+            if on("to_out") and not aq8_dbl:
+                quant(pb, o, D, o8, 0, T, tag + ".attn.q")
             with pb.side():
-                pb.gemm(o, B["cout"][0], t_txt, D, D, bias=B["cout"][1], gate=mod[b0 + 8], gate_rows_per=t_txt, res=x, out=x, label=tag + ".to_add_out")
-                adaln(pb, 0, t_txt, b0 + 9, b0 + 10, tag + ".norm2_ctx")
-                pb.gemm(nrm, B["cff1"][0], t_txt, 4 * D, D, bias=B["cff1"][1], act=abi.ACT_GELU_TANH, out=hid, label=tag + ".ff1_ctx")
-                pb.gemm(hid, B["cff2"][0], t_txt, D, 4 * D, bias=B["cff2"][1], gate=mod[b0 + 11], gate_rows_per=t_txt, res=x, out=x, label=tag + ".ff2_ctx")
-            pb.gemm(o, B["out"][0], t_img, D, D, bias=B["out"][1], gate=mod[b0 + 2], gate_rows_per=t_img, res=x, out=x,
-                    a_off=t_txt * D, c_off=t_txt * D, res_off=t_txt * D, label=tag + ".to_out")
-            adaln(pb, t_txt, T, b0 + 3, b0 + 4, tag + ".norm2")
-            pb.gemm(nrm, B["ff1"][0], t_img, 4 * D, D, bias=B["ff1"][1], act=abi.ACT_GELU_TANH, out=hid, a_off=t_txt * D, c_off=t_txt * 4 * D, label=tag + ".ff1")
-            pb.gemm(hid, B["ff2"][0], t_img, D, 4 * D, bias=B["ff2"][1], gate=mod[b0 + 5], gate_rows_per=t_img, res=x, out=x,
-                    a_off=t_txt * 4 * D, c_off=t_txt * D, res_off=t_txt * D, label=tag + ".ff2")
+                linear(pb, o, o8, B["cout"], 0, t_txt, D, D, x, gate=mod[b0 + 8], gate_rows_per=t_txt, res=x, label=tag + ".to_add_out")
+                adaln(pb, 0, t_txt, b0 + 9, b0 + 10, tag + ".norm2_ctx", (B["cff1"],))
+                mlp_in(pb, B["cff1"], 0, t_txt, hid, 4 * D, 0, hid8, ep_ff, B["cff2"], tag + ".ff1_ctx")
+                linear(pb, hid, hid8, B["cff2"], 0, t_txt, D, 4 * D, x, gate=mod[b0 + 11], gate_rows_per=t_txt, res=x, label=tag + ".ff2_ctx")
+            linear(pb, o, o8, B["out"], t_txt, T, D, D, x, gate=mod[b0 + 2], gate_rows_per=t_img, res=x, res_off=t_txt * D, label=tag + ".to_out")
+            adaln(pb, t_txt, T, b0 + 3, b0 + 4, tag + ".norm2", (B["ff1"],))
+            mlp_in(pb, B["ff1"], t_txt, T, hid, 4 * D, 0, hid8, ep_ff, B["ff2"], tag + ".ff1")
+            linear(pb, hid, hid8, B["ff2"], t_txt, T, D, 4 * D, x, gate=mod[b0 + 5], gate_rows_per=t_img, res=x, res_off=t_txt * D, label=tag + ".ff2")
 
         s0 = cfg["layers"] * 12
 
         def single_block(pb, i, S):
             b0 = s0 + i * 3
             tag = f"sgl{i}"
-            adaln(pb, 0, T, b0 + 0, b0 + 1, tag + ".norm")
-            pb.gemm(nrm, S["qkv"][0], T, 3 * D, D, bias=S["qkv"][1], out=qkv, label=tag + ".qkv")
-            pb.gemm(nrm, S["mlp"][0], T, 4 * D, D, bias=S["mlp"][1], act=abi.ACT_GELU_TANH, out=cat, ldc=5 * D, c_off=D, label=tag + ".proj_mlp")
+            adaln(pb, 0, T, b0 + 0, b0 + 1, tag + ".norm", (S["qkv"], S["mlp"]))
+            linear(pb, nrm, nrm8, S["qkv"], 0, T, 3 * D, D, qkv, label=tag + ".qkv")
+            mlp_in(pb, S["mlp"], 0, T, cat, 5 * D, D, cat8, ep_mlp, S["out"], tag + ".proj_mlp")
             rope(pb, qkv, 0, T, S["nqk"], 3 * D, tag + ".rope_qk")
-            attention(pb, cat, 5 * D, tag + ".attn")
-            pb.gemm(cat, S["out"][0], T, D, 5 * D, bias=S["out"][1], gate=mod[b0 + 2], gate_rows_per=T, res=x, out=x, label=tag + ".proj_out")
+            attention(pb, cat, 5 * D, tag + ".attn", q8=(cat8[0], cat8[1], 5 * D, lds, 0) if aq8_sgl else None)
+            if on("proj_out") and not aq8_sgl:          # the attention half of the concatenation: its own quantiser pass over columns [0, D)
+                pb.quantize(cat, T, D, ldx=5 * D, q=cat8[0], scale=cat8[1], lds=lds, ldq=5 * D, label=tag + ".attn.q")
+            linear(pb, cat, cat8, S["out"], 0, T, D, 5 * D, x, gate=mod[b0 + 2], gate_rows_per=T, res=x, label=tag + ".proj_out")
 
         f0 = s0 + cfg["single_layers"] * 3
 

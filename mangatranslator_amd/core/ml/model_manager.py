@@ -716,6 +716,8 @@ class ModelManager:
             log_message(f"SAM 2.1 model loaded: {'f16' if hip.dtype == abi.F16 else 'bf16'} storage ({why}), precision {want!r}.", always_print=True)
             return self.models[slot]
 
+    flux_kontext_fp8 = False   # opt-in: FLUX.1-Kontext's block linears on the MX fp8 matrix path (FluxDiTHip(fp8=True)); read when the pipeline is loaded
+
     def load_flux_kontext_sdnq(self, low_vram: bool = False, verbose: bool = False):
         """FLUX.1-Kontext as libmtx_hip graphs behind the diffusers call shape (reference :1176-1252).
 
@@ -746,7 +748,9 @@ class ModelManager:
             if (root / "vae" / "config.json").exists():             # diffusers AutoencoderKL config
                 c = json.loads((root / "vae" / "config.json").read_text())
                 vcfg.update(ch=tuple(c["block_out_channels"]), groups=c["norm_num_groups"], scaling_factor=c["scaling_factor"], shift_factor=c["shift_factor"])
-            dit = FluxDiTHip(_ShardedProvider(root / "transformer", dit_param_shapes(dcfg), self.device), dcfg, self.device)
+            # flux_kontext_fp8: the reference serves this model from SDNQ uint4 / nunchaku int4 weights (:209-233, :1084-1252); e4m3 weights with one
+            # E8M0 scale per 32 k are the low-precision route here, off by default
+            dit = FluxDiTHip(_ShardedProvider(root / "transformer", dit_param_shapes(dcfg), self.device), dcfg, self.device, fp8=self.flux_kontext_fp8)
             vae = FluxVAEHip(_ShardedProvider(root / "vae", vae_param_shapes(vcfg), self.device), vcfg, self.device)
             pipe = FluxKontextHip(dit, vae)
             emb = root / "prompt_embeds.safetensors"
@@ -754,7 +758,7 @@ class ModelManager:
                 e = self._read_safetensors(emb)
                 pipe.set_prompt_embeds(e["prompt_embeds"], e["pooled_prompt_embeds"])
             self.models[mt] = pipe
-            log_message("Flux Kontext pipeline loaded (libmtx_hip graphs, bf16).", verbose=verbose)
+            log_message(f"Flux Kontext pipeline loaded (libmtx_hip graphs, {'fp8 + ' if dit.fp8 else ''}bf16).", verbose=verbose)
             return pipe
 
 

@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void gemm_f32_skinny_kernel(mtx_gemm_args p) {
 
 int gemm_f32_launch(const mtx_gemm_args* a, void* stream, const char** err) {
   if (!a->a || !a->w || !a->c) { *err = "gemm f32: null operand"; return MTX_ERR_INVALID; }
-  if (a->gate || a->glu_q || a->in_dtype == MTX_F8 || (a->out_dtype != MTX_F32 && a->out_dtype != a->dtype)) {
+  if (a->gate || a->glu_q || a->actq_q || a->in_dtype == MTX_F8 || (a->out_dtype != MTX_F32 && a->out_dtype != a->dtype)) {
     *err = "gemm f32: gate / glu / fp8 operands and 16-bit outputs are not part of the fp32 path"; return MTX_ERR_UNSUPPORTED;
   }
   if (a->m < 1 || a->n < 1 || a->batch < 1) return MTX_OK;

@@ -36,6 +36,8 @@ struct GemmParams {
   int bk;           // K elements per LDS stage row: 64 (16-bit operands) or 128 (fp8); a row is 128 bytes either way
   // SwiGLU + MX-fp8 epilogue of the fp8 kernel (mtx_gemm_args.glu_*): columns >= glu_col0 are [32 a | 32 b] spans
   unsigned char* glu_q; unsigned* glu_scale; long glu_ldq, glu_lds, glu_col0;
+  // activation + MX-fp8 epilogue of the fp8 kernel (mtx_gemm_args.actq_*): every column leaves as the e4m3 operand of the next linear
+  unsigned char* actq_q; unsigned* actq_scale; long actq_ldq, actq_lds;
   unsigned strip_w;         // 256-tile kernels: tile columns per strip of the workgroup -> tile map (gemm256_tile_origin); >= tiles_n: one strip
 };
 
@@ -803,6 +805,82 @@ __global__ __launch_bounds__(512) void gemm256_f8_glu_kernel(GemmParams p) {
   }
 }
 
+// The plain-MLP form of the same kernel (mtx_gemm_args.actq_*; FLUX.1-Kontext's Linear -> GELU(tanh) -> Linear): h = round_T(act(alpha * acc +
+// bias)) — the value the whole-tile epilogue would have stored — is quantised in registers and leaves as the MX e4m3 operand of the next linear;
+// the 16-bit [T, 4 D] matrix (216 MB written and read back per MLP at T = 8812) never exists.  A wave owns 64 columns: acc[i][0] and acc[i][1] are
+// two complete MX blocks of row l31, each split over lane and lane ^ 32 like the gated kernel's single span — the same max-exchange and two-dword
+// swap, twice per row.  Arithmetic as in quant.hip on the rounded 16-bit value: bit-identical to GEMM -> quantiser.
+template <typename T, int ACT>
+__global__ __launch_bounds__(512) void gemm256_f8_actq_kernel(GemmParams p) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G2_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const unsigned lin = xcd_remap(blockIdx.x, gridDim.x);
+  long m0, n0;
+  gemm256_tile_origin(p, lin, m0, n0);
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  gemm256_f8_loop(p, smem, p.a, p.w, m0, n0, 0, p.k / 128, acc);
+  const int l31 = lane & 31, hi = lane >> 5, wm = wv >> 2, wn = wv & 3;
+  f32x4 bv[2][4];                                         // N % 256 == 0: every column of the tile exists
+  if (p.bias != nullptr && ((size_t)p.bias & 15) == 0) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) bv[j][g] = *reinterpret_cast<const f32x4*>(p.bias + n0 + wn * 64 + j * 32 + g * 8 + hi * 4);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bv[j][g][r] = p.bias != nullptr ? p.bias[n0 + wn * 64 + j * 32 + g * 8 + hi * 4 + r] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long m = m0 + wm * 128 + i * 32 + l31;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const long span = n0 / 32 + wn * 2 + j;             // 32 outputs: columns 32 * span .. of the quantised matrix
+      float h[16];
+      float amax = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        h[e] = to_f32(from_f32<T>(apply_act_t<ACT>(acc[i][j][e] * p.alpha + bv[j][e >> 2][e & 3], p.act, p.act_param)));
+        const float v = fabsf(h[e]);
+        amax = v > amax ? v : amax;
+      }
+      { const float o = __shfl_xor(amax, 32, 64); amax = o > amax ? o : amax; }
+      const float r = amax * (1.0f / 448.0f);
+      const unsigned u = __builtin_bit_cast(unsigned, r);
+      int eb = (int)((u >> 23) & 0xff) + ((u & 0x7fffffu) ? 1 : 0);
+      eb = amax == 0.f ? 127 : (eb < 1 ? 1 : (eb > 253 ? 253 : eb));
+      const float inv = __builtin_bit_cast(float, (unsigned)(254 - eb) << 23);
+      unsigned w[4];                                       // w[g]: outputs 8 g + 4 hi + 0..3 of the span
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        float q4[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { float v = h[g * 4 + e] * inv; q4[e] = v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
+        w[g] = 0;
+        w[g] = cvt_pk_fp8<false>(q4[0], q4[1], w[g]); w[g] = cvt_pk_fp8<true>(q4[2], q4[3], w[g]);
+      }
+      // lane (hi = 0) keeps bytes 0..15 of the span (g = 0, 1), lane ^ 32 bytes 16..31 (g = 2, 3): swap the two dwords the other needs
+      const unsigned s0 = hi ? w[0] : w[2], s1 = hi ? w[1] : w[3];
+      const unsigned r0 = (unsigned)__shfl_xor((int)s0, 32, 64), r1 = (unsigned)__shfl_xor((int)s1, 32, 64);
+      const u32x4 out = hi ? u32x4{r0, w[2], r1, w[3]} : u32x4{w[0], r0, w[1], r1};
+      if (m < p.m) {
+        *reinterpret_cast<u32x4*>(p.actq_q + (size_t)m * p.actq_ldq + span * 32 + hi * 16) = out;
+        if (hi == 0) reinterpret_cast<unsigned char*>(p.actq_scale + (size_t)(span >> 2) * p.actq_lds + m)[span & 3] = (unsigned char)eb;
+      }
+    }
+  }
+}
+
 
 // ---- K-slice tail with a last-arriver fix-up (round 4) ---------------------------------------------------------------------
 // With one 256 x 256 tile per CU at a time, `rem = tiles % CUs` left-over tiles keep rem CUs busy for a whole tile time while the
@@ -1016,9 +1094,10 @@ static bool gemm_fits32(const mtx_gemm_args* a) {
   return ((size_t)G2_BM * a->lda + a->k) * esz < (1ull << 32) && ((size_t)G2_BN * a->ldw + a->k) * esz < (1ull << 32);
 }
 
-// common checks, then the fp8 kernel's, then its SwiGLU epilogue's; fp32 operands (dtype == MTX_F32) are checked by their own launcher
+// common checks, then the fp8 kernel's, then its two quantising epilogues'; fp32 operands (dtype == MTX_F32) are checked by their own launcher
 static int gemm_validate(const mtx_gemm_args* a, const char** err) {
-  if (!a->a || !a->w || !a->c) { *err = "gemm: null operand"; return MTX_ERR_INVALID; }
+  if (!a->a || !a->w || (!a->c && !a->actq_q)) { *err = "gemm: null operand"; return MTX_ERR_INVALID; }      // (the activation + MX-fp8 epilogue writes no c)
+  if (a->actq_q != nullptr && a->in_dtype != MTX_F8) { *err = "gemm: the activation + MX-fp8 epilogue exists on the fp8 kernel only"; return MTX_ERR_INVALID; }
   if (a->m < 1 || a->n < 1 || a->k < 1) { *err = "gemm: empty problem"; return MTX_ERR_INVALID; }
   if (a->dtype == MTX_F32) return MTX_OK;
   const bool f8 = a->in_dtype == MTX_F8, t16 = a->dtype == MTX_BF16 || a->dtype == MTX_F16;
@@ -1041,6 +1120,11 @@ static int gemm_validate(const mtx_gemm_args* a, const char** err) {
       (!a->glu_scale || a->glu_col0 < 0 || a->glu_col0 % G2_BN || a->glu_col0 >= a->n || (a->n - a->glu_col0) % G2_BN || a->glu_ldq % 16 ||
        ((size_t)a->glu_q & 15) || a->glu_lds < a->m || a->bias || a->gate || a->res || a->act != MTX_ACT_NONE)) {
     *err = "gemm(fp8, SwiGLU epilogue): needs glu_col0 and n - glu_col0 multiples of 256, glu_ldq % 16 == 0, glu_lds >= m, and no bias / gate / res / act";
+    return MTX_ERR_INVALID;
+  }
+  if (a->actq_q != nullptr &&
+      (!a->actq_scale || a->n % G2_BN || a->gate || a->res || a->glu_q || ((size_t)a->actq_q & 15) || a->actq_ldq % 16 || a->actq_ldq < a->n || a->actq_lds < a->m)) {
+    *err = "gemm(fp8, activation + MX-fp8 epilogue): needs n % 256 == 0, no gate / res / glu_q, actq_q 16-byte aligned with actq_ldq % 16 == 0 and >= n, actq_lds >= m";
     return MTX_ERR_INVALID;
   }
   return MTX_OK;
@@ -1071,15 +1155,20 @@ static GemmParams gemm_params(const mtx_gemm_args* a) {
     p.glu_q = reinterpret_cast<unsigned char*>(a->glu_q); p.glu_scale = reinterpret_cast<unsigned*>(a->glu_scale);
     p.glu_ldq = a->glu_ldq; p.glu_lds = a->glu_lds; p.glu_col0 = a->glu_col0;
   }
+  if (a->actq_q != nullptr) {
+    p.actq_q = reinterpret_cast<unsigned char*>(a->actq_q); p.actq_scale = reinterpret_cast<unsigned*>(a->actq_scale);
+    p.actq_ldq = a->actq_ldq; p.actq_lds = a->actq_lds;
+  }
   p.strip_w = 0x7fffffffu;                                     // one strip; the 256-tile routes choose (gemm256_choose_strip)
   return p;
 }
 
-enum class GemmRoute { Tile128, Tile128Pair, Tile256, Tile256F8, Tile256F8Glu };
+enum class GemmRoute { Tile128, Tile128Pair, Tile256, Tile256F8, Tile256F8Glu, Tile256F8ActQ };
 
 // Which kernel family runs a validated problem on a device of `cus` compute units.  (How a 256-tile launch splits its tail: launch_gemm256.)
 static GemmRoute gemm_route(const mtx_gemm_args* a, int cus) {
-  if (a->in_dtype == MTX_F8) return a->glu_q != nullptr ? GemmRoute::Tile256F8Glu : GemmRoute::Tile256F8;      // fp8 exists as 256 tiles only
+  if (a->in_dtype == MTX_F8)                                   // fp8 exists as 256 tiles only; the quantising epilogues as whole tiles only
+    return a->glu_q != nullptr ? GemmRoute::Tile256F8Glu : (a->actq_q != nullptr ? GemmRoute::Tile256F8ActQ : GemmRoute::Tile256F8);
   // large, aligned problems: the 256 x 256 LDS-DMA kernel (needs whole K tiles and 16-byte rows everywhere)
   const bool can256 = !gemm_out_f32(a) && a->w_lo == nullptr && a->k % G2_BK == 0 && gemm_rows_vec(a) && gemm_fits32(a);
   // with the descriptor-DMA loop the 256-tile kernel wins from ~24 tiles up even though most CUs idle (512x9216x3072: 55 vs 68 us,
@@ -1104,7 +1193,7 @@ int gemm_launch(const mtx_gemm_args* a, void* stream, const char** err) {
   const bool big = route != GemmRoute::Tile128 && route != GemmRoute::Tile128Pair;
   const long bm = big ? G2_BM : GBM, bn = big ? G2_BN : GBN;
   p.tiles_m = (unsigned)((a->m + bm - 1) / bm); p.tiles_n = (unsigned)((a->n + bn - 1) / bn);
-  if (route == GemmRoute::Tile256F8Glu) p.strip_w = gemm256_choose_strip(p.tiles_n, true);
+  if (route == GemmRoute::Tile256F8Glu || route == GemmRoute::Tile256F8ActQ) p.strip_w = gemm256_choose_strip(p.tiles_n, true);
   const dim3 grid(p.tiles_m * p.tiles_n, (unsigned)gemm_batch(a));
   with_storage_type(a->dtype, [&](auto t) {
     typedef typename decltype(t)::type T;
@@ -1114,6 +1203,9 @@ int gemm_launch(const mtx_gemm_args* a, void* stream, const char** err) {
       case GemmRoute::Tile256: launch_gemm256<T, false>(p, grid, stream, a->flags); break;
       case GemmRoute::Tile256F8: launch_gemm256<T, true>(p, grid, stream, a->flags); break;
       case GemmRoute::Tile256F8Glu: MTX_LAUNCH((gemm256_f8_glu_kernel<T>), grid, dim3(512), 0, stream, p); break;
+      case GemmRoute::Tile256F8ActQ:
+        with_gemm256_act(p.act, [&](auto act) { MTX_LAUNCH((gemm256_f8_actq_kernel<T, decltype(act)::value>), grid, dim3(512), 0, stream, p); });
+        break;
     }
   });
   return MTX_OK;

@@ -2,7 +2,7 @@
 mtx_abi_sizeof() when the library is opened)."""
 import ctypes as C
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # enums
 BF16, F16, F32, U8, I32, F8 = 0, 1, 2, 3, 4, 5
@@ -48,7 +48,8 @@ class GemmArgs(C.Structure):
                 ("dtype", i32), ("out_dtype", i32), ("workspace", vp), ("workspace_bytes", i64),
                 ("a_scale", vp), ("w_scale", vp), ("lds_a", i64), ("lds_w", i64), ("in_dtype", i32), ("flags", i32),
                 ("glu_q", vp), ("glu_scale", vp), ("glu_ldq", i64), ("glu_lds", i64), ("glu_col0", i64),
-                ("w_lo", vp), ("res_dtype", i32)]
+                ("w_lo", vp), ("res_dtype", i32),
+                ("actq_q", vp), ("actq_scale", vp), ("actq_ldq", i64), ("actq_lds", i64)]
 
 
 GEMM_FORCE_TILE256, GEMM_NO_SPLIT = 1, 2

@@ -308,16 +308,23 @@ class PlanBuilder:
     def gemm(self, a_t, w_t, m, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE,
              res=None, ldres=None, gate=None, ldgate=None, gate_rows_per=1, alpha=1.0, batch=1,
              a_bs=0, w_bs=0, c_bs=0, res_bs=0, out_f32=False, a_off=0, w_off=0, c_off=0, res_off=0,
-             label="gemm", f8=None, flags=0, glu=None, w_lo=None, res_f32=False):
+             label="gemm", f8=None, flags=0, glu=None, w_lo=None, res_f32=False, actq=None):
         """w_lo: the low half of a weight pair W = w_t + w_lo (same layout as w_t; mtx_gemm_args.w_lo).  res_f32: `res` is an fp32 matrix
         (needs out_f32; the fp32 residual stream of SAM's precision "high").
         f8 = (a_scale, lds_a, w_scale, lds_w, a_scale_off, w_scale_off): a_t / w_t are e4m3 byte matrices from `quantize` (offsets in
         bytes), the epilogue operands and the output stay in the builder's 16-bit type (include/mtx_hip.h, in_dtype == MTX_F8).
         glu = (q, scale, ldq, lds, col0, row_off, q_col_off): the columns from col0 on are [32 a | 32 b] spans (`glu_interleave` order of
         w's rows) and land as the MX fp8 matrix silu(a) * b in rows [row_off, row_off + m) of q / scale from byte column q_col_off on
-        (mtx_gemm_args.glu_*); with col0 == 0 no 16-bit output exists at all"""
+        (mtx_gemm_args.glu_*); with col0 == 0 no 16-bit output exists at all
+        actq = (q, scale, ldq, lds, row_off, q_col_off): act(alpha * acc + bias) of EVERY column lands as an MX fp8 matrix in rows
+        [row_off, row_off + m) of q / scale from byte column q_col_off on (mtx_gemm_args.actq_*); no 16-bit `out` is needed or written"""
         g = abi.GemmArgs()
         g.flags = flags
+        if actq is not None:
+            aq, asc, aldq, alds, arow, aqcol = actq
+            assert f8 is not None and glu is None and out is None and aqcol % 128 == 0
+            g.actq_q, g.actq_scale = aq.data_ptr() + arow * aldq + aqcol, asc.data_ptr() + 4 * (arow + (aqcol // 128) * alds)
+            g.actq_ldq, g.actq_lds = aldq, alds
         if glu is not None:
             gq, gsc, gldq, glds, gcol0, grow, gqcol = glu
             assert f8 is not None and gqcol % 128 == 0 and gcol0 % 256 == 0
@@ -329,9 +336,9 @@ class PlanBuilder:
             a_sc, lds_a, w_sc, lds_w, a_sc_off, w_sc_off = f8
             g.a_scale, g.w_scale = a_sc.data_ptr() + 4 * a_sc_off, w_sc.data_ptr() + 4 * w_sc_off
             g.lds_a, g.lds_w, g.in_dtype = lds_a, lds_w, abi.F8
-        if out is None:
+        if out is None and actq is None:
             out = self.buf((batch, m, n) if batch > 1 else (m, n), torch.float32 if out_f32 else self.tdtype)
-        g.a, g.w, g.c = _ptr(a_t, a_off), _ptr(w_t, w_off), _ptr(out, c_off)
+        g.a, g.w, g.c = _ptr(a_t, a_off), _ptr(w_t, w_off), (_ptr(out, c_off) if out is not None else None)
         g.bias, g.res, g.gate = _ptr(bias), _ptr(res, res_off), _ptr(gate)
         g.m, g.n, g.k = m, n, k
         g.lda, g.ldw, g.ldc = (lda or k), (ldw or k), (ldc or n)

@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] ..."""
 import os
 import sys
 
@@ -117,6 +117,108 @@ def gemm8_glu(M, hid, K, col0=0, iters=20, fused=True):
         pb.quantize(c, M, hid, ldx=N, x_off=col0, q=q8, scale=sc, lds=lds, ldq=hid, swiglu_b=c, b_off=col0 + hid, ldb=N)
     ms = _time(pb.build(), iters)
     print(f"gemm8 + SwiGLU -> MX fp8 M={M} N={N} K={K} [{'gated epilogue' if fused else 'GEMM + SwiGLU quantiser launch'}]: {ms:.3f} ms  {2 * M * N * K / ms / 1e9:.0f} TFLOP/s", flush=True)
+
+
+def gemm8_actq(M, N, K, iters=20, fused=True, plan_only=False):
+    """FLUX.1-Kontext MLP-in: fp8 GEMM + bias + tanh-GELU whose result leaves as the MX fp8 operand of the next linear (fused: mtx_gemm_args.actq_*;
+    else GEMM into 16 bits + quantiser launch)"""
+    pb = PlanBuilder(lib, dev, abi.BF16)
+    g = torch.Generator(device=dev).manual_seed(5)
+    a = pb.buf((M, K), torch.bfloat16); a.normal_(generator=g)
+    w = pb.buf((N, K), torch.bfloat16); w.normal_(0, K ** -0.5, generator=g)
+    bias = pb.buf((N,), torch.float32); bias.normal_(generator=g)
+    q = PlanBuilder(lib, dev, abi.BF16)
+    aq, asc, la = q.quantize(a, M, K)
+    wq, wsc, lw = q.quantize(w, N, K)
+    q.build().run(); torch.cuda.synchronize()
+    pb.keep += [aq, asc, wq, wsc]
+    lds = (M + 63) // 64 * 64
+    q8 = pb.buf((M, N), torch.uint8, zero=True)
+    sc = pb.buf((N // 128, lds), torch.int32, zero=True)
+    kw = dict(bias=bias, act=abi.ACT_GELU_TANH, f8=(asc, la, wsc, lw, 0, 0))
+    if fused:
+        pb.gemm(aq, wq, M, N, K, actq=(q8, sc, N, lds, 0, 0), **kw)
+    else:
+        c = pb.gemm(aq, wq, M, N, K, **kw)
+        pb.quantize(c, M, N, q=q8, scale=sc, lds=lds, ldq=N)
+    plan = pb.build()
+    plan.q8, plan.sc = q8, sc
+    if plan_only:
+        return plan
+    ms = _time(plan, iters)
+    print(f"gemm8 + bias + tanh-GELU -> MX fp8 M={M} N={N} K={K} [{'activation epilogue' if fused else 'GEMM + quantiser launch'}]: {ms:.3f} ms  {2 * M * N * K / ms / 1e9:.0f} TFLOP/s", flush=True)
+    return ms
+
+
+def gemm8_actq_ab(M, N, K, reps=3, iters=20):
+    """fused against unfused, alternating in one process; the operand bytes must be the same when the unfused GEMM runs whole tiles"""
+    plans = {f: gemm8_actq(M, N, K, fused=f, plan_only=True) for f in (True, False)}
+    best = {}
+    for _ in range(reps):
+        for f, plan in plans.items():
+            best[f] = min(best.get(f, 1e9), _time(plan, iters))
+    same = torch.equal(plans[True].q8, plans[False].q8) and torch.equal(plans[True].sc, plans[False].sc)
+    split = lib.gemm_last_split()
+    print(f"gemm8 + bias + tanh-GELU -> MX fp8 M={M} N={N} K={K}: activation epilogue {best[True]:.4f} ms ({2 * M * N * K / best[True] / 1e9:.0f} TF), "
+          f"GEMM + quantiser launch {best[False]:.4f} ms ({2 * M * N * K / best[False] / 1e9:.0f} TF); same bytes: {same} "
+          f"(the unfused GEMM's whole tiles, K slices, pieces = {split})", flush=True)
+
+
+def _kontext_dits(layers, singles, modes, seed=11):
+    from mangatranslator_amd.core.ml import flux as fx
+    cfg = dict(fx.KONTEXT_DIT_CFG, layers=layers, single_layers=singles)
+    shapes = fx.dit_param_shapes(cfg)
+    # the same seeded weights for every mode: the provider is re-created per graph (it draws tensor by tensor from one generator, in load order)
+    return cfg, {m: fx.FluxDiTHip(fx.synthetic_provider(shapes, dev, seed), cfg, dev, lib=lib, fp8=m) for m in modes}
+
+
+def kontext_step_ab(h2, w2, layers=19, singles=38, t_txt=512, reps=3, iters=3):
+    """One FLUX.1-Kontext denoising step, bf16 against fp8 block linears on the same seeded weights, graph replays alternating in one process;
+    the block linears' share of each (plan.time_ops) and the fp8 linears' rate against the 5 PF MX-fp8 peak"""
+    cfg, dits = _kontext_dits(layers, singles, (False, True))
+    g = torch.Generator(device=dev).manual_seed(3)
+    plans, groups = {}, {}
+    for m, dit in dits.items():
+        plan = dit.plan_for(t_txt, h2, w2, 1)
+        plan.ctx_in.normal_(generator=g); plan.lat.normal_(generator=g)
+        plan.mod.copy_(dit.modulation(0.7, 2.5, torch.zeros(cfg["pooled_dim"], device=dev, dtype=torch.bfloat16)))
+        plans[m] = plan
+        groups[m] = [i for i, (lb, o) in enumerate(zip(plan.labels, plan.ops)) if o.kind == abi.OP_GEMM and lb.startswith(("dbl", "sgl"))]
+    step, gemms = {}, {}
+    for _ in range(reps):
+        for m, plan in plans.items():
+            plan.run(graph=True); torch.cuda.synchronize()
+            step[m] = min(step.get(m, 1e9), plan.time(iters, graph=True))
+            gemms[m] = min(gemms.get(m, 1e9), plan.time_ops(groups[m], iters) / iters)
+    fl = dits[True].flops_per_step(t_txt, h2, w2, 1)["gemm"]
+    nq = sum(1 for o in plans[True].ops if o.kind == abi.OP_QUANT)
+    print(f"Kontext step {layers}+{singles} blocks T={plans[True].T}: bf16 {step[False]:.2f} ms (block linears {gemms[False]:.2f} ms, {fl / gemms[False] / 1e9:.0f} TF), "
+          f"fp8 {step[True]:.2f} ms (block linears {gemms[True]:.2f} ms, {fl / gemms[True] / 1e9:.0f} TF = {fl / gemms[True] / 1e9 / 5000:.2f} of the 5 PF fp8 peak); "
+          f"quantiser launches left in the fp8 step: {nq}", flush=True)
+
+
+def kontext_psnr(h, w, layers=4, singles=8, steps=4, t_txt=512):
+    """4-step image PSNR of the fp8 Kontext pipeline against the bf16 one on the same seeded full-width weights (reduced depth)"""
+    import math
+    import numpy as np
+    from mangatranslator_amd.core.ml import flux as fx
+    cfg, dits = _kontext_dits(layers, singles, (False, True))
+    vshapes = fx.vae_param_shapes(fx.KONTEXT_VAE_CFG)
+    g = torch.Generator().manual_seed(1)
+    img = (torch.rand(h, w, 3, generator=g) * 255).to(torch.uint8).numpy()
+    pe = torch.randn(t_txt, cfg["joint_dim"], generator=g)
+    pooled = torch.randn(cfg["pooled_dim"], generator=g)
+    noise = torch.randn(1, 16, h // 8, w // 8, generator=g)
+    outs = {}
+    for m, dit in dits.items():
+        vae = fx.FluxVAEHip(fx.synthetic_provider(vshapes, dev, 12), dict(fx.KONTEXT_VAE_CFG), dev, lib=lib)
+        pipe = fx.FluxKontextHip(dit, vae)
+        outs[m] = pipe(image=img, width=w, height=h, num_inference_steps=steps, guidance_scale=2.5, prompt_embeds=pe[None],
+                       pooled_prompt_embeds=pooled[None], latents=noise).images[0].float().cpu()
+    mse = ((outs[True] - outs[False]) ** 2).mean().item()
+    T = t_txt + 2 * (h // 16) * (w // 16)
+    print(f"Kontext {steps} steps {w}x{h} (T={T}, {layers}+{singles} blocks, d=3072, seeded weights): fp8 block linears vs bf16 image PSNR "
+          f"{99.0 if mse == 0 else 10 * math.log10(1.0 / mse):.1f} dB", flush=True)
 
 
 def gemm(M, N, K, iters=20, f8=False, pad=0, flags=0, act=0):
@@ -258,6 +360,16 @@ if __name__ == "__main__":
             attn_q8(int(args[1]), fused=args[0] != "attnqs"); args = args[2:]
         elif args[0] in ("glu", "glus"):              # glu M hid K col0
             gemm8_glu(int(args[1]), int(args[2]), int(args[3]), int(args[4]), fused=args[0] == "glu"); args = args[5:]
+        elif args[0] in ("actq", "actqs", "actqab"):  # actq M N K: fp8 GEMM + bias + GELU -> MX fp8: fused epilogue / separate quantiser / both, alternating
+            if args[0] == "actqab":
+                gemm8_actq_ab(int(args[1]), int(args[2]), int(args[3]))
+            else:
+                gemm8_actq(int(args[1]), int(args[2]), int(args[3]), fused=args[0] == "actq")
+            args = args[4:]
+        elif args[0] == "kontext":                    # kontext H2 W2 LAYERS SINGLES: one step, bf16 against fp8 block linears
+            kontext_step_ab(int(args[1]), int(args[2]), int(args[3]), int(args[4])); args = args[5:]
+        elif args[0] == "kontextpsnr":                # kontextpsnr H W LAYERS SINGLES: 4-step image PSNR, fp8 against bf16
+            kontext_psnr(int(args[1]), int(args[2]), int(args[3]), int(args[4])); args = args[5:]
         elif args[0] in ("norm", "normq"):              # norm ROWS C: every norm kernel form in turn
             norm(int(args[1]), int(args[2]), q8=args[0] == "normq"); args = args[3:]
         elif args[0] == "quant":

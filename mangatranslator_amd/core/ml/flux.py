@@ -22,6 +22,9 @@ Graph design (MI355X-first):
   * fp8 (`FluxDiTHip(fp8=True)`, opt-in): the block linears run on the MX-scaled fp8 matrix instructions (gemm.hip gemm256_f8_kernel) from
     weights quantised once at load; the adaLN norms, the joint attention and the MLP-in GEMMs (bias + GELU-tanh + quantisation in the epilogue,
     mtx_gemm_args.actq_*) write the next linear's e4m3 operand themselves into fp8 twins of the buffers above.  Everything else stays bf16 / fp32.
+  * the ops a block is wired from (linear, adaLN norm, norm + RoPE, joint attention, quantiser pass), the weight holder and the modulation cache
+    are core/ml/dit_graph.py's, shared with FLUX.2-Klein; this file keeps the parameter names, the block wiring, the side lane, the MLP-in
+    epilogue and the decisions about who writes which fp8 operand.
   * VAE: NHWC 3x3 convs with fused bias / residual, GroupNorm+SiLU kernels, nearest-2x fused into a copy,
     Downsample2D's asymmetric pad as a conv mode; the single-head mid-block attention (d = 512) runs as
     GEMM -> row softmax -> GEMM.
@@ -37,12 +40,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, PlanBuilder, PlanCache, residual_distance
 from ...utils.exceptions import ModelError
-
-
-def _rows(t2d, r0, r1, c0=0, c=None):
-    """Act view of rows [r0, r1) and columns [c0, c0+c) of a [R, LD] buffer."""
-    v = t2d[r0:r1]
-    return Act(v.view(1, 1, r1 - r0, t2d.shape[1]), 1, 1, r1 - r0, c if c is not None else t2d.shape[1] - c0, c0)
+from .dit_graph import DiTStep, ModulationCache, Weight, _rows, quantize_weight
 
 
 def sinusoid(value: float, dim=256) -> np.ndarray:
@@ -81,13 +79,6 @@ def image_ids(h2, w2, first) -> np.ndarray:
 
 
 FP8_ALL = ("qkv", "to_out", "ff1", "ff2", "proj_mlp", "proj_out")      # the block linears by kind (both streams of a double block share a kind)
-
-
-class _W8:
-    """MX fp8 copy of one linear's weight: e4m3 bytes [N, K] + E8M0 scale plane (the 16-bit tensor it replaces is dropped)"""
-
-    def __init__(self, q, scale, lds):
-        self.q, self.scale, self.lds = q, scale, lds
 
 
 class FluxDiTHip:
@@ -139,9 +130,9 @@ class FluxDiTHip:
         W["mods"] = (torch.cat(mods_w, 0).contiguous(), torch.cat(mods_b, 0).contiguous())
         self.n_vec = W["mods"][0].shape[0] // D
         self.blocks, self.singles = [], []
-        cat3 = lambda p, names, kind="qkv": (self._weight(torch.cat([g(f"{p}.{n}.weight") for n in names], 0).contiguous(), kind),
-                                             torch.cat([g(f"{p}.{n}.bias", f32) for n in names], 0).contiguous())
-        lin = lambda name, kind: (self._weight(g(name + ".weight"), kind), g(name + ".bias", f32))
+        cat3 = lambda p, names, kind="qkv": self._weight(torch.cat([g(f"{p}.{n}.weight") for n in names], 0).contiguous(), kind,
+                                                         torch.cat([g(f"{p}.{n}.bias", f32) for n in names], 0).contiguous())
+        lin = lambda name, kind: self._weight(g(name + ".weight"), kind, g(name + ".bias", f32))
         for i in range(cfg["layers"]):
             p = f"transformer_blocks.{i}"
             self.blocks.append(dict(
@@ -158,20 +149,11 @@ class FluxDiTHip:
                                      mlp=lin(p + ".proj_mlp", "proj_mlp"), out=lin(p + ".proj_out", "proj_out")))
         self.W = W
         self._plans = PlanCache(6)           # a DiT plan pins ~T x 15 D bytes of activations: a few crop resolutions only
-        self._mod_plan = None
-        self._mod_cache = {}
+        self._mods = ModulationCache(self._build_mod_plan, self.n_vec)
 
-    def _weight(self, w16: torch.Tensor, kind: str):
-        """the 16-bit weight, or — for a kind on the fp8 path — its MX fp8 copy"""
-        if kind not in self.fp8:
-            return w16
-        n, k = w16.shape
-        pb = PlanBuilder(self.lib, self.device, self.dtype)
-        q, scale, lds = pb.quantize(w16, n, k)
-        pb.build().run()
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        return _W8(q, scale, lds)
+    def _weight(self, w16: torch.Tensor, kind: str, bias) -> Weight:
+        """one block linear: the 16-bit weight, or — for a kind on the fp8 path — its MX fp8 copy"""
+        return quantize_weight(self.lib, self.device, self.dtype, w16, bias) if kind in self.fp8 else Weight(w16, bias=bias)
 
     # ---- modulation vectors of one (timestep, guidance, pooled) ------------------------------------------
     def _build_mod_plan(self):
@@ -198,18 +180,12 @@ class FluxDiTHip:
         if pooled_key is None:
             pooled_key = hash(pooled.detach().float().cpu().numpy().tobytes())
         key = (round(float(timestep), 7), round(float(guidance), 5), pooled_key)
-        if len(self._mod_cache) > 256:          # a few schedules x prompts at most; never grow without bound
-            self._mod_cache.clear()
-        if key not in self._mod_cache:
-            if self._mod_plan is None:
-                self._mod_plan = self._build_mod_plan()
-            mp = self._mod_plan
+
+        def fill(mp):
             tin = np.stack([sinusoid(timestep * 1000.0), sinusoid(guidance * 1000.0)])
             mp.tin.copy_(torch.from_numpy(tin).to(self.device, self.tdt))
             mp.pooled.copy_(pooled.reshape(1, -1).to(self.device, self.tdt))
-            mp.run()
-            self._mod_cache[key] = mp.mods.view(self.n_vec, self.cfg["d"]).clone()
-        return self._mod_cache[key]
+        return self._mods.get(key, fill)
 
     # ---- one denoising step as a plan ----------------------------------------------------------------------
     def _build(self, t_txt, h2, w2, n_ref, cached: bool = False):
@@ -218,7 +194,7 @@ class FluxDiTHip:
         residual-distance probe), `body` (this step's first residual kept, blocks 1.., the whole-stack residual kept, output layers) and
         `skip` (cached whole-stack residual added, output layers) — so that the host can choose between `body` and `skip` after `head`."""
         cfg, W = self.cfg, self.W
-        D, H, hd = cfg["d"], cfg["heads"], self.hd
+        D, H = cfg["d"], cfg["heads"]
         t_noise = h2 * w2
         t_img = t_noise * (1 + n_ref)
         T = t_txt + t_img
@@ -226,88 +202,34 @@ class FluxDiTHip:
         pb = new_pb()
         lat = pb.buf((t_img, cfg["in_channels"]), self.tdt)       # [noise tokens ; reference tokens]
         ctx_in = pb.buf((t_txt, cfg["joint_dim"]), self.tdt)      # prompt embeddings
-        mod = pb.buf((self.n_vec, D), self.tdt)
         ids = np.concatenate([np.zeros((t_txt, 3), np.float32)] + [image_ids(h2, w2, k) for k in range(1 + n_ref)])
-        # rotary tables [2][T, 2, hd/2]: plain (k heads) and pre-multiplied by softmax scale * log2(e) (q heads), so q leaves the
-        # norm+rope kernel as base-2 logit factors after its ONE rounding and the attention kernel spends no VALU slot on scaling
-        tab = torch.from_numpy(rope_table(ids, cfg["axes_dim"]))
-        q_fold = (1.0 / math.sqrt(hd)) * 1.4426950408889634
-        cs2 = pb.hold(torch.stack([tab, tab * q_fold]).to(self.device).contiguous())
-        cs = cs2[0]
-        x = pb.buf((T, D), self.tdt)
-        nrm = pb.buf((T, D), self.tdt)
+        g = DiTStep(pb, T, D, H, self.n_vec, torch.from_numpy(rope_table(ids, cfg["axes_dim"])), bool(self.fp8), self.fused_quant)
+        x, nrm, nrm8, mod, lds = g.x, g.nrm, g.nrm8, g.mod, g.lds
         qkv = pb.buf((T, 3 * D), self.tdt)
         o = pb.buf((T, D), self.tdt)
         hid = pb.buf((T, 4 * D), self.tdt)
         cat = pb.buf((T, 5 * D), self.tdt)
         vel = pb.buf((t_noise, cfg["in_channels"]), torch.float32)
-        m_ = lambda idx: (mod, idx * D)       # (tensor, element offset) of one modulation row
+        o8, hid8, cat8 = g.twin(pb, D), g.twin(pb, 4 * D), g.twin(pb, 5 * D)      # fp8 twins of the GEMM inputs (nrm8 is the recorder's)
         on = lambda *kinds: all(k in self.fp8 for k in kinds)
-        is8 = lambda wb: isinstance(wb[0], _W8)
-        lds = (T + 63) // 64 * 64
-        if self.fp8:      # fp8 twins of the GEMM inputs: e4m3 bytes + scale plane
-            twin = lambda k: (pb.buf((T, k), torch.uint8), pb.buf((k // 128, lds), torch.int32, zero=True))
-            nrm8, o8, hid8, cat8 = twin(D), twin(D), twin(4 * D), twin(5 * D)
-        else:
-            nrm8 = o8 = hid8 = cat8 = None
         ep_ff, ep_mlp = self.act_epilogue and on("ff1", "ff2"), self.act_epilogue and on("proj_mlp", "proj_out")      # who writes hid8 / cat8[:, D:]
         aq8_dbl, aq8_sgl = self.attn_q8 and T >= 1024 and on("to_out"), self.attn_q8 and T >= 1024 and on("proj_out")  # who writes o8 / cat8[:, :D]
-
-        def quant(pb, src, k, dst, r0, r1, label):
-            pb.quantize(src, r1 - r0, k, x_off=r0 * k, q=dst[0], scale=dst[1], row_off=r0, lds=lds, label=label)
-
-        def linear(pb, src, src8, wb, r0, r1, n, k, out, ldc=None, c_col=0, label="linear", actq=None, **epi):
-            """out[r0:r1, c_col : c_col + n] = epilogue(src[r0:r1, :k] W^T + bias) on the 16-bit or the fp8 kernel, as the weight says; with actq
-            (fp8 only) the result leaves as the MX fp8 operand of the next linear and `out` is not written"""
-            w, bias = wb
-            m, ldc = r1 - r0, (ldc or n)
-            if isinstance(w, _W8):
-                pb.gemm(src8[0], w.q, m, n, k, out=None if actq is not None else out, ldc=ldc, a_off=r0 * k, c_off=r0 * ldc + c_col, bias=bias,
-                        f8=(src8[1], lds, w.scale, w.lds, r0, 0), label=label + ".f8", actq=actq, **epi)
-            else:
-                pb.gemm(src, w, m, n, k, out=out, ldc=ldc, a_off=r0 * k, c_off=r0 * ldc + c_col, bias=bias, label=label, **epi)
 
         def embed(pb):
             pb.gemm(ctx_in, W["context_embedder"][0], t_txt, D, cfg["joint_dim"], bias=W["context_embedder"][1], out=x, label="context_embedder")
             pb.gemm(lat, W["x_embedder"][0], t_img, D, cfg["in_channels"], bias=W["x_embedder"][1], out=x, c_off=t_txt * D, label="x_embedder")
 
-        def adaln(pb, r0, r1, shift_i, scale_i, label, consumers=()):
-            """adaLN LayerNorm of rows [r0, r1).  With fp8 consumers the kernel writes their MX fp8 operand itself (mtx_norm_args.q: bit-identical
-            to a quantiser pass over its 16-bit output, which is then only written if some consumer still reads 16-bit)"""
-            any8 = any(is8(wb) for wb in consumers)
-            to8 = any8 and self.fused_quant
-            need16 = not to8 or any(not is8(wb) for wb in consumers)
-            pb.norm(x, nrm if need16 else None, r1 - r0, D, eps=1e-6, kind=0, mod_scale=mod[scale_i], mod_shift=mod[shift_i], rows_per=r1 - r0, ldmod=D,
-                    x_off=r0 * D, y_off=r0 * D, label=label, q8=nrm8 if to8 else None, q_row_off=r0, lds_q=lds)
-            if any8 and not to8:
-                quant(pb, nrm, D, nrm8, r0, r1, label + ".q")
-
-        def rope(pb, buf, r0, r1, gamma_qk, ld, label):
-            """per-head RMSNorm + RoPE over the q AND k column slices (2D columns) of rows [r0, r1) in one launch"""
-            v = _rows(buf, r0, r1, 0, 2 * D)
-            e = abi.EwArgs()
-            e.a, e.b, e.s, e.y = v.ptr, cs[r0:].data_ptr(), gamma_qk.data_ptr(), v.ptr
-            e.n, e.h, e.w, e.c = 1, 1, r1 - r0, 2 * D
-            e.lda, e.ldb, e.ldy, e.lds = ld, T * hd, ld, 0
-            e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_NORM_ROPE, 0, 1e-6, hd, H, self.dtype
-            pb._add(abi.OP_EW, e, label)
-
-        def attention(pb, out_t, out_ld, label, q8=None):
-            """q8: the rows leave as the MX fp8 operand of the projection that follows (mtx_attn_args.q8) and out_t is not written"""
-            pb.attention(qkv, qkv, qkv, None if q8 is not None else out_t, 1, H, T, T, hd, (0, 3 * D, hd), (0, 3 * D, hd), (0, 3 * D, hd), (0, out_ld, hd),
-                         1.0 / math.sqrt(hd), k_off=D, v_off=2 * D, label=label, q_prescaled=True, q8=q8)
-
-        def mlp_in(pb, wb, r0, r1, out, ldc, c_col, dst8, fused, consumer, label):
+        def mlp_in(pb, w, r0, r1, out, c_col, dst8, fused, consumer, label):
             """Linear + bias + GELU(tanh) of rows [r0, r1) of nrm into out[:, c_col : c_col + 4 D].  An fp8 consumer reads the twin dst8 instead: written by
             this GEMM's epilogue (fused: no 16-bit result exists) or by a quantiser launch behind it"""
+            ldc = out.shape[1]
             if fused:
-                linear(pb, nrm, nrm8, wb, r0, r1, 4 * D, D, None, ldc=ldc, c_col=c_col, act=abi.ACT_GELU_TANH, label=label,
-                       actq=(dst8[0], dst8[1], ldc, lds, r0, c_col))
+                g.linear(pb, nrm, nrm8, w, r0, r1, 4 * D, D, None, ldc=ldc, c_col=c_col, act=abi.ACT_GELU_TANH, label=label,
+                         actq=(dst8[0], dst8[1], ldc, lds, r0, c_col))
                 return
-            linear(pb, nrm, nrm8, wb, r0, r1, 4 * D, D, out, ldc=ldc, c_col=c_col, act=abi.ACT_GELU_TANH, label=label)
-            if is8(consumer):
-                pb.quantize(out, r1 - r0, 4 * D, ldx=ldc, x_off=r0 * ldc + c_col, q=dst8[0], scale=dst8[1], row_off=r0, lds=lds, ldq=ldc, q_col_off=c_col,
-                            label=label + ".q")
+            g.linear(pb, nrm, nrm8, w, r0, r1, 4 * D, D, out, ldc=ldc, c_col=c_col, act=abi.ACT_GELU_TANH, label=label)
+            if consumer.fp8:
+                g.quant(pb, out, ldc, 4 * D, dst8, r0, r1, label + ".q", c0=c_col)
 
         # Double-stream blocks: the text stream's ops (512 rows: GEMMs of 24 - 96 tiles that cannot fill the chip, 4 % of a step when run in
         # line) go to the plan's SIDE lane and run beside the image stream's ops; the lanes meet at the joint attention and at the next block.
@@ -316,39 +238,39 @@ class FluxDiTHip:
             b0 = i * 12
             tag = f"dbl{i}"
             with pb.side():
-                adaln(pb, 0, t_txt, b0 + 6, b0 + 7, tag + ".norm1_ctx", (B["cqkv"],))
-                linear(pb, nrm, nrm8, B["cqkv"], 0, t_txt, 3 * D, D, qkv, label=tag + ".qkv_ctx")
-                rope(pb, qkv, 0, t_txt, B["cnqk"], 3 * D, tag + ".rope_qk_ctx")
-            adaln(pb, t_txt, T, b0 + 0, b0 + 1, tag + ".norm1", (B["qkv"],))
-            linear(pb, nrm, nrm8, B["qkv"], t_txt, T, 3 * D, D, qkv, label=tag + ".qkv")
-            rope(pb, qkv, t_txt, T, B["nqk"], 3 * D, tag + ".rope_qk")
+                g.adaln(pb, 0, t_txt, b0 + 6, b0 + 7, tag + ".norm1_ctx", (B["cqkv"],))
+                g.linear(pb, nrm, nrm8, B["cqkv"], 0, t_txt, 3 * D, D, qkv, label=tag + ".qkv_ctx")
+                g.rope(pb, qkv, 0, t_txt, B["cnqk"], tag + ".rope_qk_ctx")
+            g.adaln(pb, t_txt, T, b0 + 0, b0 + 1, tag + ".norm1", (B["qkv"],))
+            g.linear(pb, nrm, nrm8, B["qkv"], t_txt, T, 3 * D, D, qkv, label=tag + ".qkv")
+            g.rope(pb, qkv, t_txt, T, B["nqk"], tag + ".rope_qk")
             pb.join()
-            attention(pb, o, D, tag + ".attn", q8=(o8[0], o8[1], D, lds, 0) if aq8_dbl else None)
+            g.attention(pb, qkv, o, tag + ".attn", q8=o8 if aq8_dbl else None)
             if on("to_out") and not aq8_dbl:
-                quant(pb, o, D, o8, 0, T, tag + ".attn.q")
+                g.quant(pb, o, D, D, o8, 0, T, tag + ".attn.q")
             with pb.side():
-                linear(pb, o, o8, B["cout"], 0, t_txt, D, D, x, gate=mod[b0 + 8], gate_rows_per=t_txt, res=x, label=tag + ".to_add_out")
-                adaln(pb, 0, t_txt, b0 + 9, b0 + 10, tag + ".norm2_ctx", (B["cff1"],))
-                mlp_in(pb, B["cff1"], 0, t_txt, hid, 4 * D, 0, hid8, ep_ff, B["cff2"], tag + ".ff1_ctx")
-                linear(pb, hid, hid8, B["cff2"], 0, t_txt, D, 4 * D, x, gate=mod[b0 + 11], gate_rows_per=t_txt, res=x, label=tag + ".ff2_ctx")
-            linear(pb, o, o8, B["out"], t_txt, T, D, D, x, gate=mod[b0 + 2], gate_rows_per=t_img, res=x, res_off=t_txt * D, label=tag + ".to_out")
-            adaln(pb, t_txt, T, b0 + 3, b0 + 4, tag + ".norm2", (B["ff1"],))
-            mlp_in(pb, B["ff1"], t_txt, T, hid, 4 * D, 0, hid8, ep_ff, B["ff2"], tag + ".ff1")
-            linear(pb, hid, hid8, B["ff2"], t_txt, T, D, 4 * D, x, gate=mod[b0 + 5], gate_rows_per=t_img, res=x, res_off=t_txt * D, label=tag + ".ff2")
+                g.linear(pb, o, o8, B["cout"], 0, t_txt, D, D, x, gate=mod[b0 + 8], gate_rows_per=t_txt, res=x, label=tag + ".to_add_out")
+                g.adaln(pb, 0, t_txt, b0 + 9, b0 + 10, tag + ".norm2_ctx", (B["cff1"],))
+                mlp_in(pb, B["cff1"], 0, t_txt, hid, 0, hid8, ep_ff, B["cff2"], tag + ".ff1_ctx")
+                g.linear(pb, hid, hid8, B["cff2"], 0, t_txt, D, 4 * D, x, gate=mod[b0 + 11], gate_rows_per=t_txt, res=x, label=tag + ".ff2_ctx")
+            g.linear(pb, o, o8, B["out"], t_txt, T, D, D, x, gate=mod[b0 + 2], gate_rows_per=t_img, res=x, res_off=t_txt * D, label=tag + ".to_out")
+            g.adaln(pb, t_txt, T, b0 + 3, b0 + 4, tag + ".norm2", (B["ff1"],))
+            mlp_in(pb, B["ff1"], t_txt, T, hid, 0, hid8, ep_ff, B["ff2"], tag + ".ff1")
+            g.linear(pb, hid, hid8, B["ff2"], t_txt, T, D, 4 * D, x, gate=mod[b0 + 5], gate_rows_per=t_img, res=x, res_off=t_txt * D, label=tag + ".ff2")
 
         s0 = cfg["layers"] * 12
 
         def single_block(pb, i, S):
             b0 = s0 + i * 3
             tag = f"sgl{i}"
-            adaln(pb, 0, T, b0 + 0, b0 + 1, tag + ".norm", (S["qkv"], S["mlp"]))
-            linear(pb, nrm, nrm8, S["qkv"], 0, T, 3 * D, D, qkv, label=tag + ".qkv")
-            mlp_in(pb, S["mlp"], 0, T, cat, 5 * D, D, cat8, ep_mlp, S["out"], tag + ".proj_mlp")
-            rope(pb, qkv, 0, T, S["nqk"], 3 * D, tag + ".rope_qk")
-            attention(pb, cat, 5 * D, tag + ".attn", q8=(cat8[0], cat8[1], 5 * D, lds, 0) if aq8_sgl else None)
+            g.adaln(pb, 0, T, b0 + 0, b0 + 1, tag + ".norm", (S["qkv"], S["mlp"]))
+            g.linear(pb, nrm, nrm8, S["qkv"], 0, T, 3 * D, D, qkv, label=tag + ".qkv")
+            mlp_in(pb, S["mlp"], 0, T, cat, D, cat8, ep_mlp, S["out"], tag + ".proj_mlp")
+            g.rope(pb, qkv, 0, T, S["nqk"], tag + ".rope_qk")
+            g.attention(pb, qkv, cat, tag + ".attn", q8=cat8 if aq8_sgl else None)
             if on("proj_out") and not aq8_sgl:          # the attention half of the concatenation: its own quantiser pass over columns [0, D)
-                pb.quantize(cat, T, D, ldx=5 * D, q=cat8[0], scale=cat8[1], lds=lds, ldq=5 * D, label=tag + ".attn.q")
-            linear(pb, cat, cat8, S["out"], 0, T, D, 5 * D, x, gate=mod[b0 + 2], gate_rows_per=T, res=x, label=tag + ".proj_out")
+                g.quant(pb, cat, 5 * D, D, cat8, 0, T, tag + ".attn.q")
+            g.linear(pb, cat, cat8, S["out"], 0, T, D, 5 * D, x, gate=mod[b0 + 2], gate_rows_per=T, res=x, label=tag + ".proj_out")
 
         f0 = s0 + cfg["single_layers"] * 3
 

@@ -8,7 +8,8 @@ restated in oracle/flux2_ref.py.
 
 Graph design (MI355X-first), on top of what core/ml/flux.py already does for FLUX.1 (one [T, D] token buffer with the text
 rows first, fused q|k|v projections, per-head RMSNorm + RoPE in one in-place kernel with the softmax scale folded into q's
-rotary table, gated residuals as GEMM epilogues, one hipGraph replay per denoising step):
+rotary table, gated residuals as GEMM epilogues, one hipGraph replay per denoising step; the ops both graphs are wired from,
+the weight holder and the modulation cache are core/ml/dit_graph.py's):
   * FLUX.2 shares ONE set of modulation vectors per stream type across all blocks, so a step needs 17 vectors in total:
     one [17 D, D] GEMV per schedule step, cached per timestep.
   * single-stream blocks: `to_qkv_mlp_proj` is one [3 D + 6 D, D] GEMM; attention reads q / k / v straight out of its
@@ -16,9 +17,10 @@ rotary table, gated residuals as GEMM epilogues, one hipGraph replay per denoisi
     kernel fills, so `to_out(cat(attn, mlp))` is a plain GEMM.
   * fp8 (`fp8=True`, BASELINE.json config 5): every block linear runs on the MX-scaled fp8 matrix instructions
     (gemm.hip gemm256_f8_kernel, 2x the bf16 rate).  Weights are quantised once at load (e4m3 + one E8M0 scale per 32 k);
-    activations are quantised by `mtx_quantize_mx` right after the kernel that produces them (LayerNorm / attention /
-    SwiGLU), into fp8 twins of the bf16 buffers.  Embedders, modulation GEMVs, norm_out / proj_out and all
-    normalisation / softmax / residual arithmetic stay bf16 / fp32.
+    activations are quantised into fp8 twins of the bf16 buffers by the kernel that produces them (LayerNorm, attention,
+    the MLP-in GEMM's gated epilogue) or, with a fusion switched off, by `mtx_quantize_mx` right behind it — and only where
+    the linear that reads them is on the fp8 path (`fp8=` may name a subset of FP8_ALL).  Embedders, modulation GEMVs,
+    norm_out / proj_out and all normalisation / softmax / residual arithmetic stay bf16 / fp32.
 """
 import math
 import threading
@@ -31,6 +33,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, PlanBuilder, PlanCache, glu_interleave
 from ...utils.exceptions import ModelError
+from .dit_graph import DiTStep, ModulationCache, Weight, quantize_weight
 from .flux import FluxVAEHip, _rows, rope_table, sinusoid, synthetic_provider  # noqa: F401  (re-exported for callers)
 
 
@@ -72,13 +75,6 @@ def token_ids(t_txt, h2, w2, rh2, rw2, ref_t=10.0) -> np.ndarray:
 
 
 FP8_ALL = ("qkv", "out", "ff_in", "ff_out", "single_in", "single_out")
-
-
-class _W:
-    """one linear's weight: 16-bit [N, K], or its MX fp8 copy (bytes [N, K] + scale plane)"""
-
-    def __init__(self, w16=None, q=None, scale=None, lds=0):
-        self.w16, self.q, self.scale, self.lds = w16, q, scale, lds
 
 
 class Flux2DiTHip:
@@ -151,21 +147,14 @@ class Flux2DiTHip:
                                      nqk=torch.cat([g(p + ".norm_q.weight", f32), g(p + ".norm_k.weight", f32)]).contiguous(),
                                      out=self._weight(g(p + ".to_out.weight"), "single_out")))
         self._plans = PlanCache(6)           # a plan pins ~T x 40 D bytes of activations: keep a few resolutions only
-        self._mod_plan = None
-        self._mod_cache = {}
+        self._mods = ModulationCache(self._build_mod_plan, self.n_vec)
 
-    def _weight(self, w16: torch.Tensor, kind: str, glu_col0=None) -> _W:
+    def _weight(self, w16: torch.Tensor, kind: str, glu_col0=None) -> Weight:
         if kind not in self.fp8:
-            return _W(w16=w16)
+            return Weight(w16)
         if glu_col0 is not None and self.glu_epilogue:       # rows in [32 a | 32 b] runs from glu_col0 on (hip/plan.py glu_interleave)
             w16 = w16[glu_interleave(glu_col0, self.hid).to(w16.device)].contiguous()
-        n, k = w16.shape
-        pb = PlanBuilder(self.lib, self.device, self.dtype)
-        q, scale, lds = pb.quantize(w16, n, k)
-        pb.build().run()
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        return _W(q=q, scale=scale, lds=lds)            # the 16-bit copy is dropped: half the resident bytes
+        return quantize_weight(self.lib, self.device, self.dtype, w16)
 
     # ---- modulation vectors of one timestep ---------------------------------------------------------------
     def _build_mod_plan(self):
@@ -187,22 +176,16 @@ class Flux2DiTHip:
     def modulation(self, timestep: float, guidance=None) -> torch.Tensor:
         """[17, D] bf16 modulation rows of one denoising step, cached per (timestep, guidance)"""
         key = (round(float(timestep), 7), None if guidance is None else round(float(guidance), 5))
-        if len(self._mod_cache) > 256:
-            self._mod_cache.clear()
-        if key not in self._mod_cache:
-            if self._mod_plan is None:
-                self._mod_plan = self._build_mod_plan()
-            mp = self._mod_plan
+
+        def fill(mp):
             tin = np.stack([sinusoid(timestep * 1000.0), sinusoid((guidance or 0.0) * 1000.0)])
             mp.tin.copy_(torch.from_numpy(tin).to(self.device, self.tdt))
-            mp.run()
-            self._mod_cache[key] = mp.mods.view(self.n_vec, self.cfg["d"]).clone()
-        return self._mod_cache[key]
+        return self._mods.get(key, fill)
 
     # ---- one denoising step as a plan ------------------------------------------------------------------------
     def _build(self, t_txt, h2, w2, rh2, rw2):
         cfg, W = self.cfg, self.W
-        D, H, hd, hid = cfg["d"], cfg["heads"], self.hd, self.hid
+        D, H, hid = cfg["d"], cfg["heads"], self.hid
         t_noise, t_ref = h2 * w2, rh2 * rw2
         t_img = t_noise + t_ref
         T = t_txt + t_img
@@ -210,91 +193,36 @@ class Flux2DiTHip:
         pb = PlanBuilder(self.lib, self.device, self.dtype)
         lat = pb.buf((t_img, cfg["in_channels"]), self.tdt)       # [noise tokens ; reference tokens]
         ctx_in = pb.buf((t_txt, cfg["joint_dim"]), self.tdt)      # prompt embeddings
-        mod = pb.buf((self.n_vec, D), self.tdt)
         tab = torch.from_numpy(rope_table(token_ids(t_txt, h2, w2, rh2, rw2), cfg["axes_dim"], theta=cfg.get("rope_theta", 2000.0)))
-        q_fold = (1.0 / math.sqrt(hd)) * 1.4426950408889634       # softmax scale * log2(e), folded into q's rotary table
-        cs2 = pb.hold(torch.stack([tab, tab * q_fold]).to(self.device).contiguous())
-        cs = cs2[0]
-        x = pb.buf((T, D), self.tdt)
-        nrm = pb.buf((T, D), self.tdt)
+        f8 = bool(self.fp8)
+        g = DiTStep(pb, T, D, H, self.n_vec, tab, f8, self.fused_quant)
+        x, nrm, nrm8, mod, lds = g.x, g.nrm, g.nrm8, g.mod, g.lds
         qkv = pb.buf((T, 3 * D), self.tdt)
         o = pb.buf((T, D), self.tdt)
         ffh = pb.buf((T, 2 * hid), self.tdt)
         ffa = pb.buf((T, hid), self.tdt)
         big = pb.buf((T, FW), self.tdt)
         cat = pb.buf((T, D + hid), self.tdt)
-        f8 = bool(self.fp8)
-        lds = (T + 63) // 64 * 64
-        if f8:      # fp8 twins of the GEMM inputs
-            twin = lambda k: (pb.buf((T, k), torch.uint8), pb.buf((k // 128, lds), torch.int32, zero=True))
-            nrm8, o8, ffa8, cat8 = twin(D), twin(D), twin(hid), twin(D + hid)
-
-        def quant(src, k, dst, r0, r1, label):
-            pb.quantize(src, r1 - r0, k, x_off=r0 * k, q=dst[0], scale=dst[1], row_off=r0, lds=lds, label=label)
-
-        def linear(src, src8, w: _W, r0, r1, n, k, out, ldc=None, c_off=0, label="linear", **epi):
-            """out[r0:r1, c_off : c_off + n] = epilogue(src[r0:r1, :k] W^T) on the 16-bit or the fp8 kernel, as the weight says"""
-            m = r1 - r0
-            ldc = ldc or n
-            if w.q is not None:
-                pb.gemm(src8[0], w.q, m, n, k, out=out, ldc=ldc, a_off=r0 * k, c_off=r0 * ldc + c_off,
-                        f8=(src8[1], lds, w.scale, w.lds, r0, 0), label=label + ".f8", **epi)
-            else:
-                pb.gemm(src, w.w16, m, n, k, out=out, ldc=ldc, a_off=r0 * k, c_off=r0 * ldc + c_off, label=label, **epi)
+        o8, ffa8, cat8 = g.twin(pb, D), g.twin(pb, hid), g.twin(pb, D + hid)      # fp8 twins of the GEMM inputs (nrm8 is the recorder's)
+        aq8 = self.attn_q8 and f8 and T >= 1024                                   # the attention writes o8 / cat8[:, :D] itself
+        qk8 = pb.buf((T, 2 * D), torch.uint8, zero=True) if (self.attn_qk_f8 and T >= 1024) else None      # [token][q heads | k heads] e4m3
+        vt8 = pb.buf((D, lds), torch.uint8, zero=True) if (self.attn_pv_f8 and qk8 is not None and aq8) else None      # e4m3 V^T, reused by every block
 
         pb.gemm(ctx_in, W["context_embedder"], t_txt, D, cfg["joint_dim"], out=x, label="context_embedder")
         pb.gemm(lat, W["x_embedder"], t_img, D, cfg["in_channels"], out=x, c_off=t_txt * D, label="x_embedder")
 
-        def adaln(r0, r1, shift_i, scale_i, label, consumers=()):
-            """adaLN LayerNorm of rows [r0, r1).  With fp8 consumers the kernel writes their MX fp8 operand itself (mtx_norm_args.q:
-            bit-identical to a quantiser pass over its 16-bit output, which is then only written if some consumer still reads 16-bit)"""
-            to8 = f8 and self.fused_quant and any(w.q is not None for w in consumers)
-            need16 = not to8 or any(w.q is None for w in consumers)
-            pb.norm(x, nrm if need16 else None, r1 - r0, D, eps=1e-6, kind=0, mod_scale=mod[scale_i], mod_shift=mod[shift_i], rows_per=r1 - r0, ldmod=D,
-                    x_off=r0 * D, y_off=r0 * D, label=label, q8=nrm8 if to8 else None, q_row_off=r0, lds_q=lds)
-            if f8 and not to8:
-                quant(nrm, D, nrm8, r0, r1, label + ".q")
-
-        def rope(buf, r0, r1, gamma_qk, ld, label):
-            v = _rows(buf, r0, r1, 0, 2 * D)
-            e = abi.EwArgs()
-            e.a, e.b, e.s, e.y = v.ptr, cs[r0:].data_ptr(), gamma_qk.data_ptr(), v.ptr
-            e.n, e.h, e.w, e.c = 1, 1, r1 - r0, 2 * D
-            e.lda, e.ldb, e.ldy, e.lds = ld, T * hd, ld, 0
-            e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_NORM_ROPE, 0, 1e-6, hd, H, self.dtype
-            if qk8 is not None:
-                e.y8, e.ldy8, e.y8_mul = qk8.data_ptr() + r0 * 2 * D, 2 * D, 8.0
-            pb._add(abi.OP_EW, e, label)
-
-        aq8 = self.attn_q8 and f8 and T >= 1024
-        qk8 = pb.buf((T, 2 * D), torch.uint8, zero=True) if (self.attn_qk_f8 and T >= 1024) else None      # [token][q heads | k heads] e4m3
-
-        vt8 = pb.buf((D, (T + 63) // 64 * 64), torch.uint8, zero=True) if (self.attn_pv_f8 and qk8 is not None and aq8) else None      # e4m3 V^T, reused by every block
-
-        def attention(src, ld, out_t, out_ld, label, q8=None):
-            pv = None
-            if vt8 is not None and q8 is not None:
-                pv = pb.v_f8t(src, T, H, ld, v_off=2 * D, out=vt8, label=label + ".v_f8t")
-            pb.attention(src, src, src, None if q8 is not None else out_t, 1, H, T, T, hd, (0, ld, hd), (0, ld, hd), (0, ld, hd), (0, out_ld, hd),
-                         1.0 / math.sqrt(hd), k_off=D, v_off=2 * D, label=label, q_prescaled=True, q8=q8,
-                         qk_f8=(qk8, 0, D, 2 * D, -3) if qk8 is not None else None, pv_f8=pv)
-
-        def swiglu(src, ld, c0, r0, r1, dst, dst_ld, dst_c0, label, dst8=None, consumers=()):
-            """silu(a) * b of the two halves of a fused projection.  With fp8 consumers: one pass that writes their MX fp8 operand
-            (MTX_QUANT_SWIGLU) and the 16-bit result only if somebody still reads it"""
-            to8 = dst8 is not None and self.fused_quant and any(w.q is not None for w in consumers)
-            need16 = not to8 or any(w.q is None for w in consumers)
-            if to8:
+        def swiglu(src, c0, r0, r1, dst, dst_c0, label, dst8, consumer):
+            """silu(a) * b of the two halves of a fused projection (columns from c0 on) into dst[:, dst_c0 : dst_c0 + hid].  An fp8 consumer
+            reads the twin dst8 instead: written by one pass that also applies SwiGLU (MTX_QUANT_SWIGLU: no 16-bit result exists), or by a
+            quantiser launch behind the element-wise kernel"""
+            ld, dst_ld = src.shape[1], dst.shape[1]
+            if consumer.fp8 and self.fused_quant:
                 pb.quantize(src, r1 - r0, hid, ldx=ld, x_off=r0 * ld + c0, q=dst8[0], scale=dst8[1], row_off=r0, lds=lds, ldq=dst_ld, q_col_off=dst_c0,
-                            swiglu_b=src, b_off=r0 * ld + c0 + hid, ldb=ld, y=dst if need16 else None, y_off=r0 * dst_ld + dst_c0, ldy=dst_ld,
-                            label=label + ".q")
+                            swiglu_b=src, b_off=r0 * ld + c0 + hid, ldb=ld, y_off=r0 * dst_ld + dst_c0, ldy=dst_ld, label=label + ".q")
                 return
-            a_ = _rows(src, r0, r1, c0, hid)
-            b_ = _rows(src, r0, r1, c0 + hid, hid)
-            pb.ew(abi.EW_SWIGLU, a_, b=b_, out=_rows(dst, r0, r1, dst_c0, hid), label=label)
-            if dst8 is not None:
-                pb.quantize(dst, r1 - r0, hid, ldx=dst_ld, x_off=r0 * dst_ld + dst_c0, q=dst8[0], scale=dst8[1], row_off=r0, lds=lds, ldq=dst_ld,
-                            q_col_off=dst_c0, label=label + ".q")
+            pb.ew(abi.EW_SWIGLU, _rows(src, r0, r1, c0, hid), b=_rows(src, r0, r1, c0 + hid, hid), out=_rows(dst, r0, r1, dst_c0, hid), label=label)
+            if consumer.fp8:
+                g.quant(pb, dst, dst_ld, hid, dst8, r0, r1, label + ".q", c0=dst_c0)
 
         res_gate = lambda i, rows: dict(gate=mod[i], gate_rows_per=rows, res=x)
         # double-stream blocks: norms, quantisers and SwiGLU run over both streams at once; the text stream's four linears (512 rows, a
@@ -302,47 +230,47 @@ class Flux2DiTHip:
         for i, B in enumerate(self.blocks):
             tag = f"dbl{i}"
             pb.join()
-            adaln(t_txt, T, 0, 1, tag + ".norm1", (B["qkv"],))
-            adaln(0, t_txt, 6, 7, tag + ".norm1_ctx", (B["cqkv"],))
+            g.adaln(pb, t_txt, T, 0, 1, tag + ".norm1", (B["qkv"],))
+            g.adaln(pb, 0, t_txt, 6, 7, tag + ".norm1_ctx", (B["cqkv"],))
             with pb.side():
-                linear(nrm, nrm8 if f8 else None, B["cqkv"], 0, t_txt, 3 * D, D, qkv, label=tag + ".qkv_ctx")
-            linear(nrm, nrm8 if f8 else None, B["qkv"], t_txt, T, 3 * D, D, qkv, label=tag + ".qkv")
+                g.linear(pb, nrm, nrm8, B["cqkv"], 0, t_txt, 3 * D, D, qkv, label=tag + ".qkv_ctx")
+            g.linear(pb, nrm, nrm8, B["qkv"], t_txt, T, 3 * D, D, qkv, label=tag + ".qkv")
             pb.join()
-            rope(qkv, t_txt, T, B["nqk"], 3 * D, tag + ".rope_qk")
-            rope(qkv, 0, t_txt, B["cnqk"], 3 * D, tag + ".rope_qk_ctx")
-            attention(qkv, 3 * D, o, D, tag + ".attn", q8=(o8[0], o8[1], D, lds, 0) if aq8 else None)
-            if f8 and not aq8:
-                quant(o, D, o8, 0, T, tag + ".attn.q")
+            g.rope(pb, qkv, t_txt, T, B["nqk"], tag + ".rope_qk", qk_f8=qk8)
+            g.rope(pb, qkv, 0, t_txt, B["cnqk"], tag + ".rope_qk_ctx", qk_f8=qk8)
+            g.attention(pb, qkv, o, tag + ".attn", q8=o8 if aq8 else None, qk_f8=qk8, pv_f8=vt8)
+            if "out" in self.fp8 and not aq8:
+                g.quant(pb, o, D, D, o8, 0, T, tag + ".attn.q")
             with pb.side():
-                linear(o, o8 if f8 else None, B["cout"], 0, t_txt, D, D, x, label=tag + ".to_add_out", **res_gate(8, t_txt))
-            linear(o, o8 if f8 else None, B["out"], t_txt, T, D, D, x, res_off=t_txt * D, label=tag + ".to_out", **res_gate(2, t_img))
+                g.linear(pb, o, o8, B["cout"], 0, t_txt, D, D, x, label=tag + ".to_add_out", **res_gate(8, t_txt))
+            g.linear(pb, o, o8, B["out"], t_txt, T, D, D, x, res_off=t_txt * D, label=tag + ".to_out", **res_gate(2, t_img))
             pb.join()
-            adaln(t_txt, T, 3, 4, tag + ".norm2", (B["ff_in"],))
-            adaln(0, t_txt, 9, 10, tag + ".norm2_ctx", (B["cff_in"],))
+            g.adaln(pb, t_txt, T, 3, 4, tag + ".norm2", (B["ff_in"],))
+            g.adaln(pb, 0, t_txt, 9, 10, tag + ".norm2_ctx", (B["cff_in"],))
             glu = (lambda r0: dict(glu=(ffa8[0], ffa8[1], hid, lds, 0, r0, 0))) if self.glu_epilogue else (lambda r0: {})
             with pb.side():
-                linear(nrm, nrm8 if f8 else None, B["cff_in"], 0, t_txt, 2 * hid, D, ffh, label=tag + ".ff_in_ctx", **glu(0))
-            linear(nrm, nrm8 if f8 else None, B["ff_in"], t_txt, T, 2 * hid, D, ffh, label=tag + ".ff_in", **glu(t_txt))
+                g.linear(pb, nrm, nrm8, B["cff_in"], 0, t_txt, 2 * hid, D, ffh, label=tag + ".ff_in_ctx", **glu(0))
+            g.linear(pb, nrm, nrm8, B["ff_in"], t_txt, T, 2 * hid, D, ffh, label=tag + ".ff_in", **glu(t_txt))
             pb.join()
             if not self.glu_epilogue:
-                swiglu(ffh, 2 * hid, 0, t_txt, T, ffa, hid, 0, tag + ".swiglu", ffa8 if f8 else None, (B["ff_out"],))
-                swiglu(ffh, 2 * hid, 0, 0, t_txt, ffa, hid, 0, tag + ".swiglu_ctx", ffa8 if f8 else None, (B["cff_out"],))
+                swiglu(ffh, 0, t_txt, T, ffa, 0, tag + ".swiglu", ffa8, B["ff_out"])
+                swiglu(ffh, 0, 0, t_txt, ffa, 0, tag + ".swiglu_ctx", ffa8, B["cff_out"])
             with pb.side():
-                linear(ffa, ffa8 if f8 else None, B["cff_out"], 0, t_txt, D, hid, x, label=tag + ".ff_out_ctx", **res_gate(11, t_txt))
-            linear(ffa, ffa8 if f8 else None, B["ff_out"], t_txt, T, D, hid, x, res_off=t_txt * D, label=tag + ".ff_out", **res_gate(5, t_img))
+                g.linear(pb, ffa, ffa8, B["cff_out"], 0, t_txt, D, hid, x, label=tag + ".ff_out_ctx", **res_gate(11, t_txt))
+            g.linear(pb, ffa, ffa8, B["ff_out"], t_txt, T, D, hid, x, res_off=t_txt * D, label=tag + ".ff_out", **res_gate(5, t_img))
         pb.join()
         for i, S in enumerate(self.singles):
             tag = f"sgl{i}"
-            adaln(0, T, 12, 13, tag + ".norm", (S["fused"],))
-            linear(nrm, nrm8 if f8 else None, S["fused"], 0, T, FW, D, big, label=tag + ".to_qkv_mlp",
-                   **(dict(glu=(cat8[0], cat8[1], D + hid, lds, 3 * D, 0, D)) if self.glu_epilogue else {}))
-            rope(big, 0, T, S["nqk"], FW, tag + ".rope_qk")
-            attention(big, FW, cat, D + hid, tag + ".attn", q8=(cat8[0], cat8[1], D + hid, lds, 0) if aq8 else None)
+            g.adaln(pb, 0, T, 12, 13, tag + ".norm", (S["fused"],))
+            g.linear(pb, nrm, nrm8, S["fused"], 0, T, FW, D, big, label=tag + ".to_qkv_mlp",
+                     **(dict(glu=(cat8[0], cat8[1], D + hid, lds, 3 * D, 0, D)) if self.glu_epilogue else {}))
+            g.rope(pb, big, 0, T, S["nqk"], tag + ".rope_qk", qk_f8=qk8)
+            g.attention(pb, big, cat, tag + ".attn", q8=cat8 if aq8 else None, qk_f8=qk8, pv_f8=vt8)
             if not self.glu_epilogue:
-                swiglu(big, FW, 3 * D, 0, T, cat, D + hid, D, tag + ".swiglu", cat8 if f8 else None, (S["out"],))
-            if f8 and S["out"].q is not None and not aq8:          # the attention half of the concatenation: its own quantiser pass over columns [0, D)
-                pb.quantize(cat, T, D, ldx=D + hid, q=cat8[0], scale=cat8[1], lds=lds, ldq=D + hid, label=tag + ".attn.q")
-            linear(cat, cat8 if f8 else None, S["out"], 0, T, D, D + hid, x, label=tag + ".to_out", **res_gate(14, T))
+                swiglu(big, 3 * D, 0, T, cat, D, tag + ".swiglu", cat8, S["out"])
+            if "single_out" in self.fp8 and not aq8:          # the attention half of the concatenation: its own quantiser pass over columns [0, D)
+                g.quant(pb, cat, D + hid, D, cat8, 0, T, tag + ".attn.q")
+            g.linear(pb, cat, cat8, S["out"], 0, T, D, D + hid, x, label=tag + ".to_out", **res_gate(14, T))
         pb.norm(x, nrm, t_noise, D, eps=1e-6, kind=0, mod_scale=mod[15], mod_shift=mod[16], rows_per=t_noise, ldmod=D,
                 x_off=t_txt * D, y_off=t_txt * D, label="norm_out")
         vel = pb.gemm(nrm, W["proj_out"], t_noise, cfg["in_channels"], D, a_off=t_txt * D, out_f32=True, label="proj_out")

@@ -461,6 +461,20 @@ class PlanBuilder:
         self._add(abi.OP_EW, e, label)
         return out
 
+    def qk_norm_rope(self, qk: Act, cs, ld_cs, gamma_qk, d, heads, eps=1e-6, y8=None, label="qk_norm_rope"):
+        """MTX_EW_QK_NORM_ROPE in place over `qk`, the q | k column view ([rows, 2 * heads * d]) of some token rows: per-head RMSNorm (gamma_qk
+        fp32 [2 d]: q's vector, then k's) and the rotary turn.  cs: fp32 [rows][2][d / 2] cos | sin rows of the same tokens; the q heads read
+        the copy ld_cs floats behind it (pre-multiplied by softmax scale * log2(e), MTX_ATTN_Q_PRESCALED).
+        y8 = (e4m3 bytes of the same rows, ldy8, q multiplier): also the plain e4m3 twin of the result (mtx_ew_args.y8; `attention(qk_f8=...)`)"""
+        e = abi.EwArgs()
+        e.a, e.b, e.s, e.y = qk.ptr, _ptr(cs), _ptr(gamma_qk), qk.ptr
+        e.n, e.h, e.w, e.c = 1, 1, qk.w, qk.c
+        e.lda, e.ldb, e.ldy, e.lds = qk.ld, ld_cs, qk.ld, 0
+        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_NORM_ROPE, 0, eps, d, heads, self.dtype
+        if y8 is not None:
+            e.y8, e.ldy8, e.y8_mul = _ptr(y8[0]), y8[1], y8[2]
+        self._add(abi.OP_EW, e, label)
+
     def residual_dist(self, after, before, prev, rows, c, parts=None, after_off=0, before_off=0, ld=None, label="residual_dist"):
         """first-block cache probe (include/mtx_hip.h MTX_EW_RESIDUAL_DIST): r = after - before (rounded to the storage type) against `prev`;
         -> fp32 [RESDIST_PARTS, 2]: per part (sum |prev - r|, sum |prev|); `residual_distance(parts)` adds them in index order"""

@@ -66,6 +66,28 @@ def test_kontext_fp8_geometry(emu_lib):
     assert sum(1 for o in plan.ops if o.kind == abi.OP_QUANT) == 1          # the attention half of cat8 (T < 1024: the attention cannot write it)
 
 
+def test_plan_dump_names_every_pointer_and_repeats(emu_lib):
+    """tools/plan_dump.py on the three plans of a cached fp8 build: every pointer of every op lies in a buffer of the plans or in a weight of
+    the model (the dump raises otherwise), and a second, independent build of the same model gives the same text"""
+    import sys
+    from pathlib import Path
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
+    import plan_dump as pd
+    dumps = []
+    for _ in range(2):
+        plan, dit = pd.toy_plan("kontext", emu_lib, (4, 6, 16), fp8=True, cached=True)
+        dumps.append(pd.dump(plan, dit))
+        assert len(dumps[-1]) == len(plan.ops) + len(plan.body.ops) + len(plan.skip.ops)
+    assert dumps[0] == dumps[1]
+    heads = {ln.split()[0] for ln in dumps[0]}
+    assert heads == {"head", "body", "skip"} and any(" q=b" in ln for ln in dumps[0]) and "0x" not in "".join(dumps[0])
+    # an op that points outside every known buffer is an error, not a line
+    stray = torch.zeros(64, dtype=torch.bfloat16)
+    plan.ops[0].u.gemm.bias = stray.data_ptr()
+    with pytest.raises(LookupError):
+        pd.dump(plan, dit)
+
+
 @pytest.fixture()
 def manager(emu_lib, tmp_path, monkeypatch):
     import mangatranslator_amd.hip.lib as libmod
@@ -86,7 +108,7 @@ def test_manager_flag_reaches_the_dit_and_the_memo_key(manager, fp8):
     """ModelManager.flux_kontext_fp8 -> load_flux_kontext_sdnq -> FluxDiTHip(fp8=): the inpainter runs, and its stage-memo key carries the
     arithmetic only when the flag is on (off: the key the package made before the flag existed)"""
     from mangatranslator_amd.core.image.inpainting import FluxKontextInpainter
-    from mangatranslator_amd.core.ml.flux import _W8
+    from mangatranslator_amd.core.ml.dit_graph import Weight
     from mangatranslator_amd.core.ml.model_manager import ModelManager, ModelType
     assert ModelManager.flux_kontext_fp8 is False                 # the default stays bf16
     t, v = fc.models(seed=4)
@@ -107,7 +129,7 @@ def test_manager_flag_reaches_the_dit_and_the_memo_key(manager, fp8):
     pipe = manager.load_flux_kontext_sdnq()
     assert pipe is not None and manager.load_flux_models()[2] is pipe
     dit = pipe.transformer
-    assert bool(dit.fp8) == fp8 and isinstance(dit.blocks[0]["qkv"][0], _W8) == fp8 and isinstance(dit.singles[0]["out"][0], _W8) == fp8
+    assert bool(dit.fp8) == fp8 and dit.blocks[0]["qkv"].fp8 == fp8 and dit.singles[0]["out"].fp8 == fp8 and isinstance(dit.blocks[0]["qkv"], Weight)
     assert dit.W["proj_out"][0].dtype == torch.bfloat16           # the output layer stays 16-bit either way
     inp = FluxKontextInpainter(num_inference_steps=1, backend="sdnq")
     inp.PREFERED_KONTEXT_RESOLUTIONS = [(48, 32), (32, 48), (32, 32)]

@@ -145,7 +145,7 @@ def test_load_flux_klein_and_inpaint(manager, fp8):
     manager.flux_klein_fp8 = fp8
     pipe = manager.load_flux_klein_4b()
     assert pipe is not None and manager.load_flux_klein_4b() is pipe
-    assert bool(pipe.transformer.fp8) == fp8 and (pipe.transformer.blocks[0]["qkv"].q is not None) == fp8
+    assert bool(pipe.transformer.fp8) == fp8 and pipe.transformer.blocks[0]["qkv"].fp8 == fp8
     assert torch.allclose(pipe.vae.bn_mean.cpu(), v.bn.running_mean)
     inp = FluxKleinInpainter(variant="4b", num_inference_steps=1)
     inp.upscale_small_crops = False                        # keep the simulator's crop at 64 x 64

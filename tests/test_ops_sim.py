@@ -202,6 +202,32 @@ def test_flux_prep_kernels(emu_lib):
     oc.check_softmax_transpose(emu_lib, abi.F16, rows=70, cols=136)
 
 
+@pytest.mark.parametrize("twin", [False, True])
+def test_qk_norm_rope_builder_fills_the_block(emu_lib, twin):
+    """PlanBuilder.qk_norm_rope records the mtx_ew_args a model used to fill by hand: rows [r0, r1) of a [T, 3 D] q | k | v buffer, the rotary
+    table's plane stride, both gamma vectors, with and without the e4m3 twin — field by field"""
+    from mangatranslator_amd.hip.plan import Act, PlanBuilder
+    T, H, hd, r0, r1 = 40, 2, 128, 8, 29
+    D = H * hd
+    pb = PlanBuilder(emu_lib, "cpu", abi.BF16)
+    qkv, cs, gamma = pb.buf((T, 3 * D), torch.bfloat16), pb.buf((2, T, 2, hd // 2)), pb.buf((2 * hd,))
+    qk8 = pb.buf((T, 2 * D), torch.uint8)
+    want = abi.EwArgs()
+    want.a = want.y = qkv.data_ptr() + r0 * 3 * D * 2
+    want.b, want.s = cs.data_ptr() + r0 * hd * 4, gamma.data_ptr()
+    want.n, want.h, want.w, want.c = 1, 1, r1 - r0, 2 * D
+    want.lda, want.ldb, want.ldy, want.lds = 3 * D, T * hd, 3 * D, 0
+    want.kind, want.act, want.act_param, want.i0, want.i1, want.dtype = abi.EW_QK_NORM_ROPE, 0, 1e-6, hd, H, abi.BF16
+    if twin:
+        want.y8, want.ldy8, want.y8_mul = qk8.data_ptr() + r0 * 2 * D, 2 * D, 8.0
+    view = Act(qkv[r0:r1].view(1, 1, r1 - r0, 3 * D), 1, 1, r1 - r0, 2 * D)
+    pb.qk_norm_rope(view, cs[0][r0:], T * hd, gamma, hd, H, eps=1e-6, y8=(qk8[r0:], 2 * D, 8.0) if twin else None, label="rope")
+    assert pb.labels == ["rope"] and pb.ops[0].kind == abi.OP_EW and pb.ops[0].lane == 0
+    got = pb.ops[0].u.ew
+    for name, _ in abi.EwArgs._fields_:
+        assert getattr(got, name) == getattr(want, name), name
+
+
 def test_gemm_k_slice_tail(emu_lib):
     """tiles % CUs != 0 (the simulator reports 3 CUs): the left-over tile is cut into K slices whose last arriver sums the partials in
     slice order and runs the epilogue (gemm256_slice_kernel); a second and third run of the same plan must reproduce the first bit for

@@ -331,7 +331,9 @@ typedef struct mtx_img_args {
   int32_t unshuffle;      /* 1 or 2 (pixel-unshuffle factor folded into the layout change) */
   float mul; float add[4];
   int32_t kind; int32_t dtype;
-  const int32_t* valid_hw;       /* optional DEVICE {valid_h, valid_w} in SOURCE pixels (kinds 0 and 3): destination pixels beyond are zero */
+  const int32_t* valid_hw;       /* optional DEVICE {valid_h, valid_w} in SOURCE pixels (kinds 0 and 3): a destination pixel whose first source
+                                    pixel (y * unshuffle, x * unshuffle) lies beyond is zero in all c_pad channels; one that straddles the edge
+                                    (odd valid size, unshuffle 2) is converted whole, source pixels beyond the valid size included (callers pad) */
 } mtx_img_args;
 
 /* bilinear resize of fp32/T logits to page size fused with the >0 threshold
@@ -348,8 +350,9 @@ typedef struct mtx_resize_thresh_args {
 } mtx_resize_thresh_args;
 
 /* SAM-2.1 single-mask selection (transformers Sam2MaskDecoder._dynamic_multimask_via_stability,
- * modeling_sam2.py:1265-1311): per box, stability = |logit0 > +delta| / |logit0 > -delta|;
- * sel = 0 if stability >= thresh else 1 + argmax(iou[1:4]).  logits fp32 [N, pix, 4].        */
+ * modeling_sam2.py:1265-1311): per box, stability = |logit0 > +delta| / |logit0 > -delta| (both comparisons
+ * strict, the quotient in fp32, 1 when the denominator is 0); sel = 0 if stability >= thresh else
+ * 1 + argmax(iou[1:4]) (the first maximum).  logits fp32 [N, pix, 4]; counts is zeroed by the call.   */
 typedef struct mtx_mask_select_args {
   const float* logits; const float* iou; int32_t* counts /* [N][2] scratch */; int32_t* sel /* [N] */;
   int64_t n, pix; float delta, thresh;

@@ -1,6 +1,7 @@
 """GPU tier: op-level parity of libmtx_hip.so (through the C ABI) against torch fp32 on MI355X."""
 import pytest
 
+import detector_checks as dc
 import exact_checks as ec
 import op_checks as oc
 import operand_checks as pc
@@ -433,3 +434,79 @@ def test_residual_dist_exact(hip_lib, dtype):
 def test_attention_fp8_output_selects_rows_merge(hip_lib, dtype):
     """260 query blocks on 256 CUs: four go through the key-split tail and leave through the quantising merge kernel"""
     pc.check_attention_selector(hip_lib, dtype, sq=33030, sk=320, seed=1)
+
+
+# ---- exact inputs for the detector pre- and post-processing kernels (detector_checks.py): deformable attention, box refinement, YOLO decode,
+# mask selection, resize + threshold, page boundary conversions, letterbox
+def _id(cfg):
+    return "-".join(str(v).replace(" ", "") for v in cfg.values())
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.DEFORM_CASES + dc.DEFORM_CASES_GPU, ids=_id)
+def test_deform_attention_exact(hip_lib, dtype, cfg):
+    dc.check_deform_attn(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.BOX_CASES, ids=_id)
+def test_box_refine_exact(hip_lib, dtype, cfg):
+    dc.check_box_refine(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.YOLO_CASES, ids=_id)
+def test_yolo_decode_exact(hip_lib, dtype, cfg):
+    dc.check_yolo_decode(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("cfg", dc.MASK_CASES, ids=_id)
+def test_mask_select_exact(hip_lib, cfg):
+    dc.check_mask_select(hip_lib, **cfg)
+
+
+@pytest.mark.parametrize("cfg", dc.RESIZE_CASES, ids=_id)
+def test_resize_threshold_exact(hip_lib, cfg):
+    dc.check_resize_exact(hip_lib, **cfg)
+
+
+@pytest.mark.parametrize("roi", [None, (3, 2, 10, 12)])
+def test_resize_threshold_general(hip_lib, roi):
+    dc.check_resize_general(hip_lib, roi=roi)
+    dc.check_resize_general(hip_lib, roi=roi, thresh=0.5, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_image_convert_u8_intake_exact(hip_lib, dtype):
+    """MTX_IMG_HWC_U8_TO_NHWC with the mul / add of its two call sites, every byte value in every channel"""
+    dc.check_u8_to_nhwc(hip_lib, dtype, 1.0, 0.0, unshuffle=1, c_pad=8)
+    dc.check_u8_to_nhwc(hip_lib, dtype, 2.0, -1.0, unshuffle=1, c_pad=16)
+    dc.check_u8_to_nhwc(hip_lib, dtype, 2.0, -1.0, unshuffle=2, c_pad=16)
+    dc.check_u8_to_nhwc(hip_lib, dtype, 1.0, 0.0, unshuffle=2, c_pad=16)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("mul_add", [(1.0, 0.0), (0.5, 0.5)])
+def test_image_convert_u8_output_census(hip_lib, dtype, mul_add):
+    dc.check_nhwc_to_u8(hip_lib, dtype, *mul_add)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_image_convert_valid_hw_and_batch(hip_lib, dtype):
+    dc.check_nchw(hip_lib, dtype, n=2)
+    dc.check_nchw(hip_lib, dtype, n=2, unshuffle=2, c_pad=16)
+    dc.check_nchw(hip_lib, dtype, n=2, h=10, w=14, valid=(7, 9))
+    dc.check_nchw(hip_lib, dtype, n=2, h=10, w=14, unshuffle=2, c_pad=16, valid=(7, 9))
+    dc.check_u8_to_nhwc(hip_lib, dtype, 2.0, -1.0, n=2, h=10, w=14, valid=(7, 9))
+    dc.check_u8_to_nhwc(hip_lib, dtype, 1.0, 0.0, n=2, h=10, w=14, unshuffle=2, c_pad=16, valid=(7, 9))
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.LETTERBOX_CASES, ids=_id)
+def test_letterbox_exact(hip_lib, dtype, cfg):
+    dc.check_letterbox(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_image_convert_round_trip_beyond_one_grid(hip_lib, dtype):
+    dc.check_u8_round_trip_large(hip_lib, dtype)

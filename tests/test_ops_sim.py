@@ -4,6 +4,7 @@ maps, epilogues) where no GPU exists; the same checks run on hardware in test_op
 import pytest
 import torch
 
+import detector_checks as dc
 import exact_checks as ec
 import op_checks as oc
 import operand_checks as pc
@@ -458,3 +459,74 @@ def test_softmax_rows_exact(emu_lib, dtype):
 def test_residual_dist_exact(emu_lib, dtype):
     pc.check_residual_dist_exact(emu_lib, dtype, rows=33, c=136, ld_extra=24)
     pc.check_residual_dist_exact(emu_lib, dtype, rows=700, c=768, ld_extra=8, seed=1, expect_trips=2)      # more chunks than MTX_RESDIST_PARTS * 256 threads
+
+
+# ---- exact inputs for the detector pre- and post-processing kernels (detector_checks.py): deformable attention, box refinement, YOLO decode,
+# mask selection, resize + threshold, page boundary conversions, letterbox
+def _id(cfg):
+    return "-".join(str(v).replace(" ", "") for v in cfg.values())
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.DEFORM_CASES, ids=_id)
+def test_deform_attention_exact(emu_lib, dtype, cfg):
+    dc.check_deform_attn(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.BOX_CASES, ids=_id)
+def test_box_refine_exact(emu_lib, dtype, cfg):
+    dc.check_box_refine(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.YOLO_CASES, ids=_id)
+def test_yolo_decode_exact(emu_lib, dtype, cfg):
+    dc.check_yolo_decode(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("cfg", dc.MASK_CASES, ids=_id)
+def test_mask_select_exact(emu_lib, cfg):
+    dc.check_mask_select(emu_lib, **cfg)
+
+
+@pytest.mark.parametrize("cfg", dc.RESIZE_CASES, ids=_id)
+def test_resize_threshold_exact(emu_lib, cfg):
+    dc.check_resize_exact(emu_lib, **cfg)
+
+
+@pytest.mark.parametrize("roi", [None, (3, 2, 10, 12)])
+def test_resize_threshold_general(emu_lib, roi):
+    dc.check_resize_general(emu_lib, roi=roi)
+    dc.check_resize_general(emu_lib, roi=roi, thresh=0.5, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_image_convert_u8_intake_exact(emu_lib, dtype):
+    """MTX_IMG_HWC_U8_TO_NHWC with the mul / add of its two call sites, every byte value in every channel"""
+    dc.check_u8_to_nhwc(emu_lib, dtype, 1.0, 0.0, unshuffle=1, c_pad=8)
+    dc.check_u8_to_nhwc(emu_lib, dtype, 2.0, -1.0, unshuffle=1, c_pad=16)
+    dc.check_u8_to_nhwc(emu_lib, dtype, 2.0, -1.0, unshuffle=2, c_pad=16)
+    dc.check_u8_to_nhwc(emu_lib, dtype, 1.0, 0.0, unshuffle=2, c_pad=16)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("mul_add", [(1.0, 0.0), (0.5, 0.5)])
+def test_image_convert_u8_output_census(emu_lib, dtype, mul_add):
+    dc.check_nhwc_to_u8(emu_lib, dtype, *mul_add)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_image_convert_valid_hw_and_batch(emu_lib, dtype):
+    dc.check_nchw(emu_lib, dtype, n=2)
+    dc.check_nchw(emu_lib, dtype, n=2, unshuffle=2, c_pad=16)
+    dc.check_nchw(emu_lib, dtype, n=2, h=10, w=14, valid=(7, 9))
+    dc.check_nchw(emu_lib, dtype, n=2, h=10, w=14, unshuffle=2, c_pad=16, valid=(7, 9))
+    dc.check_u8_to_nhwc(emu_lib, dtype, 2.0, -1.0, n=2, h=10, w=14, valid=(7, 9))
+    dc.check_u8_to_nhwc(emu_lib, dtype, 1.0, 0.0, n=2, h=10, w=14, unshuffle=2, c_pad=16, valid=(7, 9))
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", dc.LETTERBOX_CASES, ids=_id)
+def test_letterbox_exact(emu_lib, dtype, cfg):
+    dc.check_letterbox(emu_lib, dtype, **cfg)

@@ -149,7 +149,117 @@ def _opaque_for_device_resize(crop: Image.Image) -> bool:
     return False
 
 
-class FluxKontextInpainter:
+class _FluxInpainter:
+    """What the two operators do alike around their own `inpaint_mask`: the DeviceTail, the stage-memo key, the composite clip, the crop upload,
+    the page round trip of the device composite and the locked, seeded pipeline call.  A subclass supplies `load_models()`, `_memo_own()`,
+    `_unavailable_warning()` and `_run_pipeline()`, and the attributes its constructor sets (`manager`, `cache`, `pipeline`, `backend`, ...)."""
+
+    device_tail = True          # False: the host path (PIL / numpy), the reference's own arithmetic
+    _tail = None                # the DeviceTail once made; `unload_models()` drops it with the pipeline it belongs to
+
+    def _device_tail(self):
+        """the DeviceTail of the pipeline's device, or None (host path): needs a loaded pipeline made of libmtx_hip graphs that lives on a GPU
+        (or the test simulator) and takes / returns device tensors"""
+        if not self.device_tail:
+            return None
+        if self._tail is not None:
+            return self._tail
+        self.load_models()
+        pipe = self.pipeline
+        lib = getattr(getattr(pipe, "transformer", None), "lib", None)
+        if pipe is None or lib is None or not hasattr(pipe, "device"):
+            return None
+        from .device_tail import get_device_tail
+        self._tail = get_device_tail(lib, pipe.device)
+        return self._tail
+
+    # ---- the stage-memo key ---------------------------------------------------------------------------
+    @staticmethod
+    def _mask_signature(mask_crop: np.ndarray) -> np.ndarray:
+        """the mask as the key sees it: bilinear to at most 64x64 (at least 4x4), thresholded at 0.5 — robust to one-pixel jitter of the detections"""
+        if mask_crop.size == 0:
+            return mask_crop
+        size = (min(64, max(4, mask_crop.shape[0])), min(64, max(4, mask_crop.shape[1])))
+        small = torch.nn.functional.interpolate(torch.from_numpy(mask_crop.astype(np.float32))[None, None], size=size, mode="bilinear", align_corners=False)
+        return (small > 0.5).numpy().astype(np.uint8)[0, 0]
+
+    def _memo_key(self, crop, mask_crop, seed, bbox, padding, blur, ocr_params, strict_mask_clipping, composite_clip_bbox):
+        """Key of the crop-sized patch in the stage memo (reference :781-827 and :1433-1489): crop pixels, the mask signature, sampler settings
+        and crop geometry, plus what `_memo_own()` adds for the class.  None when seed == -1 (fresh noise)."""
+        if not self.cache.should_use_inpaint_cache(seed):
+            return None
+        own, (threshold, guidance_scale, prompt) = self._memo_own()
+        params = {"bbox": tuple(int(v) for v in bbox), "padding": int(padding), "blur": int(blur), "backend": self.backend, **own}
+        if self.backend == "sdcpp":
+            params.update(sdcpp_cache=self.sdcpp_cache_mode, sdcpp_diffusion_quant=self.sdcpp_diffusion_quant,
+                          sdcpp_text_encoder_quant=self.sdcpp_text_encoder_quant)
+        if strict_mask_clipping:
+            params["strict_clip"] = True
+        if composite_clip_bbox is not None:
+            params["clip_bbox"] = tuple(composite_clip_bbox)
+        if ocr_params:
+            params.update(ocr_params)
+        return self.cache.get_inpaint_cache_key(crop, self._mask_signature(mask_crop), seed, self.num_inference_steps, threshold, guidance_scale,
+                                                prompt, params)
+
+    # ---- the composite clip ---------------------------------------------------------------------------
+    @staticmethod
+    def _clip_rect(composite_clip_bbox, page_size: Tuple[int, int], crop_box: Tuple[int, int, int, int]):
+        """`composite_clip_bbox` (x1, y1, x2, y2 on the page) clamped to the page of `page_size` = (w, h) and moved into the coordinates of
+        `crop_box` = (x, y, w, h): (x0, y0, x1, y1), empty when x1 <= x0 or y1 <= y0.  None without a bbox."""
+        if composite_clip_bbox is None:
+            return None
+        (img_w, img_h), (x, y, w, h) = page_size, crop_box
+        cx1, cy1, cx2, cy2 = composite_clip_bbox
+        cx1, cx2 = max(0, min(img_w, cx1)), max(0, min(img_w, cx2))
+        cy1, cy2 = max(0, min(img_h, cy1)), max(0, min(img_h, cy2))
+        return max(0, cx1 - x), max(0, cy1 - y), min(w, cx2 - x), min(h, cy2 - y)
+
+    @staticmethod
+    def _clip_weight(alpha: np.ndarray, clip_rect) -> np.ndarray:
+        """the host composite weight kept only inside `clip_rect` (`DeviceTail.feather` does the same to the device weight)"""
+        if clip_rect is None:
+            return alpha
+        ax0, ay0, ax1, ay1 = clip_rect
+        keep = np.zeros_like(alpha)
+        if ax1 > ax0 and ay1 > ay0:
+            keep[ay0:ay1, ax0:ax1] = alpha[ay0:ay1, ax0:ax1]
+        return keep
+
+    # ---- host <-> device ------------------------------------------------------------------------------
+    @staticmethod
+    def _upload_rgb(tail, crop: Image.Image) -> torch.Tensor:
+        """the crop as a uint8 HWC tensor on the tail's device (callers checked `_opaque_for_device_resize`: the conversion drops no alpha)"""
+        return torch.from_numpy(np.array(crop if crop.mode == "RGB" else crop.convert("RGB"))).to(tail.device)
+
+    @staticmethod
+    def _composite_on_device(tail, image_pil: Image.Image, patch_dev, alpha_dev, x: int, y: int) -> Image.Image:
+        """the page uploaded, `patch_dev` blended in at (x, y) with `alpha_dev`, downloaded in the page's own mode"""
+        page = torch.from_numpy(np.array(image_pil)).to(tail.device)          # a copy: the composite is in place
+        if page.dim() == 2:
+            page = page[..., None]
+        tail.composite(page.contiguous(), patch_dev, alpha_dev, x, y)
+        out_np = page.cpu().numpy()
+        return Image.fromarray(out_np[..., 0] if out_np.shape[2] == 1 else out_np, image_pil.mode)
+
+    # ---- the pipeline call ----------------------------------------------------------------------------
+    def _generate(self, image, inf_w: int, inf_h: int, seed: int):
+        """`image` at inf_w x inf_h — PIL on the host path, a uint8 HWC device tensor on the device path — through the pipeline: the patch at
+        that size in the form the image came in, or None (after the warning) when there is no pipeline"""
+        with self.manager.flux_inference_lock:
+            self.load_models()
+            if self.pipeline is None:
+                log_message(self._unavailable_warning(), always_print=True)
+                return None
+            with torch.inference_mode():
+                # the reference seeds a generator on ITS device (:1568), so its noise comes from that backend's Philox stream; these
+                # pipelines draw the initial latents on the host (bit-stable across boxes and ranks).  Same seed -> same noise within
+                # either implementation, never across them: pixel parity with a checkpoint is judged on the SAME latents (the
+                # pipelines accept `latents=`, which the parity tests use)
+                return self._run_pipeline(image, inf_w, inf_h, torch.Generator(device="cpu").manual_seed(seed))
+
+
+class FluxKontextInpainter(_FluxInpainter):
     def __init__(self, device: Optional[torch.device] = None, huggingface_token: str = "", num_inference_steps: int = 8,
                  residual_diff_threshold: float = 0.15, backend: str = "nunchaku", low_vram: bool = False,
                  sdcpp_cache_mode: str = "none", sdcpp_diffusion_quant: str = "", sdcpp_text_encoder_quant: str = ""):
@@ -242,16 +352,7 @@ class FluxKontextInpainter:
             alpha[sy0 - qy:sy1 - qy, sx0 - qx:sx1 - qx] = alpha_full[sy0:sy1, sx0:sx1]
         if strict_mask_clipping:
             alpha = alpha * mask[qy:qy + qh, qx:qx + qw].astype(np.float32)
-        if composite_clip_bbox is not None:
-            cx1, cy1, cx2, cy2 = composite_clip_bbox
-            cx1, cx2 = max(0, min(img_w, cx1)), max(0, min(img_w, cx2))
-            cy1, cy2 = max(0, min(img_h, cy1)), max(0, min(img_h, cy2))
-            keep = np.zeros_like(alpha)
-            ax0, ax1 = max(0, cx1 - qx), min(qw, cx2 - qx)
-            ay0, ay1 = max(0, cy1 - qy), min(qh, cy2 - qy)
-            if ax1 > ax0 and ay1 > ay0:
-                keep[ay0:ay1, ax0:ax1] = alpha[ay0:ay1, ax0:ax1]
-            alpha = keep
+        alpha = self._clip_weight(alpha, self._clip_rect(composite_clip_bbox, (img_w, img_h), (qx, qy, qw, qh)))
         return alpha, qx, qy, qw, qh, padding, blur
 
     # ---- the operator ---------------------------------------------------------------------------------
@@ -268,109 +369,50 @@ class FluxKontextInpainter:
         crop = image_pil.crop((x, y, x + w, y + h))
         key = self._memo_key(crop, mask[y:y + h, x:x + w], seed, (x, y, w, h), padding, blur, ocr_params, strict_mask_clipping, composite_clip_bbox)
         patch = self.cache.get_inpainted_image(key) if key is not None else None
+        # LANCZOS to the preferred Kontext resolution, the pipeline, LANCZOS back and the composite without leaving HBM
+        # (core/image/device_tail.py: Pillow's resize and the composite bit for bit); translucent crops: the host path (premultiplied resize)
+        tail = self._device_tail() if patch is None and _opaque_for_device_resize(crop) else None
         if patch is not None:
             log_message("  - Using cached inpainting patch", verbose=verbose)
-            return Image.fromarray(composite_u8(np.asarray(image_pil), np.asarray(patch), alpha, x, y))
-        tail = self._device_tail() if _opaque_for_device_resize(crop) else None      # translucent crops: the host path (premultiplied resize)
-        if tail is not None:
-            # LANCZOS to the preferred Kontext resolution, the pipeline, LANCZOS back and the composite without leaving HBM
-            # (core/image/device_tail.py: Pillow's resize and the composite bit for bit)
-            dev = tail.device
-            crop_dev = torch.from_numpy(np.array(crop if crop.mode == "RGB" else crop.convert("RGB"))).to(dev)
-            inf_w, inf_h = nearest_preferred_resolution(w, h, self.PREFERED_KONTEXT_RESOLUTIONS) if w and h else (w, h)
-            scaled = tail.resize(crop_dev, (inf_w, inf_h), "lanczos")
-            with self.manager.flux_inference_lock:
-                self.load_models()
-                if self.pipeline is None:
-                    log_message("Warning: Flux Kontext pipeline not available. Skipping inpainting.", always_print=True)
-                    return image_pil
-                with torch.inference_mode():
-                    gen = torch.Generator(device="cpu").manual_seed(seed)
-                    out = self.pipeline(image=scaled, width=inf_w, height=inf_h, num_inference_steps=self.num_inference_steps,
-                                        guidance_scale=self.guidance_scale, generator=gen, output_type="pt",
-                                        max_area=inf_w * inf_h, residual_diff_threshold=self._cache_threshold, **self._prompt_kwargs())
-                    img = torch.nan_to_num(out.images[0].float(), nan=0.0, posinf=1.0, neginf=0.0).clamp_(0, 1)
-                    patch_dev = img.mul(255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
-            patch_dev = tail.resize(patch_dev, (w, h), "lanczos")
-            if key is not None:
-                self.cache.set_inpainted_image(key, Image.fromarray(patch_dev.cpu().numpy()))
-            page = torch.from_numpy(np.array(image_pil)).to(dev)          # a copy: the composite is in place
-            if page.dim() == 2:
-                page = page[..., None]
-            tail.composite(page.contiguous(), patch_dev, torch.from_numpy(np.ascontiguousarray(alpha, dtype=np.float32)).to(dev), x, y)
-            out_np = page.cpu().numpy()
-            return Image.fromarray(out_np[..., 0] if out_np.shape[2] == 1 else out_np, image_pil.mode)
-        scaled = self.flux_kontext_image_scale(crop)
-        inf_w, inf_h = scaled.size
-        if scaled.mode == "RGBA":
-            scaled = scaled.convert("RGB")
-        with self.manager.flux_inference_lock:
-            self.load_models()
-            if self.pipeline is None:
-                log_message("Warning: Flux Kontext pipeline not available. Skipping inpainting.", always_print=True)
+        else:
+            inf_w, inf_h = nearest_preferred_resolution(w, h, self.PREFERED_KONTEXT_RESOLUTIONS)
+            if tail is not None:
+                scaled = tail.resize(self._upload_rgb(tail, crop), (inf_w, inf_h), "lanczos")
+            else:
+                scaled = self.flux_kontext_image_scale(crop)
+                if scaled.mode == "RGBA":
+                    scaled = scaled.convert("RGB")
+            patch = self._generate(scaled, inf_w, inf_h, seed)
+            if patch is None:
                 return image_pil
-            with torch.inference_mode():
-                gen = torch.Generator(device="cpu").manual_seed(seed)
-                out = self.pipeline(image=scaled, width=inf_w, height=inf_h, num_inference_steps=self.num_inference_steps,
-                                    guidance_scale=self.guidance_scale, generator=gen, output_type="pt",
-                                    max_area=inf_w * inf_h, residual_diff_threshold=self._cache_threshold, **self._prompt_kwargs())
-                # sanitise / quantise where the tensor lives (on the GPU these are microseconds; on the host 100 ms of fp32 passes
-                # over 3 MP) and download the uint8 HWC image — the same IEEE operations in the same order, so the bytes are identical
-                img = torch.nan_to_num(out.images[0].float(), nan=0.0, posinf=1.0, neginf=0.0).clamp_(0, 1)
-                patch = Image.fromarray(img.mul(255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy())
-        patch = patch.resize((w, h), Image.Resampling.LANCZOS)
-        if key is not None:
-            self.cache.set_inpainted_image(key, patch)
-        page = np.asarray(image_pil)
-        return Image.fromarray(composite_u8(page, np.asarray(patch), alpha, x, y))
+            patch = tail.resize(patch, (w, h), "lanczos") if tail is not None else patch.resize((w, h), Image.Resampling.LANCZOS)
+            if key is not None:
+                self.cache.set_inpainted_image(key, patch if tail is None else Image.fromarray(patch.cpu().numpy()))
+        if tail is not None:
+            return self._composite_on_device(tail, image_pil, patch, torch.from_numpy(np.ascontiguousarray(alpha, dtype=np.float32)).to(tail.device), x, y)
+        return Image.fromarray(composite_u8(np.asarray(image_pil), np.asarray(patch), alpha, x, y))
 
-    device_tail = True          # False: the host path (PIL / numpy), the reference's own arithmetic
+    def _unavailable_warning(self) -> str:
+        return "Warning: Flux Kontext pipeline not available. Skipping inpainting."
 
-    def _device_tail(self):
-        """the DeviceTail of the pipeline's device, or None (host path): needs a loaded pipeline made of libmtx_hip graphs"""
-        if not self.device_tail:
-            return None
-        t = getattr(self, "_tail", None)
-        if t is not None:
-            return t
-        self.load_models()
-        pipe = self.pipeline
-        lib = getattr(getattr(pipe, "transformer", None), "lib", None)
-        if pipe is None or lib is None or not hasattr(pipe, "device"):
-            return None
-        from .device_tail import get_device_tail
-        self._tail = get_device_tail(lib, pipe.device)
-        return self._tail
+    def _run_pipeline(self, image, inf_w, inf_h, gen):
+        out = self.pipeline(image=image, width=inf_w, height=inf_h, num_inference_steps=self.num_inference_steps,
+                            guidance_scale=self.guidance_scale, generator=gen, output_type="pt",
+                            max_area=inf_w * inf_h, residual_diff_threshold=self._cache_threshold, **self._prompt_kwargs())
+        # sanitise / quantise where the tensor lives (on the GPU these are microseconds; on the host 100 ms of fp32 passes
+        # over 3 MP) and download the uint8 HWC image — the same IEEE operations in the same order, so the bytes are identical
+        img = torch.nan_to_num(out.images[0].float(), nan=0.0, posinf=1.0, neginf=0.0).clamp_(0, 1)
+        patch = img.mul(255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
+        return patch if torch.is_tensor(image) else Image.fromarray(patch.cpu().numpy())
 
     def _fp8_linears(self) -> bool:
         """whether the DiT's block linears run on the MX fp8 path: what the loaded pipeline was built with, else what the manager would build"""
         dit = getattr(self.pipeline, "transformer", None)
         return bool(dit.fp8) if hasattr(dit, "fp8") else bool(getattr(self.manager, "flux_kontext_fp8", False))
 
-    def _memo_key(self, crop, mask_crop, seed, bbox, padding, blur, ocr_params, strict_mask_clipping, composite_clip_bbox):
-        """Key of the crop-sized patch in the stage memo (reference :781-827): crop pixels, a <= 64x64 bilinear signature of the mask
-        (robust to one-pixel jitter of the detections), sampler settings and crop geometry.  None when seed == -1 (fresh noise)."""
-        if not self.cache.should_use_inpaint_cache(seed):
-            return None
-        params = {"bbox": tuple(int(v) for v in bbox), "padding": int(padding), "blur": int(blur), "backend": self.backend}
-        if self.backend == "sdcpp":
-            params.update(sdcpp_cache=self.sdcpp_cache_mode, sdcpp_diffusion_quant=self.sdcpp_diffusion_quant,
-                          sdcpp_text_encoder_quant=self.sdcpp_text_encoder_quant)
-        if self._fp8_linears():                 # this package only (absent = the reference's key): a patch made by the fp8 graph is not served to the bf16 one
-            params["arithmetic"] = "fp8"
-        if strict_mask_clipping:
-            params["strict_clip"] = True
-        if composite_clip_bbox is not None:
-            params["clip_bbox"] = tuple(composite_clip_bbox)
-        if ocr_params:
-            params.update(ocr_params)
-        signature = mask_crop
-        if mask_crop.size > 0:
-            size = (min(64, max(4, mask_crop.shape[0])), min(64, max(4, mask_crop.shape[1])))
-            small = torch.nn.functional.interpolate(torch.from_numpy(mask_crop.astype(np.float32))[None, None], size=size, mode="bilinear", align_corners=False)
-            signature = (small > 0.5).numpy().astype(np.uint8)[0, 0]
-        return self.cache.get_inpaint_cache_key(crop, signature, seed, self.num_inference_steps, self.residual_diff_threshold,
-                                                self.guidance_scale, self.prompt, params)
+    def _memo_own(self):
+        # the arithmetic tag is this package's only (absent = the reference's key): a patch made by the fp8 graph is not served to the bf16 one
+        return ({"arithmetic": "fp8"} if self._fp8_linears() else {}), (self.residual_diff_threshold, self.guidance_scale, self.prompt)
 
     def _prompt_kwargs(self) -> dict:
         enc = getattr(self.pipeline, "encode_prompt", None)
@@ -414,7 +456,7 @@ SDCPP_DIFFUSION_QUANT_DEFAULT = "Q4_K_M"              # reference utils/model_me
 SDCPP_KLEIN_TEXT_ENCODER_QUANT_DEFAULT = "Q4_K_XL"    # ... ["llm"]["default"] (flux_klein_4b and flux_klein_9b alike)
 
 
-class FluxKleinInpainter:
+class FluxKleinInpainter(_FluxInpainter):
     """Same constructor, attributes and operator surface as the reference class (core/image/inpainting.py:980-1068, 1070-1103,
     1350-1665).  `backend` ("sdnq" / "sdcpp") and the sd.cpp quantisation names are accepted and carried into the stage-memo key,
     but every backend is served by the one MI355X graph pair `ModelManager.load_flux_klein_4b() / _9b()` builds (core/ml/flux2.py)."""
@@ -599,143 +641,62 @@ class FluxKleinInpainter:
         mask_crop = mask[y:y + h, x:x + w]
         key = self._memo_key(crop, mask_crop, seed, (x, y, w, h), padding, blur, ocr_params, strict_mask_clipping, composite_clip_bbox)
         patch = self.cache.get_inpainted_image(key) if key is not None else None
+        clip_rect = self._clip_rect(composite_clip_bbox, (img_w, img_h), (x, y, w, h))
+        # on the device the whole chain around the pipeline stays in HBM (core/image/device_tail.py): the feather weight from the mask (exact EDT
+        # in a window of the blur radius), LANCZOS to the inference size, the pipeline, LANCZOS back, the luminance match and the
+        # composite — weight, resize and composite bit for bit, the Lab leg within a level; translucent crops: the host path
+        tail = self._device_tail() if patch is None and _opaque_for_device_resize(crop) else None
         if patch is not None:
             log_message("  - Using cached inpainting patch", verbose=verbose)
-        clip_rect = None                                   # composite_clip_bbox in crop coordinates
-        if composite_clip_bbox is not None:
-            cx1, cy1, cx2, cy2 = composite_clip_bbox
-            cx1, cx2 = max(0, min(img_w, cx1)), max(0, min(img_w, cx2))
-            cy1, cy2 = max(0, min(img_h, cy1)), max(0, min(img_h, cy2))
-            clip_rect = (max(0, cx1 - x), max(0, cy1 - y), min(w, cx2 - x), min(h, cy2 - y))
-        generated_now = patch is None
-        tail = self._device_tail() if patch is None and _opaque_for_device_resize(crop) else None     # translucent crops: the host path
-        if tail is not None:
-            # the whole chain around the pipeline stays in HBM (core/image/device_tail.py): the feather weight from the mask (exact EDT in
-            # a window of the blur radius), LANCZOS to the inference size, the pipeline, LANCZOS back, the luminance match and the
-            # composite — weight, resize and composite bit for bit, the Lab leg within a level
-            result, patch = self._inpaint_on_device(tail, image_pil, crop, mask_crop, (blur, strict_mask_clipping, clip_rect), x, y, w, h, seed,
-                                                    verbose)
-            if result is None:
+        else:
+            inf_w, inf_h = self._inference_size(w, h)
+            if tail is not None:
+                mask_dev = torch.from_numpy(np.ascontiguousarray(mask_crop, dtype=np.uint8)).to(tail.device)
+                crop_dev = self._upload_rgb(tail, crop)
+                if (inf_w, inf_h) != (w, h):
+                    log_message(f"  - Scaling {w}x{h} -> {inf_w}x{inf_h}", verbose=verbose)
+                scaled = tail.resize(crop_dev, (inf_w, inf_h), "lanczos")
+            else:
+                scaled, _, _ = self._prepare_image_for_inference(crop, verbose=verbose)
+                if scaled.mode == "RGBA":
+                    scaled = scaled.convert("RGB")
+            log_message("  - Running inference...", verbose=verbose)
+            patch = self._generate(scaled, inf_w, inf_h, seed)
+            if patch is None:
                 return image_pil
+            if tail is not None:
+                patch = tail.resize(patch, (w, h), "lanczos")
+                if self.luminance_correction:
+                    patch = tail.match_luminance(patch, crop_dev, mask_dev, log=lambda m: log_message(m, verbose=verbose))
+            else:
+                patch = patch.resize((w, h), Image.Resampling.LANCZOS)
+                if self.luminance_correction:
+                    patch = self._match_luminance(patch, crop, mask_crop, verbose=verbose)
             if key is not None:
-                self.cache.set_inpainted_image(key, patch)
-            return result
+                self.cache.set_inpainted_image(key, patch if tail is None else Image.fromarray(patch.cpu().numpy()))
+        if tail is not None:
+            return self._composite_on_device(tail, image_pil, patch, tail.feather(mask_dev, blur, strict_mask_clipping, clip_rect), x, y)
         alpha = self._crop_alpha(mask_crop, blur)
         if strict_mask_clipping:
             alpha = alpha * mask_crop.astype(np.float32)
-        if clip_rect is not None:
-            ax0, ay0, ax1, ay1 = clip_rect
-            keep = np.zeros_like(alpha)
-            if ax1 > ax0 and ay1 > ay0:
-                keep[ay0:ay1, ax0:ax1] = alpha[ay0:ay1, ax0:ax1]
-            alpha = keep
-        if patch is None:
-            scaled, _, _ = self._prepare_image_for_inference(crop, verbose=verbose)
-            inf_w, inf_h = scaled.size
-            if scaled.mode == "RGBA":
-                scaled = scaled.convert("RGB")
-            log_message("  - Running inference...", verbose=verbose)
-            with self.manager.flux_inference_lock:
-                self.load_models()
-                if self.pipeline is None:
-                    log_message(f"Warning: Flux Klein {self.variant.upper()} pipeline unavailable.", always_print=True)
-                    return image_pil
-                with torch.inference_mode():
-                    # the reference seeds a generator on ITS device (:1568), so its noise comes from that backend's Philox stream; this
-                    # pipeline draws the initial latents on the host (bit-stable across boxes and ranks).  Same seed -> same noise within
-                    # either implementation, never across them: pixel parity with a checkpoint is judged on the SAME latents (the
-                    # pipelines accept `latents=`, which the parity tests use)
-                    gen = torch.Generator(device="cpu").manual_seed(seed)
-                    out = self.pipeline(**self._prompt_kwargs(), image=scaled, height=inf_h, width=inf_w,
-                                        guidance_scale=self.KLEIN_GUIDANCE_SCALE, num_inference_steps=self.num_inference_steps,
-                                        generator=gen)
-                    patch = out.images[0]
-            if (inf_w, inf_h) != (w, h):
-                patch = patch.resize((w, h), Image.Resampling.LANCZOS)
-            if self.luminance_correction:
-                patch = self._match_luminance(patch, crop, mask_crop, verbose=verbose)
-        result = Image.fromarray(composite_u8(np.asarray(image_pil), np.asarray(patch), alpha, x, y))
-        if generated_now and key is not None:
-            self.cache.set_inpainted_image(key, patch)
-        return result
+        return Image.fromarray(composite_u8(np.asarray(image_pil), np.asarray(patch), self._clip_weight(alpha, clip_rect), x, y))
 
-    # ---- the same operator with the image arithmetic on the device ------------------------------------------------------------
-    device_tail = True          # False: the host path (PIL / numpy), the reference's own arithmetic
+    def _unavailable_warning(self) -> str:
+        return f"Warning: Flux Klein {self.variant.upper()} pipeline unavailable."
 
-    def _device_tail(self):
-        """the DeviceTail of this inpainter's device, or None (host path): needs a pipeline that lives on a GPU (or the test simulator)
-        and takes / returns device tensors, and an RGB crop"""
-        if not self.device_tail:
-            return None
-        t = getattr(self, "_tail", None)
-        if t is not None:
-            return t
-        self.load_models()
-        pipe = self.pipeline
-        lib = getattr(getattr(pipe, "transformer", None), "lib", None)
-        if pipe is None or lib is None or not hasattr(pipe, "device"):
-            return None
-        from .device_tail import get_device_tail
-        self._tail = get_device_tail(lib, pipe.device)
-        return self._tail
+    def _run_pipeline(self, image, inf_w, inf_h, gen):
+        on_device = torch.is_tensor(image)
+        out = self.pipeline(**self._prompt_kwargs(), image=image, height=inf_h, width=inf_w, guidance_scale=self.KLEIN_GUIDANCE_SCALE,
+                            num_inference_steps=self.num_inference_steps, generator=gen, **({"output_type": "pt"} if on_device else {}))
+        patch = out.images[0]
+        if on_device:
+            patch = patch.mul(255).round().to(torch.uint8).permute(1, 2, 0).contiguous()       # what the "pil" output type holds
+        return patch
 
-    def _inpaint_on_device(self, tail, image_pil, crop, mask_crop, feather, x, y, w, h, seed, verbose):
-        """`feather` = (blur, strict, clip rectangle in crop coordinates or None): what the composite weight is made from"""
-        dev = tail.device
-        mask_dev = torch.from_numpy(np.ascontiguousarray(mask_crop, dtype=np.uint8)).to(dev)
-        crop_rgb = crop if crop.mode == "RGB" else crop.convert("RGB")
-        crop_dev = torch.from_numpy(np.array(crop_rgb)).to(dev)
-        inf_w, inf_h = self._inference_size(w, h)
-        if (inf_w, inf_h) != (w, h):
-            log_message(f"  - Scaling {w}x{h} -> {inf_w}x{inf_h}", verbose=verbose)
-        scaled = tail.resize(crop_dev, (inf_w, inf_h), "lanczos")
-        log_message("  - Running inference...", verbose=verbose)
-        with self.manager.flux_inference_lock:
-            self.load_models()
-            if self.pipeline is None:
-                log_message(f"Warning: Flux Klein {self.variant.upper()} pipeline unavailable.", always_print=True)
-                return None, None
-            with torch.inference_mode():
-                gen = torch.Generator(device="cpu").manual_seed(seed)
-                out = self.pipeline(**self._prompt_kwargs(), image=scaled, height=inf_h, width=inf_w, guidance_scale=self.KLEIN_GUIDANCE_SCALE,
-                                    num_inference_steps=self.num_inference_steps, generator=gen, output_type="pt").images[0]
-                patch = out.mul(255).round().to(torch.uint8).permute(1, 2, 0).contiguous()       # what the "pil" output type holds
-        if (inf_w, inf_h) != (w, h):
-            patch = tail.resize(patch, (w, h), "lanczos")
-        if self.luminance_correction:
-            patch = tail.match_luminance(patch, crop_dev, mask_dev, log=lambda m: log_message(m, verbose=verbose))
-        page = torch.from_numpy(np.array(image_pil)).to(dev)          # a copy: the composite is in place
-        if page.dim() == 2:
-            page = page[..., None]
-        blur, strict, clip_rect = feather
-        tail.composite(page.contiguous(), patch, tail.feather(mask_dev, blur, strict, clip_rect), x, y)
-        out_np = page.cpu().numpy()
-        result = Image.fromarray(out_np[..., 0] if out_np.shape[2] == 1 else out_np, image_pil.mode)
-        return result, Image.fromarray(patch.cpu().numpy())
-
-    def _memo_key(self, crop, mask_crop, seed, bbox, padding, blur, ocr_params, strict_mask_clipping, composite_clip_bbox):
-        """stage-memo key of the crop-sized patch (reference :1433-1489); None when seed == -1"""
-        if not self.cache.should_use_inpaint_cache(seed):
-            return None
-        params = {"bbox": tuple(int(v) for v in bbox), "padding": padding, "blur": blur, "variant": self.variant,
-                  "lum_corr": self.luminance_correction, "upscale_small": self.upscale_small_crops,
-                  "max_pixels": self.MAX_INFERENCE_PIXELS, "min_size": (self.MIN_RESOLUTION, self.MIN_RESOLUTION), "backend": self.backend}
-        if self.backend == "sdcpp":
-            params.update(sdcpp_cache=self.sdcpp_cache_mode, sdcpp_diffusion_quant=self.sdcpp_diffusion_quant,
-                          sdcpp_text_encoder_quant=self.sdcpp_text_encoder_quant)
-        if strict_mask_clipping:
-            params["strict_clip"] = True
-        if composite_clip_bbox is not None:
-            params["clip_bbox"] = tuple(composite_clip_bbox)
-        if ocr_params:
-            params.update(ocr_params)
-        signature = mask_crop
-        if mask_crop.size > 0:
-            size = (min(64, max(4, mask_crop.shape[0])), min(64, max(4, mask_crop.shape[1])))
-            small = torch.nn.functional.interpolate(torch.from_numpy(mask_crop.astype(np.float32))[None, None], size=size, mode="bilinear", align_corners=False)
-            signature = (small > 0.5).numpy().astype(np.uint8)[0, 0]
-        return self.cache.get_inpaint_cache_key(crop, signature, seed, self.num_inference_steps, 0.0, self.KLEIN_GUIDANCE_SCALE,
-                                                self.KLEIN_PROMPT, params)
+    def _memo_own(self):
+        return ({"variant": self.variant, "lum_corr": self.luminance_correction, "upscale_small": self.upscale_small_crops,
+                 "max_pixels": self.MAX_INFERENCE_PIXELS, "min_size": (self.MIN_RESOLUTION, self.MIN_RESOLUTION)},
+                (0.0, self.KLEIN_GUIDANCE_SCALE, self.KLEIN_PROMPT))
 
     def _prompt_kwargs(self) -> dict:
         enc = getattr(self.pipeline, "encode_prompt", None)

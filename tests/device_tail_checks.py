@@ -137,87 +137,99 @@ class StandInPipeline:
         return types.SimpleNamespace(images=[Image.fromarray(u8.cpu().numpy())])
 
 
-def check_klein_operator(lib, page_hw=(300, 400), mask_box=(120, 150, 200, 260), page_mode="RGB", translucent=False):
-    """`FluxKleinInpainter.inpaint_mask` with its image arithmetic on the device against the SAME operator on the host path (PIL / numpy):
-    same stand-in pipeline, same seed.  Pixels outside the crop identical; inside within one level (the float Lab -> RGB leg); the
-    remembered patch likewise; both LANCZOS passes (crop -> ~1 MP inference size and back), the luminance match and the composite run."""
+# the small operator cases of both tiers: a 200x260 page, an L-shaped mask (two overlapping boxes), plain / strict / a clip rectangle that
+# runs off the page / strict inside a clip rectangle
+SMALL_PAGE_HW = (200, 260)
+SMALL_MASK_BOXES = ((60, 70, 110, 150), (100, 140, 125, 170))
+OPERATOR_CASES = ((False, None), (True, None), (False, (90, 40, 400, 118)), (True, (90, 40, 160, 118)))
+
+
+def _operator_page(page_hw, mask_box, seed):
+    """a smooth RGB page with noise, and the mask: `mask_box` is one (y0, x0, y1, x1) box or several, whose union is masked"""
+    H, W = page_hw
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    page = np.clip(np.stack([140 + 70 * np.sin(xx / 13.0), 130 + 60 * np.cos(yy / 9.0), 120 + 50 * np.sin((xx + 2 * yy) / 17.0)], -1) + rng.normal(0, 5, (H, W, 3)), 0, 255).astype(np.uint8)
+    mask = np.zeros((H, W), bool)
+    for y0, x0, y1, x1 in np.reshape(mask_box, (-1, 4)):
+        mask[y0:y1, x0:x1] = True
+    return page, mask
+
+
+def _stand_in_operator(cls, lib, on_device, **attrs):
+    """an operator built without its constructor (no model manager): a `StandInPipeline`, an empty stage memo, and `attrs`"""
     import threading
     import types
     from mangatranslator_amd.core.caching import get_cache
     dev = _dev(lib)
+    inp = cls.__new__(cls)
+    inp.manager = types.SimpleNamespace(flux_inference_lock=threading.Lock(), device=dev)
+    inp.DEVICE, inp.DTYPE = dev, torch.bfloat16
+    inp.cache = get_cache()
+    inp.cache.reset()
+    inp.pipeline = StandInPipeline(lib, dev)
+    inp.load_models = lambda: None
+    inp.device_tail = on_device
+    for name, value in attrs.items():
+        setattr(inp, name, value)
+    return inp
+
+
+def _inpaint_twice(inp, page_pil, mask, seed, strict, clip):
+    """the page of `inpaint_mask`, and of a second call with the same arguments: the memo hit — the pipeline ran once, the same bytes"""
+    pages = [inp.inpaint_mask(page_pil, mask, seed=seed, strict_mask_clipping=strict, composite_clip_bbox=clip) for _ in range(2)]
+    assert len(inp.pipeline.calls) == 1, f"the pipeline ran {len(inp.pipeline.calls)} times over two identical calls"
+    assert pages[0].mode == pages[1].mode == page_pil.mode
+    first, second = np.asarray(pages[0]), np.asarray(pages[1])
+    assert np.array_equal(first, second), f"{(first != second).sum()} bytes differ between the generating call and the memo hit"
+    return first, second
+
+
+def check_klein_operator(lib, page_hw=(300, 400), mask_box=(120, 150, 200, 260), page_mode="RGB", translucent=False, strict=False, clip=None):
+    """`FluxKleinInpainter.inpaint_mask` with its image arithmetic on the device against the SAME operator on the host path (PIL / numpy):
+    same stand-in pipeline, same seed.  Pixels outside the crop identical; inside within one level (the float Lab -> RGB leg); the
+    remembered patch likewise; both LANCZOS passes (crop -> ~1 MP inference size and back), the luminance match and the composite run.
+    Each instance is called twice: the second call is the memo hit, which composites on the host from `_crop_alpha` on either instance."""
     H, W = page_hw
-    rng = np.random.default_rng(4)
-    yy, xx = np.mgrid[0:H, 0:W]
-    page = np.clip(np.stack([140 + 70 * np.sin(xx / 13.0), 130 + 60 * np.cos(yy / 9.0), 120 + 50 * np.sin((xx + 2 * yy) / 17.0)], -1) + rng.normal(0, 5, (H, W, 3)), 0, 255).astype(np.uint8)
+    page, mask = _operator_page(page_hw, mask_box, seed=4)
     if page_mode == "RGBA":
         page = np.concatenate([page, np.full((H, W, 1), 255, np.uint8)], -1)
         if translucent:          # Pillow resizes RGBA on premultiplied colours: the device path must step aside for such a crop (ADVICE r03)
-            page[mask_box[0] - 10: mask_box[0] + 30, mask_box[1]: mask_box[1] + 50, 3] = 90
-    mask = np.zeros((H, W), bool)
-    y0, x0, y1, x1 = mask_box
-    mask[y0:y1, x0:x1] = True
+            y0, x0 = np.reshape(mask_box, (-1, 4))[0, :2]
+            page[y0 - 10: y0 + 30, x0: x0 + 50, 3] = 90
     outs, pipes = [], []
     for on_device in (True, False):
-        pipe = StandInPipeline(lib, dev)
-        inp = ip.FluxKleinInpainter.__new__(ip.FluxKleinInpainter)
-        inp.variant, inp.backend, inp.num_inference_steps, inp.low_vram = "4b", "sdnq", 1, False
-        inp.luminance_correction, inp.upscale_small_crops, inp.verbose = True, True, False
-        inp.sdcpp_cache_mode, inp.sdcpp_diffusion_quant, inp.sdcpp_text_encoder_quant = "none", "Q4_K_M", "Q4_K_XL"
-        inp.manager = types.SimpleNamespace(flux_inference_lock=threading.Lock(), device=dev)
-        inp.DEVICE, inp.DTYPE, inp.huggingface_token = dev, torch.bfloat16, ""
-        inp.cache = get_cache()
-        inp.cache.reset()
-        inp.pipeline, inp._prompt_embeds = pipe, torch.zeros(4, 8)
-        inp.load_models = lambda: None
-        inp.device_tail = on_device
-        res = inp.inpaint_mask(Image.fromarray(page, page_mode), mask, seed=7)
-        assert res.mode == page_mode
-        outs.append(np.asarray(res))
-        pipes.append(pipe)
+        inp = _stand_in_operator(ip.FluxKleinInpainter, lib, on_device, variant="4b", backend="sdnq", num_inference_steps=1, low_vram=False,
+                                 luminance_correction=True, upscale_small_crops=True, verbose=False, sdcpp_cache_mode="none",
+                                 sdcpp_diffusion_quant="Q4_K_M", sdcpp_text_encoder_quant="Q4_K_XL", huggingface_token="", _prompt_embeds=torch.zeros(4, 8))
+        outs.append(_inpaint_twice(inp, Image.fromarray(page, page_mode), mask, 7, strict, clip))
+        pipes.append(inp.pipeline)
         x, y, w, h, _, _ = inp.region_for_mask(mask)
     if translucent:
-        assert pipes[0].calls[0][0] == "pil" and np.array_equal(outs[0], outs[1]), "a translucent crop must take the host path, byte for byte"
+        assert pipes[0].calls[0][0] == "pil" and np.array_equal(outs[0][0], outs[1][0]), "a translucent crop must take the host path, byte for byte"
         return 0.0, pipes[0].calls[0][1]
     assert pipes[0].calls[0][0] == "pt" and pipes[1].calls[0][0] == "pil" and pipes[0].calls[0][1] == pipes[1].calls[0][1]
-    a, b = outs
-    d = np.abs(a.astype(int) - b.astype(int))
     outside = np.ones((H, W), bool)
     outside[y:y + h, x:x + w] = False
-    assert d[outside].max() == 0 and not np.array_equal(a, page), "pixels outside the crop changed, or nothing was inpainted"
-    assert d.max() <= 1, f"device tail vs host path: max |diff| {d.max()}"
+    for a, b in zip(*outs):                                   # the generating calls, then the memo hits
+        d = np.abs(a.astype(int) - b.astype(int))
+        assert d[outside].max() == 0 and not np.array_equal(a, page), "pixels outside the crop changed, or nothing was inpainted"
+        assert d.max() <= 1, f"device tail vs host path: max |diff| {d.max()}"
+    d = np.abs(outs[0][0].astype(int) - outs[1][0].astype(int))
     return float((d > 0).mean()), pipes[0].calls[0][1]
 
 
-def check_kontext_operator(lib, page_hw=(300, 400), mask_box=(120, 150, 200, 260)):
+def check_kontext_operator(lib, page_hw=(300, 400), mask_box=(120, 150, 200, 260), strict=False, clip=None):
     """`FluxKontextInpainter.inpaint_mask`, device tail vs host path, same stand-in pipeline and seed: no Lab leg here, so the pages must be
-    IDENTICAL (Pillow's LANCZOS both ways and the composite are bit-exact on the device)"""
-    import threading
-    import types
-    from mangatranslator_amd.core.caching import get_cache
-    dev = _dev(lib)
-    H, W = page_hw
-    rng = np.random.default_rng(5)
-    yy, xx = np.mgrid[0:H, 0:W]
-    page = np.clip(np.stack([140 + 70 * np.sin(xx / 13.0), 130 + 60 * np.cos(yy / 9.0), 120 + 50 * np.sin((xx + 2 * yy) / 17.0)], -1) + rng.normal(0, 5, (H, W, 3)), 0, 255).astype(np.uint8)
-    mask = np.zeros((H, W), bool)
-    y0, x0, y1, x1 = mask_box
-    mask[y0:y1, x0:x1] = True
+    IDENTICAL (Pillow's LANCZOS both ways and the composite are bit-exact on the device), on the generating call and on the memo hit"""
+    page, mask = _operator_page(page_hw, mask_box, seed=5)
     outs = []
     for on_device in (True, False):
-        pipe = StandInPipeline(lib, dev)
-        inp = ip.FluxKontextInpainter.__new__(ip.FluxKontextInpainter)
-        inp.PREFERED_KONTEXT_RESOLUTIONS = list(ip.PREFERRED_KONTEXT_RESOLUTIONS)
-        inp.context_padding_ratio, inp.max_context_padding = ip.CONTEXT_PADDING_RATIO, ip.MAX_CONTEXT_PADDING
-        inp.num_inference_steps, inp.guidance_scale, inp.residual_diff_threshold, inp.backend, inp.prompt = 1, 2.5, 0.15, "sdnq", "Remove all text."
-        inp.sdcpp_cache_mode, inp.sdcpp_diffusion_quant, inp.sdcpp_text_encoder_quant = "none", "", ""
-        inp.manager = types.SimpleNamespace(flux_inference_lock=threading.Lock(), device=dev)
-        inp.DEVICE, inp.DTYPE = dev, torch.bfloat16
-        inp.cache = get_cache()
-        inp.cache.reset()
-        inp.pipeline, inp._prompt_embeds, inp._pooled = pipe, None, None
-        inp.load_models = lambda: None
-        inp._prompt_kwargs = lambda: {}
-        inp.device_tail = on_device
-        outs.append(np.asarray(inp.inpaint_mask(Image.fromarray(page), mask, seed=3)))
-    assert not np.array_equal(outs[0], page)
-    assert np.array_equal(outs[0], outs[1]), f"{(outs[0] != outs[1]).sum()} bytes differ between the device tail and the host path"
+        inp = _stand_in_operator(ip.FluxKontextInpainter, lib, on_device, PREFERED_KONTEXT_RESOLUTIONS=list(ip.PREFERRED_KONTEXT_RESOLUTIONS),
+                                 context_padding_ratio=ip.CONTEXT_PADDING_RATIO, max_context_padding=ip.MAX_CONTEXT_PADDING, num_inference_steps=1,
+                                 guidance_scale=2.5, residual_diff_threshold=0.15, backend="sdnq", prompt="Remove all text.", sdcpp_cache_mode="none",
+                                 sdcpp_diffusion_quant="", sdcpp_text_encoder_quant="", _prompt_embeds=None, _pooled=None, _prompt_kwargs=lambda: {})
+        outs.append(_inpaint_twice(inp, Image.fromarray(page), mask, 3, strict, clip))
+    for a, b in zip(*outs):
+        assert not np.array_equal(a, page)
+        assert np.array_equal(a, b), f"{(a != b).sum()} bytes differ between the device tail and the host path"

@@ -32,5 +32,15 @@ def test_klein_operator_on_the_device_tail(hip_lib):
     dc.check_klein_operator(hip_lib, page_hw=(700, 500), mask_box=(200, 100, 380, 330), page_mode="RGBA")
 
 
+@pytest.mark.parametrize("strict, clip", dc.OPERATOR_CASES)
+def test_klein_operator_strict_clip_and_memo_hit(hip_lib, strict, clip):
+    dc.check_klein_operator(hip_lib, page_hw=dc.SMALL_PAGE_HW, mask_box=dc.SMALL_MASK_BOXES, strict=strict, clip=clip)
+
+
 def test_kontext_operator_on_the_device_tail(hip_lib):
     dc.check_kontext_operator(hip_lib, page_hw=(1536, 1024), mask_box=(600, 300, 900, 700))
+
+
+@pytest.mark.parametrize("strict, clip", dc.OPERATOR_CASES)
+def test_kontext_operator_strict_clip_and_memo_hit(hip_lib, strict, clip):
+    dc.check_kontext_operator(hip_lib, page_hw=dc.SMALL_PAGE_HW, mask_box=dc.SMALL_MASK_BOXES, strict=strict, clip=clip)

@@ -1,5 +1,6 @@
 """CPU tier: the page-tail kernels on the simulator against Pillow / numpy (see device_tail_checks.py)."""
 import numpy as np
+import pytest
 from PIL import Image
 
 import device_tail_checks as dc
@@ -72,6 +73,12 @@ def test_klein_operator_on_the_device_tail(emu_lib):
     dc.check_klein_operator(emu_lib, page_hw=(200, 260), mask_box=(60, 70, 110, 150), page_mode="RGBA", translucent=True)
 
 
+@pytest.mark.parametrize("strict, clip", dc.OPERATOR_CASES)
+def test_klein_operator_strict_clip_and_memo_hit(emu_lib, strict, clip):
+    """strict clipping, a clip rectangle (one that runs off the page) and the second, remembered call on an L-shaped mask"""
+    dc.check_klein_operator(emu_lib, page_hw=dc.SMALL_PAGE_HW, mask_box=dc.SMALL_MASK_BOXES, strict=strict, clip=clip)
+
+
 def test_unload_drops_the_device_tail():
     """`unload_models()` left `_tail` behind, and the next call used a pipeline that was None"""
     import types
@@ -86,3 +93,8 @@ def test_unload_drops_the_device_tail():
 
 def test_kontext_operator_on_the_device_tail(emu_lib):
     dc.check_kontext_operator(emu_lib)
+
+
+@pytest.mark.parametrize("strict, clip", dc.OPERATOR_CASES)
+def test_kontext_operator_strict_clip_and_memo_hit(emu_lib, strict, clip):
+    dc.check_kontext_operator(emu_lib, page_hw=dc.SMALL_PAGE_HW, mask_box=dc.SMALL_MASK_BOXES, strict=strict, clip=clip)

@@ -250,6 +250,15 @@ constexpr int AB_KV = 64;
 #endif
 constexpr int AB_QB = 256;
 
+// The last tile of a ragged sequence: keys >= kvalid do not exist.  sacc[kb][r] is key 32*kb + (r&3) + 8*(r>>2) + 4*hi of the tile.
+__device__ __forceinline__ void attn_mask_ragged(f32x16 (&sacc)[2], const long kvalid, const int hi) {
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kvalid) sacc[kb][r] = -1.0e30f;
+}
+
 // One K/V tile of the main loop.  STAGE is a compile-time constant so every LDS address is
 // (loop-invariant VGPR) + (immediate offset).
 template <typename T, int DP, int STAGE, bool RAGGED>
@@ -273,13 +282,7 @@ __device__ __forceinline__ void attn_mma32_tile(unsigned char* smem, const typen
       sacc[kb] = Mma32<T>::mfma(kf, qf[ks], ks == 0 ? zero : sacc[kb]);
     }
 
-  if (RAGGED) {                                // last tile of a ragged sequence: keys >= kvalid do not exist
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kvalid) sacc[kb][r] = -1.0e30f;
-  }
+  if (RAGGED) attn_mask_ragged(sacc, kvalid, hi);
   float tmax = fmaxf(sacc[0][0], sacc[1][0]);
 #pragma unroll
   for (int r = 1; r < 16; ++r) tmax = fmaxf(fmaxf(tmax, sacc[0][r]), sacc[1][r]);
@@ -327,7 +330,7 @@ __device__ __forceinline__ void attn_mma32_tile(unsigned char* smem, const typen
 // s*c - M directly and the softmax needs no per-score fused multiply-add: exp2 straight from the accumulator (32 VALU issue slots
 // per wave and tile saved out of ~135).  `M` is in log2 units; the first tile always refreshes (M starts at 0, not -inf, so the
 // accumulation keeps its precision).
-// NOMAX: the row maximum is not computed on the hot path at all.  With M folded into the accumulator the only thing a stale M can
+// The row maximum is not computed on the hot path at all.  With M folded into the accumulator the only thing a stale M can
 // do is let exp2 grow large, and fp32 / bf16 keep their relative precision while it does; the tile's partial row sums (which are
 // needed anyway) flag the danger zone (> 2^40, inf or nan), and only then — and on the first tile — the exact maximum is taken and
 // the tile's probabilities are recomputed.
@@ -339,9 +342,32 @@ template <> struct AttnSumLimit<_Float16> { static constexpr float v = 3.0e4f; }
 #else
 #define MTX_SCHED_GROUP(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 #endif
+// The exact path of the three bias-family tile steps: takes the tile's row maximum (relative to M, the accumulators started at -M), moves M
+// by `delta`, rescales the row sum and O^T, and refills `minit` for the next tile's accumulators.  The first tile sets M to its own maximum
+// (may be negative); later ones only raise it.  The caller recomputes the tile's probabilities from sacc - delta and clears `first`.
+template <int DB>
+__device__ __forceinline__ float attn_refresh_max(const f32x16 (&sacc)[2], f32x16 (&oacc)[DB], float& M, float& lsum, f32x16& minit, const bool first) {
+  float tmax = fmaxf(sacc[0][0], sacc[1][0]);
+#pragma unroll
+  for (int r = 1; r < 16; ++r) tmax = fmaxf(fmaxf(tmax, sacc[0][r]), sacc[1][r]);
+  tmax = half_max(tmax);
+  const float delta = first ? tmax : fmaxf(tmax, 0.f);
+  const float alpha = fast_exp2(-delta);
+  M += delta;
+  lsum *= alpha;
+#pragma unroll
+  for (int d = 0; d < DB; ++d)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) minit[r] = -M;
+  return delta;
+}
 // DEEP (round 5, schedule 68; measured against the plain form in one process): the K fragments of four k-steps and the V^T fragments of four
 // MFMAs are in flight ahead of the matrix pipe, the order pinned with sched_group_barrier (0x100 = LDS reads, 0x008 = MFMA)
-template <typename T, int DP, int STAGE, bool RAGGED, bool NOMAX = false, int DEEP = 0>      // DEEP = 0, or K k-steps ahead | V MFMAs ahead << 4
+// The deep-prefetch P V block below (vfd through the sched_group_barrier sequence) is repeated in attn_bias_tile_k8: sharing it was tried and
+// moved the schedule of attn_mma32_d / _q8d / _k8 / _k8q for both dtypes (docs/experiments.md).
+template <typename T, int DP, int STAGE, bool RAGGED, int DEEP = 0>      // DEEP = 0, or K k-steps ahead | V MFMAs ahead << 4
 __device__ __forceinline__ void attn_bias_tile(unsigned char* smem, const typename Traits<T>::v8 (&qf)[DP / 16], f32x16 (&oacc)[DP / 32],
                                                float& M, float& lsum, f32x16& minit, bool& first,
                                                const int (&kaddr)[DP / 16], const int (&vaddr)[DP / 32], const long kvalid, const int hi) {
@@ -378,82 +404,31 @@ __device__ __forceinline__ void attn_bias_tile(unsigned char* smem, const typena
       else sacc[kb] = Mma32<T>::mfma(kf, qf[ks], sacc[kb]);
     }
   }
-  if (RAGGED) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kvalid) sacc[kb][r] = -1.0e30f;
-  }
+  if (RAGGED) attn_mask_ragged(sacc, kvalid, hi);
   v8 pb[2][2];
-  if (!NOMAX) {
-    float tmax = fmaxf(sacc[0][0], sacc[1][0]);       // relative to M
+  float tsum = 0.f;
 #pragma unroll
-    for (int r = 1; r < 16; ++r) tmax = fmaxf(fmaxf(tmax, sacc[0][r]), sacc[1][r]);
-    tmax = half_max(tmax);
-    if (first || __any(tmax > 8.0f)) {
-      const float delta = first ? tmax : fmaxf(tmax, 0.f);     // the first tile sets M to its own maximum (may be negative)
-      const float alpha = fast_exp2(-delta);
-      M += delta;
-      lsum *= alpha;
+  for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) minit[r] = -M;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sacc[kb][r] -= delta;
-      first = false;
+    for (int r = 0; r < 16; ++r) {
+      const float pv = fast_exp2(sacc[kb][r]);
+      tsum += pv;
+      pb[kb][r >> 3][r & 7] = from_f32<T>(pv);
     }
+  if (first || __any(!(tsum < AttnSumLimit<T>::v))) {          // far from overflow of T / fp32, catches inf / nan as well
+    const float delta = attn_refresh_max<DB>(sacc, oacc, M, lsum, minit, first);
+    tsum = 0.f;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pv = fast_exp2(sacc[kb][r]);
-        lsum += pv;
-        pb[kb][r >> 3][r & 7] = from_f32<T>(pv);
-      }
-  } else {
-    float tsum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = fast_exp2(sacc[kb][r]);
+        const float pv = fast_exp2(sacc[kb][r] - delta);
         tsum += pv;
         pb[kb][r >> 3][r & 7] = from_f32<T>(pv);
       }
-    if (first || __any(!(tsum < AttnSumLimit<T>::v))) {          // far from overflow of T / fp32, catches inf / nan as well
-      float tmax = fmaxf(sacc[0][0], sacc[1][0]);
-#pragma unroll
-      for (int r = 1; r < 16; ++r) tmax = fmaxf(fmaxf(tmax, sacc[0][r]), sacc[1][r]);
-      tmax = half_max(tmax);
-      const float delta = first ? tmax : fmaxf(tmax, 0.f);
-      const float alpha = fast_exp2(-delta);
-      M += delta;
-      lsum *= alpha;
-#pragma unroll
-      for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) minit[r] = -M;
-      tsum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = fast_exp2(sacc[kb][r] - delta);
-          tsum += pv;
-          pb[kb][r >> 3][r & 7] = from_f32<T>(pv);
-        }
-      first = false;
-    }
-    lsum += tsum;
+    first = false;
   }
+  lsum += tsum;
   if constexpr (DEEP) {
     v8 vfd[4][DB];
 #pragma unroll
@@ -493,7 +468,7 @@ __device__ __forceinline__ void attn_bias_tile(unsigned char* smem, const typena
         oacc[d] = Mma32<T>::mfma(vf, pb[kb][s2], oacc[d]);
       }
 }
-// The fp8-score form of attn_bias_tile<.., NOMAX = true, DEEP> (round 6): S^T = K Q^T from plain e4m3 rows on v_mfma_scale_f32_32x32x64_f8f6f4 —
+// The fp8-score form of attn_bias_tile<.., DEEP> (round 6): S^T = K Q^T from plain e4m3 rows on v_mfma_scale_f32_32x32x64_f8f6f4 —
 // two k-steps of 64 instead of eight of 16, at twice the rate per k — block scales 2^0 (K) and 2^qk_f8_exp (Q).  Softmax and P V as above.
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 __device__ __forceinline__ f32x16 mfma_f8_scores(i32x8 a, i32x8 b, f32x16 c, int sb) {
@@ -527,13 +502,7 @@ __device__ __forceinline__ void attn_bias_tile_k8(unsigned char* smem, const i32
     MTX_SCHED_GROUP(0x100, 8);
     MTX_SCHED_GROUP(0x008, 4);
   }
-  if (RAGGED) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kvalid) sacc[kb][r] = -1.0e30f;
-  }
+  if (RAGGED) attn_mask_ragged(sacc, kvalid, hi);
   v8 pb[2][2];
   float tsum = 0.f;
 #pragma unroll
@@ -545,20 +514,7 @@ __device__ __forceinline__ void attn_bias_tile_k8(unsigned char* smem, const i32
       pb[kb][r >> 3][r & 7] = from_f32<T>(pv);
     }
   if (first || __any(!(tsum < AttnSumLimit<T>::v))) {
-    float tmax = fmaxf(sacc[0][0], sacc[1][0]);
-#pragma unroll
-    for (int r = 1; r < 16; ++r) tmax = fmaxf(fmaxf(tmax, sacc[0][r]), sacc[1][r]);
-    tmax = half_max(tmax);
-    const float delta = first ? tmax : fmaxf(tmax, 0.f);
-    const float alpha = fast_exp2(-delta);
-    M += delta;
-    lsum *= alpha;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) minit[r] = -M;
+    const float delta = attn_refresh_max<DB>(sacc, oacc, M, lsum, minit, first);
     tsum = 0.f;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
@@ -622,13 +578,7 @@ __device__ __forceinline__ void attn_bias_tile_k8v8(unsigned char* smem, const i
     MTX_SCHED_GROUP(0x100, 8);
     MTX_SCHED_GROUP(0x008, 4);
   }
-  if (RAGGED) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= kvalid) sacc[kb][r] = -1.0e30f;
-  }
+  if (RAGGED) attn_mask_ragged(sacc, kvalid, hi);
   float pv[2][16];
   float tsum = 0.f;
 #pragma unroll
@@ -636,20 +586,7 @@ __device__ __forceinline__ void attn_bias_tile_k8v8(unsigned char* smem, const i
 #pragma unroll
     for (int r = 0; r < 16; ++r) { pv[kb][r] = fast_exp2(sacc[kb][r]); tsum += pv[kb][r]; }
   if (first || __any(!(tsum < 240.0f))) {
-    float tmax = fmaxf(sacc[0][0], sacc[1][0]);
-#pragma unroll
-    for (int r = 1; r < 16; ++r) tmax = fmaxf(fmaxf(tmax, sacc[0][r]), sacc[1][r]);
-    tmax = half_max(tmax);
-    const float delta = first ? tmax : fmaxf(tmax, 0.f);
-    const float alpha = fast_exp2(-delta);
-    M += delta;
-    lsum *= alpha;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) minit[r] = -M;
+    const float delta = attn_refresh_max<DB>(sacc, oacc, M, lsum, minit, first);
     tsum = 0.f;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
@@ -689,47 +626,59 @@ __device__ __forceinline__ void half_pair_exchange(uint32_t& a, uint32_t& b) {
 #endif
 }
 
+// the seven variants of the long-sequence kernel (table in attn_mma32_body.inc, which undefines all six macros at its end)
 #define ATTN_MMA32_NAME attn_mma32_kernel
 #define ATTN_MMA32_Q8 0
 #define ATTN_MMA32_WIDE 0
+#define ATTN_MMA32_DEEP 0
+#define ATTN_MMA32_K8 0
+#define ATTN_MMA32_V8 0
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#undef ATTN_MMA32_Q8
 #define ATTN_MMA32_NAME attn_mma32_q8_kernel
 #define ATTN_MMA32_Q8 1
+#define ATTN_MMA32_WIDE 0
+#define ATTN_MMA32_DEEP 0
+#define ATTN_MMA32_K8 0
+#define ATTN_MMA32_V8 0
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#define ATTN_MMA32_DEEP 0x44
 #define ATTN_MMA32_NAME attn_mma32_q8d_kernel
+#define ATTN_MMA32_Q8 1
+#define ATTN_MMA32_WIDE 0
+#define ATTN_MMA32_DEEP 0x44
+#define ATTN_MMA32_K8 0
+#define ATTN_MMA32_V8 0
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#undef ATTN_MMA32_Q8
-#undef ATTN_MMA32_WIDE
+#define ATTN_MMA32_NAME attn_mma32_d_kernel
 #define ATTN_MMA32_Q8 0
 #define ATTN_MMA32_WIDE 1
-#define ATTN_MMA32_NAME attn_mma32_d_kernel
+#define ATTN_MMA32_DEEP 0x44
+#define ATTN_MMA32_K8 0
+#define ATTN_MMA32_V8 0
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#define ATTN_MMA32_K8 1
 #define ATTN_MMA32_NAME attn_mma32_k8_kernel
+#define ATTN_MMA32_Q8 0
+#define ATTN_MMA32_WIDE 1
+#define ATTN_MMA32_DEEP 0x44
+#define ATTN_MMA32_K8 1
+#define ATTN_MMA32_V8 0
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#undef ATTN_MMA32_WIDE
-#undef ATTN_MMA32_Q8
-#define ATTN_MMA32_Q8 1
 #define ATTN_MMA32_NAME attn_mma32_k8q_kernel
+#define ATTN_MMA32_Q8 1
+#define ATTN_MMA32_WIDE 0
+#define ATTN_MMA32_DEEP 0x44
+#define ATTN_MMA32_K8 1
+#define ATTN_MMA32_V8 0
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#define ATTN_MMA32_V8 1
 #define ATTN_MMA32_NAME attn_mma32_k8v8q_kernel
+#define ATTN_MMA32_Q8 1
+#define ATTN_MMA32_WIDE 0
+#define ATTN_MMA32_DEEP 0x44
+#define ATTN_MMA32_K8 1
+#define ATTN_MMA32_V8 1
 #include "attn_mma32_body.inc"
-#undef ATTN_MMA32_NAME
-#undef ATTN_MMA32_V8
-#undef ATTN_MMA32_K8
-#undef ATTN_MMA32_DEEP
-#undef ATTN_MMA32_Q8
 
 // merges the `split` key-range partials of every tail query block: O = sum_i 2^((m_i - M) c) O_i / sum_i 2^((m_i - M) c) l_i
+// (the weighted sum is repeated in attn_merge_q8_kernel: sharing it was tried and moved the code of both kernels, docs/experiments.md)
 template <typename T, int DP>
 __global__ __launch_bounds__(256) void attn_merge_kernel(AttnParams p) {
   constexpr unsigned BANDS = AB_QB / 32;

@@ -1,22 +1,28 @@
-// attn_mma32_body.inc — the long-sequence attention kernel, included twice by attention.hip: as attn_mma32_kernel (16-bit output;
-// ATTN_MMA32_Q8 0 — token for token the kernel as it was tuned and measured) and as attn_mma32_q8_kernel (ATTN_MMA32_Q8 1: the rows leave
-// as the MX fp8 operand of the next linear, mtx_attn_args.q8).  An include rather than a template flag or a shared device function on
-// purpose: both of those changed the register allocation and the schedule of the 16-bit kernel (5 % of its instruction sequence moved,
-// compared with `hipcc -S`), and that kernel is 30 % of a page's GPU time.
-// Round 5 adds inclusions on the same principle (the measured kernel's tokens do not move): ATTN_MMA32_WIDE 1 — the 16-bit rows leave as
-// 8 x 16-byte stores per lane instead of 16 x 8-byte ones — and ATTN_MMA32_DEEP — fragment reads four steps ahead of the MFMAs.
-// Round 6: ATTN_MMA32_K8 1 — the scores come from plain e4m3 copies of q and k (mtx_attn_args.q_f8 / k_f8) on the MX-scaled fp8 matrix
-// instruction: four MFMAs of K = 64 per tile instead of sixteen of K = 16; a K tile is 8 KiB of LDS.  PRESCALED only.
+// attn_mma32_body.inc — the long-sequence attention kernel, stamped by attention.hip once per variant:
+//
+//   kernel                     Q8  WIDE  DEEP  K8  V8
+//   attn_mma32_kernel           0    0     0    0   0     token for token the kernel as it was first tuned and measured
+//   attn_mma32_q8_kernel        1    0     0    0   0
+//   attn_mma32_q8d_kernel       1    0   0x44   0   0
+//   attn_mma32_d_kernel         0    1   0x44   0   0     the FLUX graphs' form
+//   attn_mma32_k8_kernel        0    1   0x44   1   0
+//   attn_mma32_k8q_kernel       1    0   0x44   1   0
+//   attn_mma32_k8v8q_kernel     1    0   0x44   1   1
+//
+// ATTN_MMA32_NAME and all five switches are defined by the includer before every inclusion and undefined at the end of this file.
+//   Q8    the rows leave as the MX fp8 operand of the next linear (mtx_attn_args.q8) instead of 16-bit rows
+//   WIDE  the 16-bit rows leave as 8 x 16-byte stores per lane instead of 16 x 8-byte ones (not read when Q8 is set)
+//   DEEP  fragment reads ahead of the MFMAs in the pre-scaled tile step: K k-steps ahead | V MFMAs ahead << 4 (attn_bias_tile)
+//   K8    the scores come from plain e4m3 copies of q and k (mtx_attn_args.q_f8 / k_f8) on the MX-scaled fp8 matrix instruction: four
+//         MFMAs of K = 64 per tile instead of sixteen of K = 16; a K tile is 8 KiB of LDS.  PRESCALED and DEEP only.
+//   V8    (with K8) P V on the fp8 instruction too: V^T tiles come as e4m3 [d][64 keys] in accumulator key order (MTX_EW_V_F8T), 8 KiB per tile
+// An include rather than a template flag or a shared device function on purpose: both of those changed the register allocation and the
+// schedule of the 16-bit kernel (5 % of its instruction sequence moved, compared with `hipcc -S`), and that kernel is 30 % of a page's
+// GPU time.  A variant is a new line of the table; tools/isa_diff.py shows that the others did not move.
 // PRESCALED (MTX_ATTN_Q_PRESCALED, the FLUX graphs): q carries scale * log2(e); the S^T accumulators start at minus the running maximum
 // and no maximum is taken on the hot path (attn_bias_tile).  Otherwise the classic online softmax of attn_mma32_tile.
-#ifndef ATTN_MMA32_K8
-#define ATTN_MMA32_K8 0
-#define ATTN_MMA32_K8_DEFAULTED 1
-#endif
-// ATTN_MMA32_V8 1 (with K8): P V on the fp8 instruction too — V^T tiles come as e4m3 [d][64 keys] in accumulator key order (MTX_EW_V_F8T), 8 KiB per tile
-#ifndef ATTN_MMA32_V8
-#define ATTN_MMA32_V8 0
-#define ATTN_MMA32_V8_DEFAULTED 1
+#if !defined(ATTN_MMA32_NAME) || !defined(ATTN_MMA32_Q8) || !defined(ATTN_MMA32_WIDE) || !defined(ATTN_MMA32_DEEP) || !defined(ATTN_MMA32_K8) || !defined(ATTN_MMA32_V8)
+#error "attn_mma32_body.inc: define ATTN_MMA32_NAME, _Q8, _WIDE, _DEEP, _K8 and _V8 before every inclusion"
 #endif
 template <typename T, int DP, bool PRESCALED>
 __global__ __launch_bounds__(512) void ATTN_MMA32_NAME(AttnParams p) {
@@ -238,10 +244,6 @@ __global__ __launch_bounds__(512) void ATTN_MMA32_NAME(AttnParams p) {
       else ATTN_TILE(0, false, AB_KV); \
     } \
   } while (0)
-#ifndef ATTN_MMA32_DEEP
-#define ATTN_MMA32_DEEP 0
-#define ATTN_MMA32_DEEP_DEFAULTED 1
-#endif
 #if ATTN_MMA32_V8
 #define ATTN_TILE(ST, RAG, KV) attn_bias_tile_k8v8<T, DP, ST, RAG>(smem, qf, oacc, m_raw, lsum, minit, first, kaddr, vaddr, KV, hi, qk_scale_b)
   (void)thr;
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(512) void ATTN_MMA32_NAME(AttnParams p) {
 #define ATTN_TILE(ST, RAG, KV) attn_bias_tile_k8<T, DP, ST, RAG, ATTN_MMA32_DEEP>(smem, qf, oacc, m_raw, lsum, minit, first, kaddr, vaddr, KV, hi, qk_scale_b)
   (void)thr;
 #else
-#define ATTN_TILE(ST, RAG, KV) do { if constexpr (BIAS) attn_bias_tile<T, DP, ST, RAG, true, ATTN_MMA32_DEEP>(smem, qf, oacc, m_raw, lsum, minit, first, kaddr, vaddr, KV, hi); \
+#define ATTN_TILE(ST, RAG, KV) do { if constexpr (BIAS) attn_bias_tile<T, DP, ST, RAG, ATTN_MMA32_DEEP>(smem, qf, oacc, m_raw, lsum, minit, first, kaddr, vaddr, KV, hi); \
                                     else attn_mma32_tile<T, DP, ST, RAG>(smem, qf, oacc, m_raw, lsum, c, thr, kaddr, vaddr, KV, hi); } while (0)
 #endif
   ATTN_MMA32_LOOP();
@@ -280,8 +282,8 @@ __global__ __launch_bounds__(512) void ATTN_MMA32_NAME(AttnParams p) {
   const long qr = q0 + l31;
 #if ATTN_MMA32_Q8
   // MX e4m3 + E8M0 of the row rounded to the storage type, exactly what quant_mx_kernel makes of the 16-bit output: a 32-wide block of the
-  // head dim lives in this lane (16 values) and in lane ^ 32 (the other 16) — one xor-shuffle for the block maximum, two dwords change
-  // lanes so that each lane stores 16 contiguous bytes; the four scale bytes of the head's 128 columns are one word
+  // head dim lives in this lane (16 values) and in lane ^ 32 (the other 16), the layout of mx_quantize_halfpair; the four scale bytes of
+  // the head's 128 columns are one word
   (void)O;
   unsigned word = 0;
 #pragma unroll
@@ -290,24 +292,8 @@ __global__ __launch_bounds__(512) void ATTN_MMA32_NAME(AttnParams p) {
     float amax = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { hv[e] = to_f32(from_f32<T>(oacc[d][e] * inv)); const float v = fabsf(hv[e]); amax = v > amax ? v : amax; }
-    { const float o = __shfl_xor(amax, 32, 64); amax = o > amax ? o : amax; }
-    const float r = amax * (1.0f / 448.0f);
-    const unsigned u = __builtin_bit_cast(unsigned, r);
-    int eb = (int)((u >> 23) & 0xff) + ((u & 0x7fffffu) ? 1 : 0);
-    eb = amax == 0.f ? 127 : (eb < 1 ? 1 : (eb > 253 ? 253 : eb));
-    const float sc = __builtin_bit_cast(float, (unsigned)(254 - eb) << 23);
-    unsigned w[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float q4[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float v = hv[g * 4 + e] * sc; q4[e] = v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
-      w[g] = 0;
-      w[g] = cvt_pk_fp8<false>(q4[0], q4[1], w[g]); w[g] = cvt_pk_fp8<true>(q4[2], q4[3], w[g]);
-    }
-    const unsigned s0 = hi ? w[0] : w[2], s1 = hi ? w[1] : w[3];
-    const unsigned r0 = (unsigned)__shfl_xor((int)s0, 32, 64), r1 = (unsigned)__shfl_xor((int)s1, 32, 64);
-    const u32x4 out = hi ? u32x4{r0, w[2], r1, w[3]} : u32x4{w[0], r0, w[1], r1};
+    int eb;
+    const u32x4 out = mx_quantize_halfpair(hv, amax, hi, eb);
     if (qr < p.sq) *reinterpret_cast<u32x4*>(p.q8 + (size_t)qr * p.ldq8 + h * DP + d * 32 + hi * 16) = out;
     word |= (unsigned)eb << (8 * d);
   }
@@ -341,16 +327,10 @@ __global__ __launch_bounds__(512) void ATTN_MMA32_NAME(AttnParams p) {
   }
 #endif
 #undef ATTN_ROW_SUM
-#ifdef ATTN_MMA32_DEEP_DEFAULTED
-#undef ATTN_MMA32_DEEP
-#undef ATTN_MMA32_DEEP_DEFAULTED
-#endif
 }
-#ifdef ATTN_MMA32_K8_DEFAULTED
+#undef ATTN_MMA32_NAME
+#undef ATTN_MMA32_Q8
+#undef ATTN_MMA32_WIDE
+#undef ATTN_MMA32_DEEP
 #undef ATTN_MMA32_K8
-#undef ATTN_MMA32_K8_DEFAULTED
-#endif
-#ifdef ATTN_MMA32_V8_DEFAULTED
 #undef ATTN_MMA32_V8
-#undef ATTN_MMA32_V8_DEFAULTED
-#endif

@@ -548,6 +548,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
   const T* W = reinterpret_cast<const T*>(p.w) + (size_t)bz * p.w_bs;
   T* Cp = reinterpret_cast<T*>(p.c) + (size_t)bz * p.c_bs;
   f32x16 acc[4][2];
+  // (this zeroing loop is written out in all five gemm256 kernels: a shared helper was tried and moved the code of every one, docs/experiments.md)
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -779,6 +780,9 @@ __global__ __launch_bounds__(512) void gemm256_f8_glu_kernel(GemmParams p) {
       const float v = fabsf(h[e]);
       amax = v > amax ? v : amax;
     }
+    // mx_quantize_halfpair (mtx_device.h) written out: with the helper this kernel's epilogue came out with other register numbers and a
+    // shifted VALU order (same MFMA / LDS / memory sequence, same resources), and the A/B on the GPU that would have cleared it was not
+    // taken (docs/experiments.md)
     { const float o = __shfl_xor(amax, 32, 64); amax = o > amax ? o : amax; }
     const float r = amax * (1.0f / 448.0f);
     const unsigned u = __builtin_bit_cast(unsigned, r);
@@ -854,25 +858,8 @@ __global__ __launch_bounds__(512) void gemm256_f8_actq_kernel(GemmParams p) {
         const float v = fabsf(h[e]);
         amax = v > amax ? v : amax;
       }
-      { const float o = __shfl_xor(amax, 32, 64); amax = o > amax ? o : amax; }
-      const float r = amax * (1.0f / 448.0f);
-      const unsigned u = __builtin_bit_cast(unsigned, r);
-      int eb = (int)((u >> 23) & 0xff) + ((u & 0x7fffffu) ? 1 : 0);
-      eb = amax == 0.f ? 127 : (eb < 1 ? 1 : (eb > 253 ? 253 : eb));
-      const float inv = __builtin_bit_cast(float, (unsigned)(254 - eb) << 23);
-      unsigned w[4];                                       // w[g]: outputs 8 g + 4 hi + 0..3 of the span
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float q4[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { float v = h[g * 4 + e] * inv; q4[e] = v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
-        w[g] = 0;
-        w[g] = cvt_pk_fp8<false>(q4[0], q4[1], w[g]); w[g] = cvt_pk_fp8<true>(q4[2], q4[3], w[g]);
-      }
-      // lane (hi = 0) keeps bytes 0..15 of the span (g = 0, 1), lane ^ 32 bytes 16..31 (g = 2, 3): swap the two dwords the other needs
-      const unsigned s0 = hi ? w[0] : w[2], s1 = hi ? w[1] : w[3];
-      const unsigned r0 = (unsigned)__shfl_xor((int)s0, 32, 64), r1 = (unsigned)__shfl_xor((int)s1, 32, 64);
-      const u32x4 out = hi ? u32x4{r0, w[2], r1, w[3]} : u32x4{w[0], r0, w[1], r1};
+      int eb;
+      const u32x4 out = mx_quantize_halfpair(h, amax, hi, eb);
       if (m < p.m) {
         *reinterpret_cast<u32x4*>(p.actq_q + (size_t)m * p.actq_ldq + span * 32 + hi * 16) = out;
         if (hi == 0) reinterpret_cast<unsigned char*>(p.actq_scale + (size_t)(span >> 2) * p.actq_lds + m)[span & 3] = (unsigned char)eb;

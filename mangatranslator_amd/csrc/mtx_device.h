@@ -318,6 +318,15 @@ __device__ __forceinline__ unsigned cvt_pk_fp8(float a, float b, unsigned old) {
 #endif
 }
 
+// The E8M0 scale byte of an MX block whose largest magnitude is amax: the smallest power of two 2^(eb - 127) >= amax / 448 (any mantissa
+// bit rounds the exponent up), kept inside 1 .. 253 so that 2^(127 - eb) is a normal float; an all-zero block gets 2^0.
+__device__ __forceinline__ int mx_scale_exp(float amax) {
+  const float r = amax * (1.0f / 448.0f);
+  const unsigned u = __builtin_bit_cast(unsigned, r);
+  const int eb = (int)((u >> 23) & 0xff) + ((u & 0x7fffffu) ? 1 : 0);
+  return amax == 0.f ? 127 : (eb < 1 ? 1 : (eb > 253 ? 253 : eb));
+}
+
 // One lane's share of an MX block quantisation (mtx_quant_args): the lane holds 8 consecutive k (chunk c8 of its row), lanes 4 g .. 4 g + 3
 // of a wave hold one 32-k block, 16 adjacent lanes one uint32 of four E8M0 scale bytes.  Every lane of the wave must call this (shuffles);
 // lanes without data pass zeros.  Out: the 8 e4m3 bytes (w0, w1) and the group's scale word (to be stored by the lane with (c8 & 15) == 0).
@@ -327,11 +336,7 @@ __device__ __forceinline__ void mx_quantize_chunk(float (&f)[8], long c8, unsign
   for (int e = 0; e < 8; ++e) { const float a = fabsf(f[e]); amax = a > amax ? a : amax; }
   { float o = __shfl_xor(amax, 1, 64); amax = o > amax ? o : amax; }
   { float o = __shfl_xor(amax, 2, 64); amax = o > amax ? o : amax; }
-  // smallest power of two 2^(eb - 127) >= amax / 448
-  const float r = amax * (1.0f / 448.0f);
-  const unsigned u = __builtin_bit_cast(unsigned, r);
-  int eb = (int)((u >> 23) & 0xff) + ((u & 0x7fffffu) ? 1 : 0);
-  eb = amax == 0.f ? 127 : (eb < 1 ? 1 : (eb > 253 ? 253 : eb));
+  const int eb = mx_scale_exp(amax);
   const float inv = __builtin_bit_cast(float, (unsigned)(254 - eb) << 23);      // 2^(127 - eb)
 #pragma unroll
   for (int e = 0; e < 8; ++e) { float v = f[e] * inv; v = v > 448.f ? 448.f : (v < -448.f ? -448.f : v); f[e] = v; }
@@ -341,6 +346,28 @@ __device__ __forceinline__ void mx_quantize_chunk(float (&f)[8], long c8, unsign
   word = (unsigned)eb << (8 * (int)((c8 & 15) >> 2));
   word |= __shfl_xor(word, 4, 64);
   word |= __shfl_xor(word, 8, 64);
+}
+
+// The same quantisation where a 32-wide MX block lives in the accumulators of a 32x32 MFMA: 16 values in this lane (h[4 g + e] is output
+// 8 g + 4 hi + e of the block), the other 16 in lane ^ 32.  `amax` is the largest magnitude of this lane's 16; one xor-shuffle makes it the
+// block's.  The lane with hi = 0 keeps bytes 0..15 of the block (g = 0, 1), lane ^ 32 bytes 16..31 (g = 2, 3): the two dwords the other one
+// needs change lanes, and each lane returns 16 contiguous bytes.  Both lanes of a pair must call this.  Out: the block's scale byte eb.
+__device__ __forceinline__ u32x4 mx_quantize_halfpair(const float (&h)[16], float amax, int hi, int& eb) {
+  { const float o = __shfl_xor(amax, 32, 64); amax = o > amax ? o : amax; }
+  eb = mx_scale_exp(amax);
+  const float inv = __builtin_bit_cast(float, (unsigned)(254 - eb) << 23);      // 2^(127 - eb)
+  unsigned w[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    float q4[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const float v = h[g * 4 + e] * inv; q4[e] = v > 448.f ? 448.f : (v < -448.f ? -448.f : v); }
+    w[g] = 0;
+    w[g] = cvt_pk_fp8<false>(q4[0], q4[1], w[g]); w[g] = cvt_pk_fp8<true>(q4[2], q4[3], w[g]);
+  }
+  const unsigned s0 = hi ? w[0] : w[2], s1 = hi ? w[1] : w[3];
+  const unsigned r0 = (unsigned)__shfl_xor((int)s0, 32, 64), r1 = (unsigned)__shfl_xor((int)s1, 32, 64);
+  return hi ? u32x4{r0, w[2], r1, w[3]} : u32x4{w[0], r0, w[1], r1};
 }
 
 // XCD-aware, bijective remap of a linear workgroup id: workgroup b runs on XCD b%8 (observed),

@@ -798,3 +798,77 @@ def check_attention_selector(lib, dtype, sq, sk, heads=2, L=192.0, seed=0):
     _assert_bytes(sc[1:, :sq], w_want, what + ": scale words")
     assert bool((q8[:sq, :128] == Q_SENTINEL).all()) and bool((q8[sq:] == Q_SENTINEL).all()), f"{what}: bytes outside the target window were written"
     assert bool((sc[0] == S_SENTINEL).all()) and bool((sc[1:, sq:] == S_SENTINEL).all()), f"{what}: scale words outside the target window were written"
+
+
+ATTN_LONG_VARIANTS = ("mma32", "d", "q8", "q8d", "k8", "k8q", "k8v8q")
+
+
+def check_attention_selector_below(lib, dtype, variant, sq=1024, sk=330, seed=0):
+    """One case per variant of the long-sequence kernel (the table in csrc/attn_mma32_body.inc; `mma32` is attn_mma32_kernel without pre-scaled q — with
+    it the launcher takes that kernel only for an output that is not 16-byte aligned), at the smallest shape that reaches it: one head, five full key
+    tiles and a ragged one of 10.
+    Channel c selects key (c * (sk - 1)) // 127 — keys of every tile, the last valid key among them: that key holds -16 at channel c, every other
+    key -112, and q rows are one-hot.  The selected logit is 96 (base 2) above the rest: the other keys weigh 2^-96, their sum (< 2^-96 * sk * 448)
+    is below half an fp32 ulp of the smallest nonzero e4m3 magnitude (2^-9), so the output row IS the selected v row, none of whose values is
+    zero.  But every real logit lies BELOW 0, the score of a key that does not exist: one key past the ragged end admitted outweighs the selected one
+    2^16 times.  A query whose key lies in a later tile moves its maximum there, by 96, far past every stale-maximum limit: without the refill of the
+    accumulators' start value the earlier tiles keep weight 1, and without the rescale of O^T their rows stay in the sum.  v holds e4m3 values
+    (exact in every operand type of every variant); the MX fp8 variants must give Q_ref of the selected rows: bytes in the order of the two
+    half-blocks, scale bytes rounded up.  (All pre-scaled logits stay above -128: the first tile's 2^-maximum must be finite in fp32.)"""
+    assert variant in ATTN_LONG_VARIANTS and sq >= 1024 and 256 <= sk < 2 * 256
+    dev, td = _dev(lib), TD[dtype]
+    d = 128
+    what = f"attention selector below zero {sq}x{sk} [{variant}, {NAME[dtype]}]"
+    prescaled, out8 = variant not in ("mma32", "q8"), variant in ("q8", "q8d", "k8q", "k8v8q")
+    g = torch.Generator().manual_seed(seed)
+    bits = torch.randint(0, 256, (sk, d), generator=g, dtype=torch.uint8)
+    bits[((bits & 0x7F) == 0x7F) | ((bits & 0x7F) == 0)] = 0x38           # no NaN, no zero
+    v = bits.view(torch.float8_e4m3fn).double() + 0.0
+    c = torch.arange(d)
+    key_of = (c * (sk - 1)) // (d - 1)
+    assert int(key_of[-1]) == sk - 1 and len(set(key_of.tolist())) == d and int((key_of >= sk // 64 * 64).sum()) >= 2 and int((key_of < 64).sum()) >= 2
+    kk = torch.full((sk, d), -112.0, dtype=torch.float64)
+    kk[key_of, c] = -16.0
+    chan = (torch.arange(sq) * 37) % d
+    q = torch.zeros(sq, d, dtype=torch.float64)
+    q[torch.arange(sq), chan] = 1.0 if prescaled else 256.0              # not pre-scaled: the kernel multiplies by log2(e) / sqrt(128) = 0.1275
+    want = v[key_of[chan]]
+    logits = (q @ kk.t()) * (1.0 if prescaled else math.log2(math.e) / math.sqrt(d))
+    top = logits.topk(2, 1).values
+    assert float(top[:, 0].max()) <= -16.0 and float((top[:, 0] - top[:, 1]).min()) >= 96.0 and (not prescaled or float(logits.min()) > -128.0)
+    assert torch.equal(logits.argmax(1), key_of[chan])
+    pb = PlanBuilder(lib, dev, dtype)
+    vt = pb.const(v.view(1, sk, 1, d).to(td))
+    kw = dict(q_prescaled=prescaled)
+    if variant in ("k8", "k8q", "k8v8q"):
+        rows = max(sq, sk)
+        packed = torch.zeros(rows, 2 * d, dtype=torch.uint8)              # [row][q bytes | k bytes]: the layout the rotary kernel leaves
+        packed[:sq, :d] = q.float().to(torch.float8_e4m3fn).view(torch.uint8)
+        packed[:sk, d:] = kk.float().to(torch.float8_e4m3fn).view(torch.uint8)
+        qt = kt = pb.buf((1, rows, 1, d), td, zero=True)                  # q / k are not read in this form
+        strides = ((rows * d, d, d), (rows * d, d, d), (sk * d, d, d), (sq * d, d, d))
+        kw["qk_f8"] = (pb.const(packed), 0, d, 2 * d, 0)
+        if variant == "k8v8q":
+            kw["pv_f8"] = pb.v_f8t(vt, sk, 1, d)
+    else:
+        qt, kt = pb.const(q.view(1, sq, 1, d).to(td)), pb.const(kk.view(1, sk, 1, d).to(td))
+        strides = ((sq * d, d, d), (sk * d, d, d), (sk * d, d, d), (sq * d, d, d))
+    if out8:
+        lds = (sq + 63) // 64 * 64
+        q8 = pb.buf((sq + 1, d), torch.uint8)
+        q8.fill_(Q_SENTINEL)
+        sc = pb.buf((1, lds), torch.int32)
+        sc.fill_(S_SENTINEL)
+        pb.attention(qt, kt, vt, None, 1, 1, sq, sk, d, *strides, 1.0 / math.sqrt(d), q8=(q8, sc, d, lds, 0), **kw)
+        _run(pb)
+        q_want, _, w_want = q_ref(want)
+        _assert_bytes(q8[:sq], q_want, what + ": e4m3 bytes")
+        _assert_bytes(sc[:, :sq], w_want, what + ": scale words")
+        assert bool((q8[sq:] == Q_SENTINEL).all()) and bool((sc[:, sq:] == S_SENTINEL).all()), f"{what}: written outside the target window"
+    else:
+        o = pb.buf((sq + 1, d), td)
+        o.fill_(SENTINEL)
+        pb.attention(qt, kt, vt, o, 1, 1, sq, sk, d, *strides, 1.0 / math.sqrt(d), **kw)
+        _run(pb)
+        _assert_equal(o[:sq].cpu(), want, what)
+        assert bool((o[sq:] == SENTINEL).all()), f"{what}: written outside the output rows"

@@ -439,6 +439,13 @@ def test_attention_fp8_output_selects_rows(emu_lib, dtype, sk):
 
 
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("variant", pc.ATTN_LONG_VARIANTS)
+def test_attention_long_variants_select_below_zero(emu_lib, dtype, variant):
+    """every variant of the long-sequence kernel at 1024 x 330: the ragged mask, the moved maximum and (MX fp8 rows) the half-block quantiser"""
+    pc.check_attention_selector_below(emu_lib, dtype, variant)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
 @pytest.mark.parametrize("cfg", pc.ROPE_CASES, ids=lambda c: f"{c['rows']}x{c['hq']}+{c['hk']}x{c['d']}")
 def test_qk_norm_rope_exact(emu_lib, dtype, cfg):
     pc.check_rope_exact(emu_lib, dtype, **cfg)

@@ -20,10 +20,13 @@ CSRC = ROOT / "mangatranslator_amd" / "csrc"
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
-def compile_to_isa(src: Path, out_dir: Path):
+AUDIT_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT / 'include'}"]
+
+
+def compile_to_isa(src: Path, out_dir: Path, flags=AUDIT_FLAGS):
+    """src -> (out_dir/stem.s, out_dir/stem.res): device assembly and the compiler's resource remarks; shared with tools/isa_diff.py"""
     asm, res = out_dir / (src.stem + ".s"), out_dir / (src.stem + ".res")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT / 'include'}", "-S", "--cuda-device-only", str(src), "-o", str(asm),
-           "-Rpass-analysis=kernel-resource-usage"]
+    cmd = [HIPCC, *flags, "-S", "--cuda-device-only", str(src), "-o", str(asm), "-Rpass-analysis=kernel-resource-usage"]
     r = subprocess.run(cmd, cwd=src.parent, capture_output=True, text=True)
     res.write_text(r.stderr)
     if not asm.exists():

@@ -270,13 +270,20 @@ typedef enum mtx_ew_kind {
                              -> y8 = e4m3 bytes [head][128 d][ldy8 keys], ldy8 = rows padded to a multiple of 64, zero beyond `rows`.  Inside every 64-key
                              tile the keys of a d-row are stored in the order the score accumulators hold them (byte j of the tile: key
                              32 (j >> 5) + (j & 3) + 8 ((j & 15) >> 2) + 4 ((j >> 4) & 1)), so that the probabilities need no shuffle.  Saturated at +-448. */
-  MTX_EW_QK_NORM_ROPE = 12 /* FLUX attention prep, in place friendly: for every token r and head hd (c = heads*d,
+  MTX_EW_QK_NORM_ROPE = 12, /* FLUX attention prep, in place friendly: for every token r and head hd (c = heads*d,
                              i0 = d): x <- RMSNorm_d(x) * gamma[d] (s = fp32 gamma, eps = act_param), then
                              rotary on interleaved pairs with b = fp32 [rows][d] cos|sin table laid out as
                              [rows][2][d/2]: (x0, x1) -> (x0*cos - x1*sin, x1*cos + x0*sin).
                              i1 > 0: heads >= i1 use the second gamma vector (fused q|k slices); with ldb > 0 the heads
                              < i1 (the q slice) read their table at b + ldb floats instead — a copy pre-multiplied by
                              the attention scale * log2(e), see MTX_ATTN_Q_PRESCALED                    */
+  MTX_EW_QK_ROPE = 22,    /* the rotary turn alone, in place friendly (SAM 3's ViT trunk): a = y = the q | k column view [rows, c = heads * d] of token rows
+                             (16-bit, row strides lda / ldy), i0 = d (64 or 128), b = fp32 [rows][2][d/2] cos | sin, 16-byte aligned; per interleaved pair
+                             (x0, x1) -> (x0*cos - x1*sin, x1*cos + x0*sin) in fp32, rounded once.  i1 > 0 and ldb > 0: heads < i1 (the q slice) read the
+                             table ldb floats (ldb % 4 == 0) behind b, a copy pre-multiplied by scale * log2(e) (MTX_ATTN_Q_PRESCALED).  Columns beyond c
+                             (the v slice of a fused qkv row) are not touched.                                                             */
+  MTX_EW_IM2COL_PATCH = 23 /* MTX_EW_IM2COL without padding: y[r, tap*C + c] = a[n, oy*s+ky, ox*s+kx, c], (h - k) / s + 1 output rows (k = s: the
+                             non-overlapping patches of a ViT's patch embedding)                                                           */
 } mtx_ew_kind;
 
 #define MTX_RESDIST_PARTS 256

@@ -288,7 +288,7 @@ def _detect_speech_bubbles(image_path, model_path, confidence, verbose, device, 
         if remembered is not None:
             log_message("Using cached SAM masks", verbose=verbose)
             return remembered, text_free_boxes
-        if seg_model == "sam3":                 # reference :1661-1666; the loader raises here (SAM 3 is not built) and the page keeps its YOLO masks
+        if seg_model == "sam3":                 # reference :1661-1666; no checkpoint staged -> ModelError, and the page keeps its YOLO masks
             processor, sam = manager.load_sam3(token=osb_text_hf_token, verbose=verbose)
         else:
             processor, sam = manager.load_sam2(verbose=verbose)
@@ -313,7 +313,7 @@ def _detect_speech_bubbles(image_path, model_path, confidence, verbose, device, 
                     sam_masks[owners[i]] = clipped
                 else:
                     synthetic_groups[i - synth_start]["parent_mask"] = clipped
-            log_message(f"Generated {len(prompts)} primary masks with SAM 2.1", always_print=True)
+            log_message(f"Generated {len(prompts)} primary masks with {'SAM 3' if seg_model == 'sam3' else 'SAM 2.1'}", always_print=True)
         detections = assemble(sam_masks)
         cache.set_sam_masks(sam_key, detections)
         return detections, text_free_boxes

@@ -105,7 +105,8 @@ def broadcast_state_dict(sd: Optional[dict], template: Optional[dict] = None, sr
 
 
 class _Sam2ProcessorShim:
-    """The slice of `Sam2Processor` the operator uses; the heavy lifting is fused into the model."""
+    """The slice of `Sam2Processor` / `Sam3TrackerProcessor` the operator uses; the heavy lifting (resize, normalisation with the model's own
+    mean / std, box scaling, mask upsampling) is fused into the model, so one shim serves both."""
 
     def __call__(self, image, input_boxes=None, return_tensors="pt"):
         import numpy as np
@@ -143,6 +144,21 @@ class _PredMasks:
         return [self._m.bool()[:, None]]
 
 
+SAM3_IGNORED_KEYS = ("detector_model.", "memory_", "mask_downsample", "object_pointer_proj", "temporal_positional_encoding_projection_layer",
+                     "no_memory_positional_encoding", "no_object_pointer", "occlusion_spatial_embedding_parameter")
+
+
+def sam3_tracker_state_dict(sd: dict) -> dict:
+    """`Sam3TrackerModel.state_dict()` names out of a checkpoint that may carry them under `tracker_model.` beside a `detector_model.` tree and
+    the video tracker's memory / object-pointer tensors (Sam3TrackerModel._keys_to_ignore_on_load_unexpected), which the image path never reads"""
+    out = {}
+    for k, v in sd.items():
+        k = k[len("tracker_model."):] if k.startswith("tracker_model.") else k
+        if not k.startswith(SAM3_IGNORED_KEYS):
+            out[k] = v
+    return out
+
+
 SAM_F16_PROBE_TOLERANCE = 0.08       # bf16's own error at Hiera-L is ~0.024 of the logit range (profiles/r04_sam_dtype_probe.json)
 
 
@@ -152,7 +168,7 @@ class _Sam2ModelShim:
 
     def __call__(self, multimask_output=False, **inputs):
         if multimask_output:
-            raise ModelError("SAM-2.1 on libmtx_hip implements multimask_output=False (the reference's call)")
+            raise ModelError(f"{self.hip.NAME} on libmtx_hip implements multimask_output=False (the reference's call)")
         masks, low, iou, _ = self.hip.segment(inputs["page"], inputs["input_boxes"][0].numpy(), return_logits=True)
         return _Sam2Outputs(masks, low, iou)
 
@@ -182,6 +198,7 @@ class ModelManager:
                 ModelType.YOLO_SPEECH_BUBBLE: model_dir / "yolo" / "yolov8m_seg-speech-bubble.pt",            # the reference's own file names (:119-132);
                 ModelType.YOLO_SPEECH_BUBBLE_2: model_dir / "yolo" / "manga109-segmentation-bubble.pt",       # a `.safetensors` sibling is read as well
                 ModelType.SAM2: model_dir / "sam" / "sam2.1-hiera-large",
+                ModelType.SAM3: model_dir / "sam" / "sam3",
                 ModelType.RTDETR_CONJOINED_BUBBLE: model_dir / "rtdetr" / "comic-text-and-bubble-detector",
                 ModelType.YOLO_OSBTEXT: model_dir / "yolo" / "animetext_yolov12x.pt",
                 ModelType.YOLO_PANEL: model_dir / "yolo" / "manga109_v2023.12.07_l_yolov11.pt",
@@ -218,7 +235,7 @@ class ModelManager:
     # measures: config 2 33 -> 37 pages/s with sixteen hardware queues).  Set 0 is the plain slot the reference's callers know; every other
     # model type ignores the setting.
     FRONT_MODEL_TYPES = frozenset({ModelType.YOLO_SPEECH_BUBBLE, ModelType.YOLO_SPEECH_BUBBLE_2, ModelType.RTDETR_CONJOINED_BUBBLE,
-                                   ModelType.YOLO_OSBTEXT, ModelType.YOLO_PANEL, ModelType.SAM2})
+                                   ModelType.YOLO_OSBTEXT, ModelType.YOLO_PANEL, ModelType.SAM2, ModelType.SAM3})
 
     # checkpoint file names earlier builds of this package staged for a slot whose default name has since become the reference's own
     # (a staging directory that still holds the old panel export must keep working, not fall back to "global sorting")
@@ -260,6 +277,8 @@ class ModelManager:
             jobs.append(("RT-DETR secondary detector", lambda: self.load_rtdetr_conjoined_bubble(verbose=verbose)))
         if g(det, "seg_model", "sam2") == "sam2":
             jobs.append(("SAM 2.1", lambda: self.load_sam2(verbose=verbose)))
+        elif g(det, "seg_model", "sam2") == "sam3":
+            jobs.append(("SAM 3", lambda: self.load_sam3(verbose=verbose)))
         if g(osb, "enabled", False) or g(det, "use_osb_text_verification", False):
             jobs.append(("outside-text detector", lambda: self.load_yolo_osbtext(token=g(osb, "huggingface_token", None), verbose=verbose)))
         if g(det, "use_panel_sorting", False):
@@ -396,11 +415,6 @@ class ModelManager:
 
     def shutdown_sdcpp_servers(self, verbose: bool = False):
         pass
-
-    def load_sam3(self, token: Optional[str] = None, verbose: bool = False):
-        """SAM 3 (`facebook/sam3`, gated; reference :1012-1046) is outside SURVEY §8 — fail the way a missing checkpoint does, so
-        `detect_speech_bubbles(seg_model="sam3")` degrades through its ModelError path instead of an AttributeError"""
-        raise ModelError("SAM 3 is not built in this package (SURVEY §8 a3 covers SAM 2.1); use seg_model='sam2'")
 
     def get_memory_stats(self):
         """reference :1495-1497"""
@@ -667,28 +681,59 @@ class ModelManager:
 
     def load_sam2(self, verbose: bool = False):
         """-> (processor, model) like the reference (:982-1010), backed by the HIP graph."""
-        with self._lock:
-            slot = self._slot(ModelType.SAM2)
-            if self.is_loaded(slot):
-                loaded = self.models[slot][1].hip
-                if slot is not ModelType.SAM2 or loaded.precision == getattr(self, "sam_precision", "high"):
-                    return self.models[slot]
-                self.unload_model(ModelType.SAM2, force_gc=False, verbose=verbose)      # `sam_precision` changed since the load: build the other arithmetic
+        def read():
+            from transformers import Sam2Config
             from .sam2 import Sam2Hip
             root = self.model_paths[ModelType.SAM2]
+            return Sam2Hip, Sam2Config.from_pretrained(str(root)), (lambda sd: sd)
+        return self._load_sam(ModelType.SAM2, "SAM 2.1", "SAM-2.1 config", read, verbose)
+
+    def load_sam3(self, token: Optional[str] = None, verbose: bool = False):
+        """-> (processor, model) like the reference (:1012-1046: `Sam3TrackerModel` / `Sam3TrackerProcessor` from the gated `facebook/sam3`),
+        backed by the HIP graph (core/ml/sam3.py).  Reads `config.json` + `model.safetensors` staged under models/sam/sam3; `token` is the
+        reference's download credential and is not used (this build never downloads).  Nothing staged -> ModelError, and
+        `detect_speech_bubbles(seg_model="sam3")` keeps the detector's own masks.  `sam_precision` / `sam_storage`, the f16-vs-bf16 load-time
+        probe, front replicas and unloading work as for SAM-2.1.
+
+        Checkpoint keys: `Sam3TrackerModel.state_dict()` names, bare or under a `tracker_model.` prefix; `detector_model.*` and the video
+        tracker's memory / object-pointer tensors (the HF class's `_keys_to_ignore_on_load_unexpected`) are dropped.  The layout of the hub's
+        own file is UNVERIFIED here: no real checkpoint was available to this build, only `save_pretrained` output of the HF class."""
+        def read():
+            import json
+            from transformers import Sam3TrackerConfig
+            from .sam3 import Sam3Hip
+            root = self.model_paths[ModelType.SAM3]
+            tree = json.loads((root / "config.json").read_text())
+            if isinstance(tree.get("tracker_config"), dict):          # a combined (video) configuration: the tracker is one branch of it
+                config = Sam3TrackerConfig(**tree["tracker_config"])
+            else:
+                config = Sam3TrackerConfig.from_pretrained(str(root))
+            return Sam3Hip, config, sam3_tracker_state_dict
+        return self._load_sam(ModelType.SAM3, "SAM 3", "SAM 3 config", read, verbose)
+
+    def _load_sam(self, mt: ModelType, label: str, cfg_label: str, read, verbose: bool):
+        """the loader SAM-2.1 and SAM 3 share.  `read()` -> (model class, HF config, state-dict filter), called once the config file is known
+        to be staged"""
+        with self._lock:
+            slot = self._slot(mt)
+            if self.is_loaded(slot):
+                loaded = self.models[slot][1].hip
+                if slot is not mt or loaded.precision == getattr(self, "sam_precision", "high"):
+                    return self.models[slot]
+                self.unload_model(mt, force_gc=False, verbose=verbose)      # `sam_precision` changed since the load: build the other arithmetic
+            root = self.model_paths[mt]
             weights, cfg = root / "model.safetensors", root / "config.json"
-            if slot is ModelType.SAM2:
-                self._staged(cfg, "SAM-2.1 config")
-            from transformers import Sam2Config
-            config = Sam2Config.from_pretrained(str(root))
-            sd = self._read_safetensors(weights, local=slot is not ModelType.SAM2)
+            if slot is mt:
+                self._staged(cfg, cfg_label)
+            SamHip, config, keys = read()
+            sd = keys(self._read_safetensors(weights, local=slot is not mt))
             want = getattr(self, "sam_precision", "high")
             if want not in ("fast", "high"):
                 raise ModelError(f"ModelManager.sam_precision must be 'fast' or 'high', not {want!r}")
-            if slot is not ModelType.SAM2 and self.is_loaded(ModelType.SAM2):
+            if slot is not mt and self.is_loaded(mt):
                 # a replica takes the storage type set 0 settled on (its probe compared the two): one more model, no second probe
-                first = self.models[ModelType.SAM2][1].hip
-                hip = Sam2Hip(sd, config, device=self.device, dtype=first.dtype, precision=first.precision)
+                first = self.models[mt][1].hip
+                hip = SamHip(sd, config, device=self.device, dtype=first.dtype, precision=first.precision)
                 self.models[slot] = (_Sam2ProcessorShim(), _Sam2ModelShim(hip, self.dtype))
                 return self.models[slot]
             # f16 storage (8x smaller logit error than bf16 against the fp32 reference: the `> 0` masks are what the page flow keeps)
@@ -699,8 +744,8 @@ class ModelManager:
             if storage not in ("auto", "bf16", "f16"):
                 raise ModelError(f"ModelManager.sam_storage must be 'auto', 'bf16' or 'f16', not {storage!r}")
             if storage == "auto":
-                hip = Sam2Hip(sd, config, device=self.device, dtype=abi.BF16)
-                hip16 = Sam2Hip(sd, config, device=self.device, dtype=abi.F16)
+                hip = SamHip(sd, config, device=self.device, dtype=abi.BF16)
+                hip16 = SamHip(sd, config, device=self.device, dtype=abi.F16)
                 ref, got = hip.probe_logits(), hip16.probe_logits()
                 gap = ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-6)).item() if torch.isfinite(got).all() else float("inf")
                 if gap < SAM_F16_PROBE_TOLERANCE:
@@ -709,11 +754,11 @@ class ModelManager:
                     why = f"f16 disagrees with bf16 on the probe page by {gap:.2f} of the logit range"
                 del hip16
             else:
-                hip, why = Sam2Hip(sd, config, device=self.device, dtype=abi.F16 if storage == "f16" else abi.BF16), "ModelManager.sam_storage"
+                hip, why = SamHip(sd, config, device=self.device, dtype=abi.F16 if storage == "f16" else abi.BF16), "ModelManager.sam_storage"
             if want == "high":
-                hip = Sam2Hip(sd, config, device=self.device, dtype=hip.dtype, precision="high")
+                hip = SamHip(sd, config, device=self.device, dtype=hip.dtype, precision="high")
             self.models[slot] = (_Sam2ProcessorShim(), _Sam2ModelShim(hip, self.dtype))
-            log_message(f"SAM 2.1 model loaded: {'f16' if hip.dtype == abi.F16 else 'bf16'} storage ({why}), precision {want!r}.", always_print=True)
+            log_message(f"{label} model loaded: {'f16' if hip.dtype == abi.F16 else 'bf16'} storage ({why}), precision {want!r}.", always_print=True)
             return self.models[slot]
 
     flux_kontext_fp8 = False   # opt-in: FLUX.1-Kontext's block linears on the MX fp8 matrix path (FluxDiTHip(fp8=True)); read when the pipeline is loaded

@@ -5,6 +5,7 @@
 //   MTX_EW_UPSAMPLE2X  nn.Upsample(2, 'nearest') of the YOLO neck / SAM FPN top-down path
 //   MTX_EW_MAXPOOL     SPPF 5x5 max-pool (YOLO) and Hiera 2x2 query pooling (SAM-2.1)
 //   MTX_EW_GATE_RES    x + gate * y of the FLUX DiT blocks
+//   MTX_EW_QK_ROPE     SAM 3's axial rotary turn of q | k (transformers Sam3ViTRoPEAttention)
 //   channel attention MLP, image<->tensor conversions of image_to_tensor / tensor_to_image
 //   (core/image/image_utils.py:351-366) and the bilinear-resize + threshold of
 //   Sam2ImageProcessor.post_process_masks (core/image/detection.py:507-510).
@@ -20,11 +21,12 @@ __global__ __launch_bounds__(256) void ew_kernel(mtx_ew_args p) {
   if (kind == MTX_EW_UPSAMPLE2X) { oh = 2 * p.h; ow = 2 * p.w; }
   if (kind == MTX_EW_MAXPOOL) { const int k = p.i0, s = p.i1, pd = (k & 1) ? k / 2 : 0; oh = (p.h + 2 * pd - k) / s + 1; ow = (p.w + 2 * pd - k) / s + 1; }
   if (kind == MTX_EW_AVGPOOL2) { oh = (p.h + 1) / 2; ow = (p.w + 1) / 2; }
-  if (kind == MTX_EW_IM2COL) { const int k = p.i0, s = p.i1, pd = k / 2; oh = (p.h + 2 * pd - k) / s + 1; ow = (p.w + 2 * pd - k) / s + 1; }
+  const bool im2col = kind == MTX_EW_IM2COL || kind == MTX_EW_IM2COL_PATCH;          // _PATCH: no padding (a ViT's patch embedding)
+  if (im2col) { const int k = p.i0, s = p.i1, pd = kind == MTX_EW_IM2COL ? k / 2 : 0; oh = (p.h + 2 * pd - k) / s + 1; ow = (p.w + 2 * pd - k) / s + 1; }
   const T* A = reinterpret_cast<const T*>(p.a);
-  if (kind == MTX_EW_IM2COL) {
+  if (im2col) {
     // one 16-byte chunk per (output row, tap, 8 channels)
-    const int k = p.i0, st = p.i1, pd = k / 2;
+    const int k = p.i0, st = p.i1, pd = kind == MTX_EW_IM2COL ? k / 2 : 0;
     const long per_row = (long)k * k * C8;
     const long rows = p.n * oh * ow;
     const int32_t* map = reinterpret_cast<const int32_t*>(p.s);
@@ -359,6 +361,7 @@ __global__ __launch_bounds__(256) void v_f8t_kernel(mtx_ew_args p) {
 }
 
 int ew_f32_launch(const mtx_ew_args* a, void* stream, const char** err);      // f32ops.hip
+int qk_rope_launch(const mtx_ew_args* a, void* stream, const char** err);      // at the end of this file
 int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
   if (a->dtype == MTX_F32) return ew_f32_launch(a, stream, err);
   if (a->kind == MTX_EW_SOFTMAX_ROWS) {
@@ -402,6 +405,7 @@ int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
     if (!MTX_LAUNCH_T(a->dtype, qk_norm_rope_kernel, grid, dim3(256), stream, *a)) { *err = "qk_norm_rope: dtype"; return MTX_ERR_INVALID; }
     return MTX_OK;
   }
+  if (a->kind == MTX_EW_QK_ROPE) return qk_rope_launch(a, stream, err);
   if (!a->a || !a->y) { *err = "elementwise: null operand"; return MTX_ERR_INVALID; }
   if (a->c % 8 || a->lda % 8 || a->ldy % 8 || (a->b && a->ldb % 8 && a->kind != MTX_EW_DWCONV)) { *err = "elementwise: C and pixel strides must be multiples of 8"; return MTX_ERR_INVALID; }
   if ((a->kind == MTX_EW_SCALE_RES || a->kind == MTX_EW_ADD || a->kind == MTX_EW_MUL || a->kind == MTX_EW_SUB || a->kind == MTX_EW_GATE_RES || a->kind == MTX_EW_SWIGLU) && !a->b) { *err = "elementwise: missing operand b"; return MTX_ERR_INVALID; }
@@ -413,9 +417,10 @@ int ew_launch(const mtx_ew_args* a, void* stream, const char** err) {
   if (a->kind == MTX_EW_MAXPOOL) { const int pd = (a->i0 & 1) ? a->i0 / 2 : 0; oh = (a->h + 2 * pd - a->i0) / a->i1 + 1; ow = (a->w + 2 * pd - a->i0) / a->i1 + 1; }
   if (a->kind == MTX_EW_AVGPOOL2) { oh = (a->h + 1) / 2; ow = (a->w + 1) / 2; }
   long total = a->n * oh * ow * (a->c / 8);
-  if (a->kind == MTX_EW_IM2COL) {
+  if (a->kind == MTX_EW_IM2COL || a->kind == MTX_EW_IM2COL_PATCH) {
     if (a->i0 < 1 || a->i1 < 1 || a->ldy < (long)a->i0 * a->i0 * a->c) { *err = "elementwise: im2col needs k, stride and ldy >= k*k*C"; return MTX_ERR_INVALID; }
-    const int pd = a->i0 / 2;
+    if (a->kind == MTX_EW_IM2COL_PATCH && (a->h < a->i0 || a->w < a->i0)) { *err = "elementwise: im2col_patch needs an image of at least k x k"; return MTX_ERR_INVALID; }
+    const int pd = a->kind == MTX_EW_IM2COL ? a->i0 / 2 : 0;
     total = a->n * ((a->h + 2 * pd - a->i0) / a->i1 + 1) * ((a->w + 2 * pd - a->i0) / a->i1 + 1) * (long)a->i0 * a->i0 * (a->c / 8);
   }
   if (a->kind == MTX_EW_ROW_GATHER && !a->s) { *err = "elementwise: row_gather needs the index map in s"; return MTX_ERR_INVALID; }
@@ -1044,6 +1049,64 @@ int yolo_decode_launch(const mtx_yolo_decode_args* a, void* stream, const char**
   if (total == 0) return MTX_OK;
   const unsigned blocks = (unsigned)((total + 255) / 256);
   if (!MTX_LAUNCH_T(a->dtype, yolo_decode_kernel, dim3(blocks), dim3(256), stream, *a, total)) { *err = "yolo_decode: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  return MTX_OK;
+}
+
+// ---- SAM 3 q/k prep: the rotary turn alone (no per-head norm), on interleaved pairs ---------------------------------------------------
+// In place over the q | k columns of the fused qkv rows: (x0, x1) -> (x0 c - x1 s, x1 c + x0 s) in fp32, one rounding to T.  The table is per
+// token row ([rows][2][d / 2] fp32, cos | sin), so window-local positions and the global layers' position scale are the host's business.
+// Same shape as qk_norm_rope_kernel (a thread owns one 16-byte column chunk and keeps QR_U rows of it in flight, their table rows included)
+// without its cross-lane sum: lanes are independent, a column past the end simply leaves.  (Last in the file, launcher included, so that the
+// kernels before it keep their place in the code object: tools/isa_diff.py then shows them unchanged.)
+template <typename T>
+__global__ __launch_bounds__(256) void qk_rope_kernel(mtx_ew_args p) {
+  const int d = p.i0, lpr = d / 8;                                   // lanes per (token, head) row: 8 or 16
+  const unsigned cpr = (unsigned)(p.c / 8);                          // 16-byte chunks per token row
+  const unsigned rows = (unsigned)(p.n * p.h * p.w);
+  const unsigned ch = blockIdx.x * 256u + threadIdx.x;               // grid.x = ceil(cpr / 256)
+  if (ch >= cpr) return;
+  const int part = (int)(ch & (unsigned)(lpr - 1));
+  const int hd = (int)(ch / (unsigned)lpr);
+  const float* cs = reinterpret_cast<const float*>(p.b);
+  if (p.i1 > 0 && p.ldb > 0 && hd < p.i1) cs += p.ldb;               // q heads: the copy pre-multiplied by softmax scale * log2(e)
+  const T* X = reinterpret_cast<const T*>(p.a);
+  T* Y = reinterpret_cast<T*>(p.y);
+  for (unsigned r0 = blockIdx.y * QR_U; r0 < rows; r0 += gridDim.y * QR_U) {
+    u32x4 raw[QR_U];
+    f32x4 co[QR_U], si[QR_U];
+#pragma unroll
+    for (int u = 0; u < QR_U; ++u) {
+      const unsigned r = r0 + u < rows ? r0 + u : rows - 1;
+      raw[u] = *reinterpret_cast<const u32x4*>(X + (size_t)r * p.lda + ch * 8);
+      const float* c_ = cs + (size_t)r * d + part * 4;                // this chunk's four pairs
+      co[u] = *reinterpret_cast<const f32x4*>(c_);
+      si[u] = *reinterpret_cast<const f32x4*>(c_ + d / 2);
+    }
+#pragma unroll
+    for (int u = 0; u < QR_U; ++u) {
+      if (r0 + u >= rows) break;
+      float f[8], o[8];
+      unpack8<T>(raw[u], f);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        o[2 * k] = f[2 * k] * co[u][k] - f[2 * k + 1] * si[u][k];
+        o[2 * k + 1] = f[2 * k + 1] * co[u][k] + f[2 * k] * si[u][k];
+      }
+      *reinterpret_cast<u32x4*>(Y + (size_t)(r0 + u) * p.ldy + ch * 8) = pack8<T>(o);
+    }
+  }
+}
+
+int qk_rope_launch(const mtx_ew_args* a, void* stream, const char** err) {
+  const int d = a->i0;
+  if (!a->a || !a->y || !a->b || (d != 64 && d != 128) || a->c < d || a->c % d || a->lda % 8 || a->ldy % 8 || a->lda < a->c || a->ldy < a->c) { *err = "qk_rope: head dim must be 64 or 128, c = heads * d, row strides multiples of 8 that cover c"; return MTX_ERR_INVALID; }
+  if (((size_t)a->b & 15) || a->ldb % 4 || a->ldb < 0 || a->i1 < 0) { *err = "qk_rope: the cos | sin table must be 16-byte aligned (ldb % 4 == 0)"; return MTX_ERR_INVALID; }
+  const long rows = a->n * a->h * a->w;
+  if (rows < 1) return MTX_OK;
+  if (rows >= (1L << 31) || a->c / 8 >= (1L << 24)) { *err = "qk_rope: problem too large"; return MTX_ERR_INVALID; }
+  const unsigned gx = (unsigned)((a->c / 8 + 255) / 256);
+  long gy = (rows + QR_U - 1) / QR_U; if (gy > 4096) gy = 4096;
+  if (!MTX_LAUNCH_T(a->dtype, qk_rope_kernel, dim3(gx, (unsigned)gy), dim3(256), stream, *a)) { *err = "qk_rope: dtype"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 

@@ -12,6 +12,8 @@ ACT_NONE, ACT_RELU, ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_SIGMOID, ACT_LEAKY = 
 EW_SHUFFLE2_ADD, EW_CVT_F32, EW_CVT_16 = 16, 17, 18            # fp32 ops only (csrc/f32ops.hip)
 EW_SUB, EW_RESIDUAL_DIST = 19, 20                              # y = a - b; the first-block cache probe (include/mtx_hip.h)
 EW_V_F8T = 21                                                  # v -> e4m3 [head][128][keys], keys in accumulator order per 64-key tile (mtx_attn_args.v_f8t)
+EW_QK_ROPE = 22                                                # rotary turn of q | k without a norm (SAM 3's trunk)
+EW_IM2COL_PATCH = 23                                           # im2col without padding (ViT patch embedding)
 RESDIST_PARTS = 256
 IMG_NCHW_F32_TO_NHWC, IMG_NHWC_TO_NCHW_F32, IMG_NHWC_TO_HWC_U8, IMG_HWC_U8_TO_NHWC = range(4)
 (OP_CONV2D, OP_GEMM, OP_ATTN, OP_NORM, OP_GROUPNORM, OP_EW, OP_CA, OP_IMG, OP_RESIZE_THRESH,

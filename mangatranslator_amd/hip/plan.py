@@ -475,6 +475,17 @@ class PlanBuilder:
             e.y8, e.ldy8, e.y8_mul = _ptr(y8[0]), y8[1], y8[2]
         self._add(abi.OP_EW, e, label)
 
+    def qk_rope(self, qk: Act, cs, d, q_heads=0, ld_cs=0, label="qk_rope"):
+        """MTX_EW_QK_ROPE in place over `qk`, the q | k column view ([rows, 2 * heads * d]) of some token rows: the rotary turn on interleaved
+        pairs, nothing else.  cs: fp32 [rows][2][d / 2] cos | sin rows of the same tokens; with ld_cs > 0 the first `q_heads` heads read the copy
+        ld_cs floats behind it (pre-multiplied by softmax scale * log2(e): the attention then runs with `q_prescaled`)"""
+        e = abi.EwArgs()
+        e.a, e.b, e.s, e.y = qk.ptr, _ptr(cs), None, qk.ptr
+        e.n, e.h, e.w, e.c = 1, 1, qk.w, qk.c
+        e.lda, e.ldb, e.ldy, e.lds = qk.ld, ld_cs, qk.ld, 0
+        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_ROPE, 0, 0.0, d, q_heads, self.dtype
+        self._add(abi.OP_EW, e, label)
+
     def residual_dist(self, after, before, prev, rows, c, parts=None, after_off=0, before_off=0, ld=None, label="residual_dist"):
         """first-block cache probe (include/mtx_hip.h MTX_EW_RESIDUAL_DIST): r = after - before (rounded to the storage type) against `prev`;
         -> fp32 [RESDIST_PARTS, 2]: per part (sum |prev - r|, sum |prev|); `residual_distance(parts)` adds them in index order"""
@@ -583,12 +594,13 @@ class PlanBuilder:
         self._add(abi.OP_EW, e, label)
         return out
 
-    def im2col(self, x: Act, dst, k, stride, ldy, row_map=None, label="im2col"):
+    def im2col(self, x: Act, dst, k, stride, ldy, row_map=None, label="im2col", pad=True):
+        """pad: taps reach k / 2 pixels beyond the image (a padded convolution); False = MTX_EW_IM2COL_PATCH, patches inside the image only"""
         e = abi.EwArgs()
         e.a, e.b, e.s, e.y = x.ptr, None, _ptr(row_map), _ptr(dst)
         e.n, e.h, e.w, e.c = x.n, x.h, x.w, x.c
         e.lda, e.ldb, e.ldy, e.lds = x.ld, 0, ldy, 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_IM2COL, 0, 0.0, k, stride, self.dtype
+        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = (abi.EW_IM2COL if pad else abi.EW_IM2COL_PATCH), 0, 0.0, k, stride, self.dtype
         self._add(abi.OP_EW, e, label)
         return dst
 

@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] ..."""
 import os
 import sys
 
@@ -347,6 +347,48 @@ def norm(rows, c, reps=3, iters=50, q8=False):
     print(f"norm {rows}x{c} {'-> MX fp8' if q8 else 'bf16'}: {t_ms * 1e3:.1f} us  {byts / t_ms / 1e6:.0f} GB/s", flush=True)
 
 
+def sam3(layers=32, boxes=8, iters=5):
+    """SAM 3 (seeded weights, the shipped widths at 1008 x 1008; `layers` < 32 for a quick look): encoder ms at "fast" and "high", decoder ms per
+    `boxes` boxes, and where the encoder's time goes — per group of launches, each group timed in context (`Plan.time_ops`: a replay of the
+    whole plan minus a replay without the group)"""
+    from transformers import Sam3TrackerConfig, Sam3TrackerModel
+    from mangatranslator_amd.core.ml.sam3 import Sam3Hip
+    cfg = Sam3TrackerConfig()
+    bb = cfg.vision_config.backbone_config
+    bb.num_hidden_layers = layers
+    bb.global_attn_indexes = [i for i in bb.global_attn_indexes if i < layers]
+    torch.manual_seed(0)
+    sd = Sam3TrackerModel(cfg).state_dict()
+    T, C, M, d = 72 * 72, bb.hidden_size, bb.intermediate_size, bb.hidden_size // bb.num_attention_heads
+    nglob = len(bb.global_attn_indexes)
+    lin = 2 * T * layers * (4 * C * C + 2 * C * M)
+    att = 4 * C * ((layers - nglob) * T * bb.window_size ** 2 + nglob * T * T)
+    print(f"sam3 work per page, {layers} layers: linears 2 T L (4 C^2 + 2 C M) = {lin / 1e12:.2f} TFLOP, attention 4 C (Lw T w^2 + Lg T^2) = {att / 1e12:.2f} TFLOP "
+          f"(T = {T}, C = {C}, M = {M}, w^2 = {bb.window_size ** 2}, Lg = {nglob})", flush=True)
+    for precision in ("fast", "high"):
+        hipm = Sam3Hip(sd, cfg, device=dev, lib=lib, dtype=abi.F16, precision=precision)
+        pre, enc, dec, post = hipm.plans(boxes, 1536, 1024)
+        enc.img.t.normal_(); dec.tok0.normal_()
+        enc.run(graph=True); dec.run(graph=True); torch.cuda.synchronize()
+        enc.time(2, graph=True); dec.time(2, graph=True)
+        e_ms = min(enc.time(iters, graph=True) for _ in range(3))
+        d_ms = min(dec.time(iters, graph=True) for _ in range(3))
+        print(f"sam3 {precision!r} f16, 1008 x 1008, {layers} layers: encoder {e_ms:.2f} ms ({len(enc.labels)} launches, {(lin * (2 if precision == 'high' else 1) + att) / e_ms / 1e9:.0f} TFLOP/s issued), "
+              f"decoder {d_ms:.2f} ms per {boxes} boxes, pre {pre.time(iters):.3f} ms, post {post.time(iters):.3f} ms", flush=True)
+        globs = {f"layer{i}" for i in bb.global_attn_indexes}
+        groups = {}
+        for i, lb in enumerate(enc.labels):
+            head, _, tail = lb.partition(".")
+            if head.startswith("layer"):
+                key = tail if tail != "attn" else ("attn.global" if head in globs else "attn.window")
+            else:
+                key = head if head.startswith("neck") else lb
+            groups.setdefault(key, []).append(i)
+        parts = {k: enc.time_ops(v, iters) / iters for k, v in groups.items()}
+        print("  per group, ms (launches): " + "  ".join(f"{k} {ms:.3f} ({len(groups[k])})" for k, ms in sorted(parts.items(), key=lambda kv: -kv[1])), flush=True)
+        del hipm
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
@@ -372,6 +414,9 @@ if __name__ == "__main__":
             kontext_psnr(int(args[1]), int(args[2]), int(args[3]), int(args[4])); args = args[5:]
         elif args[0] in ("norm", "normq"):              # norm ROWS C: every norm kernel form in turn
             norm(int(args[1]), int(args[2]), q8=args[0] == "normq"); args = args[3:]
+        elif args[0] == "sam3":                       # sam3 [LAYERS]
+            n = int(args[1]) if len(args) > 1 and args[1].isdigit() else 32
+            sam3(n); args = args[2 if len(args) > 1 and args[1].isdigit() else 1:]
         elif args[0] == "quant":
             quant(int(args[1]), int(args[2])); args = args[3:]
         elif args[0] == "conv":

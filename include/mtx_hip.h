@@ -261,7 +261,8 @@ typedef enum mtx_ew_kind {
                                ConvTranspose2d(k = 2, s = 2) done as a GEMM); y[n, 2h + dy, 2w + dx, ch] = a[...] + b[(n), 2h + dy, 2w + dx, ch] with b
                                optional and lds = its per-sample stride (0 = one image for every n) — SAM's mask upscaling                        */
   MTX_EW_CVT_F32 = 17,    /* fp32 only: y = (float) a, a of the 16-bit type i0 (MTX_F16 / MTX_BF16)                                              */
-  MTX_EW_CVT_16 = 18,     /* fp32 only: y = a rounded to the 16-bit type i0, written i1 (1..4) times side by side: y[px][j * c + ch]             */
+  MTX_EW_CVT_16 = 18,     /* fp32 only: y = a rounded to the 16-bit type i0 (nearest, ties to even, subnormals kept; f16 SATURATES at +-65504 like every
+                             16-bit store of the library, bf16 overflows to infinity), written i1 (1..4) times side by side: y[px][j * c + ch]; ldy >= i1 * c */
   MTX_EW_SUB = 19,        /* y = a - b                                                                                                             */
   MTX_EW_RESIDUAL_DIST = 20, /* first-block cache probe: r = a - b rounded to the 16-bit type, prev = s (same layout, row stride lds); y = fp32
                                 [2 * MTX_RESDIST_PARTS]: y[2 g] = part g of sum |prev - r|, y[2 g + 1] = part g of sum |prev| (fixed summation order; the

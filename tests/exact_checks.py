@@ -28,8 +28,8 @@ ROUNDS_FROM = {abi.BF16: 256.0, abi.F16: 2048.0}         # T's spacing exceeds 1
 INT_CAP = {abi.BF16: 256, abi.F16: 2048}                 # every integer up to here is representable in T (bias / residual range)
 SIGMA = {abi.BF16: 400.0, abi.F16: 3000.0}               # aimed standard deviation of the accumulators: about half of them beyond ROUNDS_FROM
 F16_LIMIT = 60000.0
-MANT = {abi.BF16: 7, abi.F16: 10}
-MIN_EXP = {abi.BF16: -126, abi.F16: -14}
+MANT = {abi.BF16: 7, abi.F16: 10, abi.F32: 23}
+MIN_EXP = {abi.BF16: -126, abi.F16: -14, abi.F32: -126}
 
 
 def _ints(g, shape, r):
@@ -182,28 +182,98 @@ def check_gemm_exact_beyond_4gb(lib, dtype, m, n, k, seed=0):
         _assert_equal(out[rows], ref, f"gemm beyond 4 GB, rows {r0}..")
 
 
+def gemm_f32_kernel_form(m, k, lda, ldw, a_off=0, a_bs=0, w_bs=0, flags=0):
+    """the dispatch rule of gemm_f32_launch (csrc/f32ops.hip), for operands whose buffers start on a 16-byte boundary"""
+    if (m <= 128 and k >= 1024 and k % 4 == 0 and lda % 4 == 0 and ldw % 4 == 0 and a_off % 4 == 0 and a_bs % 4 == 0 and w_bs % 4 == 0
+            and not flags & abi.GEMM_FORCE_TILE256):
+        return "few rows"
+    return "matrix pipe" if m >= 256 or flags & abi.GEMM_FORCE_TILE256 else "vector ALU"
+
+
+GEMM_F32_CASES = [
+    dict(form="vector ALU", m=203, n=77, k=50),
+    dict(form="vector ALU", m=40, n=24, k=32, bt=3),
+    dict(form="matrix pipe", m=300, n=70, k=50, ld_extra=1),                                  # unaligned lda: scalar loads
+    dict(form="matrix pipe", m=513, n=129, k=256),
+    dict(form="matrix pipe", m=260, n=33, k=18, bt=2),
+    dict(form="matrix pipe", m=40, n=9, k=24, flags=abi.GEMM_FORCE_TILE256),
+    dict(form="few rows", m=37, n=50, k=1024),
+    dict(form="few rows", m=72, n=19, k=2048, bt=2),
+    # the shapes the table left out
+    dict(form="matrix pipe", m=300, n=70, k=260),                                             # aligned lda: 16-byte loads, then a 4-wide scalar tail in the last K step
+    dict(form="matrix pipe", m=260, n=33, k=37, ld_extra=3),                                  # odd K on an aligned lda: the last k pair is half filled
+    dict(form="matrix pipe", m=257, n=65, k=37),                                              # odd K, odd lda
+    dict(form="few rows", m=37, n=50, k=1028),                                                # K % 256 != 0: the last lane round is partial (one lane)
+    dict(form="few rows", m=72, n=19, k=1100, bt=2, res_shared=True),                         # ... (19 lanes); one residual for both batches
+    dict(form="vector ALU", m=37, n=50, k=1028, ld_extra=1),                                  # lda % 4 != 0: few rows and a long K, yet the tiled kernel
+    dict(form="vector ALU", m=30, n=4, k=8, bt=5, w_bs_extra=5, c_slice=(7, 3)),              # per-batch weights with a batch stride, output into a column slice
+    dict(form="matrix pipe", m=260, n=33, k=20, bt=2, w_bs_extra=4, res_shared=True, c_slice=(8, 8)),
+    dict(form="few rows", m=9, n=19, k=1024, bt=2, w_bs_extra=8, pick=(3, 2), c_slice=(4, 4)),
+    dict(form="vector ALU", m=5, n=16, k=16, pick=(9, 2)),                                    # rows picked out of a wider matrix (a_off, lda)
+    dict(form="matrix pipe", m=300, n=24, k=16, pick=(2, 1), res_shared=True, bt=2),
+]
+_SENTINEL = -123.0
+
+
 def check_gemm_f32_exact(lib, seed=0):
-    """the fp32 GEMM of csrc/f32ops.hip on integer operands: no rounding anywhere, every kernel form check_f32_ops names —
-    the vector-ALU form, the matrix-pipe form (from 256 rows up; aligned and unaligned lda), the forced matrix-pipe form, few rows with a long K"""
+    """the fp32 GEMM of csrc/f32ops.hip on integer operands: no rounding anywhere, every kernel form check_f32_ops names — the vector-ALU form, the
+    matrix-pipe form (from 256 rows up or forced; aligned and unaligned lda, a K that ends inside a 16-byte load, inside a k pair), few rows with a long
+    K (whole and partial lane rounds) — with bias, RELU, alpha and a residual; per-batch weights with a batch stride (w_bs_extra), a residual shared by
+    all batches (res_shared), rows picked out of a wider matrix (pick = (rows per group NT, which one): lda = NT * row, a_off) and an output into a
+    column slice of a sentinel-filled buffer (c_slice = (extra columns, c_off)) with one spare row behind it.  Every case states the kernel form it is
+    meant for and asserts it from the dispatch rule."""
     g = torch.Generator().manual_seed(seed)
     dev = _dev(lib)
     pb = PlanBuilder(lib, dev, abi.F32)
     checks = []
-    for name, m, n, k, ld_extra, bt, flags in (("vector ALU", 203, 77, 50, 0, 1, 0), ("vector ALU, batch", 40, 24, 32, 0, 3, 0),
-                                               ("matrix pipe, unaligned lda", 300, 70, 50, 1, 1, 0), ("matrix pipe", 513, 129, 256, 0, 1, 0),
-                                               ("matrix pipe, batch", 260, 33, 18, 0, 2, 0), ("matrix pipe, forced", 40, 9, 24, 0, 1, abi.GEMM_FORCE_TILE256),
-                                               ("few rows, long K", 37, 50, 1024, 0, 1, 0), ("few rows, long K, batch", 72, 19, 2048, 0, 2, 0)):
+    for case in GEMM_F32_CASES:
+        cfg = dict(ld_extra=0, bt=1, flags=0, w_bs_extra=None, res_shared=False, pick=None, c_slice=None)
+        cfg.update(case)
+        m, n, k, bt = cfg["m"], cfg["n"], cfg["k"], cfg["bt"]
+        name = ", ".join(f"{key} {v}" for key, v in case.items())
         r = 31
-        a, w = _ints(g, (bt, m, k + ld_extra), r), _ints(g, (n, k), r)
-        b, res = _ints(g, (n,), 4096), _ints(g, (bt, m, n), 4096)
+        row = k + cfg["ld_extra"]
+        nt, which = cfg["pick"] or (1, 0)
+        a_full = _ints(g, (bt, m, nt, row), r)                                               # the unused columns and rows hold integers of the same range
+        a, lda, a_off, a_bs = a_full[:, :, which, :k], nt * row, which * row, m * nt * row
+        if cfg["w_bs_extra"] is None:
+            w_full = _ints(g, (n * k,), r)
+            w, w_bs = w_full.view(1, n, k).expand(bt, n, k), 0
+        else:
+            w_bs = n * k + cfg["w_bs_extra"]
+            w_full = _ints(g, (bt, w_bs), r)
+            w = w_full[:, :n * k].view(bt, n, k)
+            assert bt > 1 and not torch.equal(w[0], w[1])
+        b = _ints(g, (n,), 4096)
+        res = _ints(g, (m, n) if cfg["res_shared"] else (bt, m, n), 4096)
         assert k * r * r * 0.5 + 4096 + 4096 < EXACT
-        ref = F.relu(torch.einsum("bmk,nk->bmn", a[..., :k], w) * 0.5 + b) + res
-        out = pb.gemm(pb.const(a.float()), pb.const(w.float()), m, n, k, lda=k + ld_extra, bias=pb.const(b.float()), act=abi.ACT_RELU,
-                      res=pb.const(res.float()), batch=bt, a_bs=m * (k + ld_extra), c_bs=m * n, res_bs=m * n, alpha=0.5, flags=flags)
-        checks.append((name, out, ref, (bt, m, n)))
+        form = gemm_f32_kernel_form(m, k, lda, k, a_off, a_bs, w_bs, cfg["flags"])
+        assert form == cfg["form"], f"fp32 gemm ({name}): the case is meant for the {cfg['form']} kernel, the dispatch rule gives {form}"
+        ref = F.relu(torch.einsum("bmk,bnk->bmn", a, w) * 0.5 + b) + res
+        whole = None
+        if cfg["c_slice"]:
+            extra, c_off = cfg["c_slice"]
+            ldc = n + extra
+            assert c_off + n <= ldc
+            whole = pb.buf((bt * m + 1, ldc), torch.float32)
+            whole.fill_(_SENTINEL)
+            pb.gemm(pb.const(a_full.float()), pb.const(w_full.float()), m, n, k, lda=lda, a_off=a_off, out=whole, ldc=ldc, c_off=c_off, bias=pb.const(b.float()),
+                    act=abi.ACT_RELU, res=pb.const(res.float()), batch=bt, a_bs=a_bs, w_bs=w_bs, c_bs=m * ldc, res_bs=0 if cfg["res_shared"] else m * n,
+                    alpha=0.5, flags=cfg["flags"])
+            out = whole[:bt * m, c_off:c_off + n]
+        else:
+            out = pb.gemm(pb.const(a_full.float()), pb.const(w_full.float()), m, n, k, lda=lda, a_off=a_off, bias=pb.const(b.float()), act=abi.ACT_RELU,
+                          res=pb.const(res.float()), batch=bt, a_bs=a_bs, w_bs=w_bs, c_bs=m * n, res_bs=0 if cfg["res_shared"] else m * n, alpha=0.5,
+                          flags=cfg["flags"])
+        checks.append((name, out, ref, (bt, m, n), whole, cfg["c_slice"]))
     _run(pb)
-    for name, out, ref, shape in checks:
-        _assert_equal(out.cpu().view(shape), ref, f"fp32 gemm ({name})")
+    for name, out, ref, shape, whole, c_slice in checks:
+        _assert_equal(out.cpu().reshape(shape), ref, f"fp32 gemm ({name})")
+        if whole is not None:
+            keep = torch.ones(whole.shape[-1], dtype=torch.bool, device=whole.device)
+            keep[c_slice[1]:c_slice[1] + shape[2]] = False
+            assert bool((whole[:, keep] == _SENTINEL).all()), f"fp32 gemm ({name}): columns outside the output slice were written"
+            assert bool((whole[-1] == _SENTINEL).all()), f"fp32 gemm ({name}): written beyond the last output row"
 
 
 # ---- conv ---------------------------------------------------------------------------------------------------------------------------------

@@ -32,7 +32,7 @@ SLACK_FLOOR = 2.0 ** -20
 ROW_FLOOR = 2.0 ** -8
 SENTINEL, GARBAGE = -123.0, 7.0                          # outputs' surroundings / inputs' unused columns (both exact in bf16 and f16)
 PATTERNS = ((0, 1), (64, 1), (3, 2), (-64, 1), (0, 4), (-5, 8), (7, 4))      # (m, a) of a balanced row: m = 0; |m| = 64 with a = 1 (the mean far above the deviation); others
-NAME = {abi.BF16: "bf16", abi.F16: "f16"}
+NAME = {abi.BF16: "bf16", abi.F16: "f16", abi.F32: "f32"}
 _FIGURES = {}
 
 

@@ -3,6 +3,7 @@ import pytest
 
 import detector_checks as dc
 import exact_checks as ec
+import f32_checks as fc
 import op_checks as oc
 import operand_checks as pc
 import stream_checks as sc
@@ -517,3 +518,57 @@ def test_letterbox_exact(hip_lib, dtype, cfg):
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
 def test_image_convert_round_trip_beyond_one_grid(hip_lib, dtype):
     dc.check_u8_round_trip_large(hip_lib, dtype)
+
+
+# ---- exact inputs for the fp32 kernels of csrc/f32ops.hip and RCAN's channel attention (f32_checks.py): bitwise where the operands allow it, else within a
+# bound measured from the plain fp32 formula's own distance to float64
+@pytest.mark.parametrize("late_max", [False, True], ids=["plain", "late"])
+def test_attention_f32_tie_sets(hip_lib, late_max):
+    fc.check_attn_f32_ties(hip_lib, late_max=late_max)
+
+
+def test_attention_f32_census(hip_lib):
+    fc.check_attn_f32_census(hip_lib)
+
+
+@pytest.mark.parametrize("cfg", fc.ATTN_GENERAL_CASES, ids=_id)
+def test_attention_f32_general(hip_lib, cfg):
+    fc.check_attn_f32_general(hip_lib, **cfg)
+
+
+@pytest.mark.parametrize("cfg", fc.NORM_F32_BALANCED, ids=_id)
+def test_norm_f32_balanced(hip_lib, cfg):
+    fc.check_norm_f32_balanced(hip_lib, **cfg)
+
+
+@pytest.mark.parametrize("cfg", fc.NORM_F32_BOUNDED, ids=_id)
+def test_norm_f32_census_and_general(hip_lib, cfg):
+    fc.check_norm_f32_bounded(hip_lib, **cfg)
+
+
+def test_elementwise_f32_exact(hip_lib):
+    fc.check_ew_f32_exact(hip_lib)
+
+
+def test_elementwise_f32_grid_stride(hip_lib):
+    """4.2 million elements: the second trip of the grid-stride loop"""
+    fc.check_ew_f32_grid_stride(hip_lib)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_conversions_f32_census(hip_lib, dtype):
+    """every bit pattern of the 16-bit type into fp32; every value, tie and edge of the 16-bit type out of fp32, one to four copies; the refused launches"""
+    fc.check_cvt_f32_all_patterns(hip_lib, dtype)
+    fc.check_cvt_16_census(hip_lib, dtype)
+    fc.check_cvt_16_refusals(hip_lib, dtype)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", fc.CA_CASES, ids=_id)
+def test_channel_attention_exact(hip_lib, dtype, cfg):
+    fc.check_ca_exact(hip_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("cfg", fc.CA_POOLED_CASES, ids=_id)
+def test_channel_attention_pooled_exact(hip_lib, cfg):
+    fc.check_ca_pooled_exact(hip_lib, **cfg)

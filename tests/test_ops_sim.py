@@ -6,6 +6,7 @@ import torch
 
 import detector_checks as dc
 import exact_checks as ec
+import f32_checks as fc
 import op_checks as oc
 import operand_checks as pc
 import stream_checks as sc
@@ -537,3 +538,57 @@ def test_image_convert_valid_hw_and_batch(emu_lib, dtype):
 @pytest.mark.parametrize("cfg", dc.LETTERBOX_CASES, ids=_id)
 def test_letterbox_exact(emu_lib, dtype, cfg):
     dc.check_letterbox(emu_lib, dtype, **cfg)
+
+
+# ---- exact inputs for the fp32 kernels of csrc/f32ops.hip and RCAN's channel attention (f32_checks.py): bitwise where the operands allow it, else within a
+# bound measured from the plain fp32 formula's own distance to float64
+@pytest.mark.parametrize("late_max", [False, True], ids=["plain", "late"])
+def test_attention_f32_tie_sets(emu_lib, late_max):
+    fc.check_attn_f32_ties(emu_lib, late_max=late_max)
+
+
+def test_attention_f32_census(emu_lib):
+    fc.check_attn_f32_census(emu_lib)
+
+
+@pytest.mark.parametrize("cfg", fc.ATTN_GENERAL_CASES, ids=_id)
+def test_attention_f32_general(emu_lib, cfg):
+    fc.check_attn_f32_general(emu_lib, **cfg)
+
+
+@pytest.mark.parametrize("cfg", fc.NORM_F32_BALANCED, ids=_id)
+def test_norm_f32_balanced(emu_lib, cfg):
+    fc.check_norm_f32_balanced(emu_lib, **cfg)
+
+
+@pytest.mark.parametrize("cfg", fc.NORM_F32_BOUNDED, ids=_id)
+def test_norm_f32_census_and_general(emu_lib, cfg):
+    fc.check_norm_f32_bounded(emu_lib, **cfg)
+
+
+def test_elementwise_f32_exact(emu_lib):
+    fc.check_ew_f32_exact(emu_lib)
+
+
+def test_elementwise_f32_grid_stride(emu_lib):
+    """4.2 million elements: the second trip of the grid-stride loop"""
+    fc.check_ew_f32_grid_stride(emu_lib)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+def test_conversions_f32_census(emu_lib, dtype):
+    """every bit pattern of the 16-bit type into fp32; every value, tie and edge of the 16-bit type out of fp32, one to four copies; the refused launches"""
+    fc.check_cvt_f32_all_patterns(emu_lib, dtype)
+    fc.check_cvt_16_census(emu_lib, dtype)
+    fc.check_cvt_16_refusals(emu_lib, dtype)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("cfg", fc.CA_CASES, ids=_id)
+def test_channel_attention_exact(emu_lib, dtype, cfg):
+    fc.check_ca_exact(emu_lib, dtype, **cfg)
+
+
+@pytest.mark.parametrize("cfg", fc.CA_POOLED_CASES, ids=_id)
+def test_channel_attention_pooled_exact(emu_lib, cfg):
+    fc.check_ca_pooled_exact(emu_lib, **cfg)

@@ -36,7 +36,7 @@ extern "C" {
 #define MTX_API
 #endif
 
-#define MTX_ABI_VERSION 10
+#define MTX_ABI_VERSION 11
 
 typedef enum mtx_status {
   MTX_OK = 0,
@@ -526,10 +526,43 @@ typedef struct mtx_textcolor_args {
   int32_t n, page_h, page_w, max_pixels;   /* max_pixels = largest crop area */
 } mtx_textcolor_args;
 
+/* ---- ABI 11: the two ops of an autoregressive decode step (csrc/decode.hip; manga-ocr's BERT decoder, reference core/ml/model_manager.py:835-904).
+ * Single-query attention over a key / value cache whose length lives in DEVICE memory, so one captured step graph serves every token:
+ *   qkv      this step's fused projection rows [rows][q | k | v], each heads * d wide (16-bit, row stride ld_qkv)
+ *   k_cache, v_cache   [max_len][slots][heads * d]
+ *   pos      DEVICE int32: the number of positions already cached, 0 <= pos < max_len (outside that range the launch does nothing)
+ *   src      DEVICE int32 [max_len][slots]: the history of row r at position j < pos lies in slot src[j][r]
+ * Effect: row r's k and v are written to cache[pos][r]; then o[r, h] = softmax_j(scale * q[r, h] . K_j) V_j over j = 0 .. pos, K_j / V_j from
+ * cache[j][src[j][r]] for j < pos and the row's own k / v for j = pos.  Scores, softmax and accumulation in fp32, ONE rounding to `dtype`.
+ * No position beyond pos and no slot >= rows is read or written (given src[j][r] < rows); within a launch row r writes only its own slot at
+ * pos and reads other slots only below pos: no ordering hazard.  A beam reorder never moves cache data — between steps the host rewrites
+ * src'[j][r'] = src[j][parent[r']] for j <= pos (src[pos][r] = r).  rows <= slots <= 8; d == 64 is the only head width built
+ * (MTX_ERR_UNSUPPORTED otherwise); pointers 16-byte aligned, ld_qkv % 8 == 0, ld_o % 8 == 0.
+ * dtype MTX_F32: qkv, the caches and o are fp32 (the recogniser's precision "high"), no rounding at all. */
+typedef struct mtx_decode_attn_args {
+  const void* qkv; void* k_cache; void* v_cache; const int32_t* pos; const int32_t* src; void* o;
+  int32_t rows, slots, heads, d, max_len;
+  int64_t ld_qkv, ld_o;
+  float scale; int32_t dtype;
+} mtx_decode_attn_args;
+
+/* Skinny-row linear of the decode step: c[r, n] = act(alpha * sum_k a[r, k] * w[n, k] + bias[n]) (+ res[r, n]) for rows <= 8 — weight streaming:
+ * a wave owns a few output columns and reduces K inside itself, so N spreads over the whole chip.  16-bit a [rows][lda], w [n][ldw], res
+ * [rows][ldres]; fp32 accumulation; c is `dtype` or, with out_dtype == MTX_F32, fp32 (the vocabulary logits).  Rounding contract of mtx_gemm:
+ * t = round_T(act(alpha * acc + bias)), c = t without a residual (ONE rounding), c = round_T(t + res) with one (TWO); fp32 output: no rounding,
+ * c = act(alpha * acc + bias) + res.  K % 8 == 0, lda % 8 == 0, ldw % 8 == 0, a and w 16-byte aligned; alpha == 0 means 1.
+ * dtype MTX_F32: a, w, res and c are fp32 (out_dtype MTX_F32), no rounding. */
+typedef struct mtx_rowlin_args {
+  const void* a; const void* w; const float* bias; const void* res; void* c;
+  int64_t rows, n, k, lda, ldw, ldc, ldres;
+  int32_t act; float act_param; float alpha; int32_t dtype; int32_t out_dtype;
+} mtx_rowlin_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
-  MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17
+  MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17,
+  MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -546,6 +579,7 @@ typedef struct mtx_op {
     mtx_conv2d_args conv; mtx_gemm_args gemm; mtx_attn_args attn; mtx_norm_args norm;
     mtx_groupnorm_args gn; mtx_ew_args ew; mtx_ca_args ca; mtx_img_args img;
     mtx_resize_thresh_args rt; mtx_memset_args ms; mtx_mask_select_args sel; mtx_preproc_args pre; mtx_yolo_decode_args yd; mtx_detr_args detr; mtx_quant_args quant; mtx_tail_args tail; mtx_textcolor_args tc;
+    mtx_decode_attn_args dattn; mtx_rowlin_args rowlin;
   } u;
 } mtx_op;
 
@@ -578,6 +612,8 @@ MTX_API int mtx_detr(const mtx_detr_args* a, void* stream);
 MTX_API int mtx_quantize_mx(const mtx_quant_args* a, void* stream);
 MTX_API int mtx_page_tail(const mtx_tail_args* a, void* stream);
 MTX_API int mtx_text_color(const mtx_textcolor_args* a, void* stream);
+MTX_API int mtx_decode_attention(const mtx_decode_attn_args* a, void* stream);
+MTX_API int mtx_row_linear(const mtx_rowlin_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

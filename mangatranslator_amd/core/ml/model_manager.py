@@ -205,6 +205,7 @@ class ModelManager:
                 ModelType.FLUX_KONTEXT_SDNQ_PIPELINE: model_dir / "flux" / "kontext",
                 ModelType.FLUX_KLEIN_4B_PIPELINE: model_dir / "flux" / "klein-4b",
                 ModelType.FLUX_KLEIN_9B_PIPELINE: model_dir / "flux" / "klein-9b",
+                ModelType.MANGA_OCR: model_dir / "manga-ocr-base",                                             # reference :133
             }
             self.hf_token = None
             self.flux_hf_token = None
@@ -372,6 +373,9 @@ class ModelManager:
             if not self.is_loaded(model_type) and not replicas:
                 return
             log_message(f"Unloading {model_type.value}...", verbose=verbose)
+            old = self.models.get(model_type)
+            if model_type is ModelType.MANGA_OCR and hasattr(old, "close"):
+                old.close()                                   # its plans and graphs (a recogniser a deployment put in the slot has none)
             self.models[model_type] = None
             for key in replicas:
                 del self.models[key]
@@ -387,8 +391,12 @@ class ModelManager:
         empty_cache(self.device)
 
     def unload_ocr_models(self, verbose: bool = False):
-        """reference :1391-1396 (the OCR recognisers themselves are outside the hot path; only the OSB text detector slot lives here)"""
-        self.unload_model(ModelType.YOLO_OSBTEXT, verbose=verbose)
+        """reference :1397-1420: the OSB text detector, and the manga-ocr recogniser this manager built itself (it can be built again from
+        the staged directory; a recogniser object a deployment put in the slot stays, as it always has)"""
+        self.unload_model(ModelType.YOLO_OSBTEXT, force_gc=False, verbose=verbose)
+        if hasattr(self.models.get(ModelType.MANGA_OCR), "close"):
+            self.unload_model(ModelType.MANGA_OCR, force_gc=False, verbose=verbose)
+        empty_cache(self.device)
 
     def unload_flux_kontext_sdnq_models(self, verbose: bool = False):
         self.unload_model(ModelType.FLUX_KONTEXT_SDNQ_PIPELINE, verbose=verbose)
@@ -638,14 +646,37 @@ class ModelManager:
             log_message("Panel detector loaded.", verbose=verbose)
             return self._maybe_batched(slot, model)
 
+    def manga_ocr_available(self) -> bool:
+        """a recogniser sits in the slot, or a checkpoint is staged for `get_manga_ocr` to build one from"""
+        return self.is_loaded(ModelType.MANGA_OCR) or (self.model_paths[ModelType.MANGA_OCR] / "config.json").is_file()
+
     def get_manga_ocr(self, verbose: bool = False):
-        """manga-ocr recogniser slot (reference :856-904).  The OCR side is outside the MI355X hot path: whatever recogniser object a
-        deployment put in the slot is handed out, otherwise ModelError — which `extract_text_with_manga_ocr` turns into the reference's
-        "[OCR FAILED]" markers."""
+        """manga-ocr recogniser (reference :856-904): whatever recogniser object a deployment put in the slot is handed out; otherwise
+        `MangaOcrHip` (core/ml/manga_ocr.py: ViT encoder + BERT decoder as libmtx_hip graphs, beam search on the host) is built from the
+        directory staged under models/manga-ocr-base and cached in the slot; nothing staged -> ModelError, which
+        `extract_text_with_manga_ocr` turns into the reference's "[OCR FAILED]" markers.  `manga_ocr_storage` ("f16" | "bf16" | "f32") picks the
+        storage type before the first call ("f32": the fp32 kernels throughout)."""
         with self._lock:
             if self.is_loaded(ModelType.MANGA_OCR):
                 return self.models[ModelType.MANGA_OCR]
-            raise ModelError("manga-ocr is not part of this build (OCR side); load the reference's recogniser into ModelType.MANGA_OCR")
+            root = self.model_paths[ModelType.MANGA_OCR]
+            if not (root / "config.json").is_file():
+                raise ModelError(f"manga-ocr is not staged ({root}); stage the checkpoint directory or load a recogniser into ModelType.MANGA_OCR")
+            log_message("Initializing manga-ocr...", verbose=verbose)
+            try:
+                from ...hip import abi
+                from .manga_ocr import MangaOcrHip
+                storage = getattr(self, "manga_ocr_storage", "f16")
+                if storage not in ("f16", "bf16", "f32"):
+                    raise ModelError(f"manga_ocr_storage must be 'f16', 'bf16' or 'f32', not {storage!r}")
+                model = MangaOcrHip.from_directory(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16, "f32": abi.F32}[storage])
+            except ModelError:
+                raise
+            except Exception as e:
+                raise ModelError(f"Failed to load manga-ocr: {e}") from e
+            self.models[ModelType.MANGA_OCR] = model
+            log_message("manga-ocr initialized", verbose=verbose)
+            return model
 
     def get_paddle_ocr_vl(self, verbose: bool = False):
         """(processor, model) slot of PaddleOCR-VL (reference :927-980); see `get_manga_ocr`"""

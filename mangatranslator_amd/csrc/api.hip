@@ -31,6 +31,8 @@ int detr_launch(const mtx_detr_args*, void*, const char**);
 int quant_launch(const mtx_quant_args*, void*, const char**);
 int tail_launch(const mtx_tail_args*, void*, const char**);
 int textcolor_launch(const mtx_textcolor_args*, void*, const char**);
+int decode_attn_launch(const mtx_decode_attn_args*, void*, const char**);
+int rowlin_launch(const mtx_rowlin_args*, void*, const char**);
 
 static thread_local std::string g_err;
 
@@ -78,6 +80,8 @@ static int run_op(const mtx_op& op, void* stream) {
     case MTX_OP_QUANT: rc = quant_launch(&op.u.quant, stream, &err); break;
     case MTX_OP_TAIL: rc = tail_launch(&op.u.tail, stream, &err); break;
     case MTX_OP_TEXTCOLOR: rc = textcolor_launch(&op.u.tc, stream, &err); break;
+    case MTX_OP_DECODE_ATTN: rc = decode_attn_launch(&op.u.dattn, stream, &err); break;
+    case MTX_OP_ROWLIN: rc = rowlin_launch(&op.u.rowlin, stream, &err); break;
     case MTX_OP_MEMSET:
       if (op.u.ms.bytes < 0 || (!op.u.ms.ptr && op.u.ms.bytes > 0)) { rc = MTX_ERR_INVALID; err = "memset: null pointer or negative size"; break; }
       fill_bytes_async(op.u.ms.ptr, op.u.ms.value, (size_t)op.u.ms.bytes, stream);        // a kernel: a captured hipMemsetAsync (memset node) did not always clear (mtx_device.h)
@@ -175,6 +179,8 @@ size_t mtx_abi_sizeof(int kind) {
     case MTX_OP_QUANT: return sizeof(mtx_quant_args);
     case MTX_OP_TAIL: return sizeof(mtx_tail_args);
     case MTX_OP_TEXTCOLOR: return sizeof(mtx_textcolor_args);
+    case MTX_OP_DECODE_ATTN: return sizeof(mtx_decode_attn_args);
+    case MTX_OP_ROWLIN: return sizeof(mtx_rowlin_args);
     case 100: return sizeof(mtx_clean_args);       /* op-level only (not a plan op) */
     default: return 0;
   }
@@ -239,6 +245,8 @@ MTX_OP_ENTRY(mtx_detr, mtx_detr_args, detr_launch)
 MTX_OP_ENTRY(mtx_quantize_mx, mtx_quant_args, quant_launch)
 MTX_OP_ENTRY(mtx_page_tail, mtx_tail_args, tail_launch)
 MTX_OP_ENTRY(mtx_text_color, mtx_textcolor_args, textcolor_launch)
+MTX_OP_ENTRY(mtx_decode_attention, mtx_decode_attn_args, decode_attn_launch)
+MTX_OP_ENTRY(mtx_row_linear, mtx_rowlin_args, rowlin_launch)
 
 
 int mtx_gemm_last_split(int* whole_tiles, int* k_slices, int* tail_pieces) {

@@ -2,7 +2,7 @@
 mtx_abi_sizeof() when the library is opened)."""
 import ctypes as C
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # enums
 BF16, F16, F32, U8, I32, F8 = 0, 1, 2, 3, 4, 5
@@ -18,6 +18,7 @@ RESDIST_PARTS = 256
 IMG_NCHW_F32_TO_NHWC, IMG_NHWC_TO_NCHW_F32, IMG_NHWC_TO_HWC_U8, IMG_HWC_U8_TO_NHWC = range(4)
 (OP_CONV2D, OP_GEMM, OP_ATTN, OP_NORM, OP_GROUPNORM, OP_EW, OP_CA, OP_IMG, OP_RESIZE_THRESH,
  OP_MEMSET, OP_MASK_SELECT, OP_PREPROC, OP_YOLO_DECODE, OP_DETR, OP_QUANT, OP_TAIL, OP_TEXTCOLOR) = range(1, 18)
+OP_DECODE_ATTN, OP_ROWLIN = 18, 19                             # the decode step's two ops (csrc/decode.hip)
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -183,6 +184,21 @@ TC_DIST, TC_MASK, TC_HIST = 0, 1, 2
 TC_RANKS, TC_STAT_ORDER, TC_STATS = 4, 1800, 1808
 
 
+class DecodeAttnArgs(C.Structure):
+    _fields_ = [("qkv", vp), ("k_cache", vp), ("v_cache", vp), ("pos", vp), ("src", vp), ("o", vp),
+                ("rows", i32), ("slots", i32), ("heads", i32), ("d", i32), ("max_len", i32),
+                ("ld_qkv", i64), ("ld_o", i64), ("scale", f32), ("dtype", i32)]
+
+
+class RowLinArgs(C.Structure):
+    _fields_ = [("a", vp), ("w", vp), ("bias", vp), ("res", vp), ("c", vp),
+                ("rows", i64), ("n", i64), ("k", i64), ("lda", i64), ("ldw", i64), ("ldc", i64), ("ldres", i64),
+                ("act", i32), ("act_param", f32), ("alpha", f32), ("dtype", i32), ("out_dtype", i32)]
+
+
+DECODE_MAX_ROWS = 8
+
+
 class CleanArgs(C.Structure):
     _fields_ = [("page_bgr", vp), ("masks", vp), ("rois", vp), ("offsets", vp),
                 ("base", vp), ("roi", vp), ("eroded", vp), ("thresholded", vp), ("shrunk", vp),
@@ -199,7 +215,8 @@ CLEAN_ARGS_KIND = 100      # mtx_abi_sizeof() key of the op-level-only struct
 class _OpUnion(C.Union):
     _fields_ = [("conv", ConvArgs), ("gemm", GemmArgs), ("attn", AttnArgs), ("norm", NormArgs),
                 ("gn", GroupNormArgs), ("ew", EwArgs), ("ca", CaArgs), ("img", ImgArgs),
-                ("rt", ResizeThreshArgs), ("ms", MemsetArgs), ("sel", MaskSelectArgs), ("pre", PreprocArgs), ("yd", YoloDecodeArgs), ("detr", DetrArgs), ("quant", QuantArgs), ("tail", TailArgs), ("tc", TextColorArgs)]
+                ("rt", ResizeThreshArgs), ("ms", MemsetArgs), ("sel", MaskSelectArgs), ("pre", PreprocArgs), ("yd", YoloDecodeArgs), ("detr", DetrArgs), ("quant", QuantArgs), ("tail", TailArgs), ("tc", TextColorArgs),
+                ("dattn", DecodeAttnArgs), ("rowlin", RowLinArgs)]
 
 
 LANE_SIDE, LANE_JOIN = 1, 2
@@ -212,17 +229,19 @@ class Op(C.Structure):
 ARG_TYPES = {OP_CONV2D: ConvArgs, OP_GEMM: GemmArgs, OP_ATTN: AttnArgs, OP_NORM: NormArgs,
              OP_GROUPNORM: GroupNormArgs, OP_EW: EwArgs, OP_CA: CaArgs, OP_IMG: ImgArgs,
              OP_RESIZE_THRESH: ResizeThreshArgs, OP_MEMSET: MemsetArgs,
-             OP_MASK_SELECT: MaskSelectArgs, OP_PREPROC: PreprocArgs, OP_YOLO_DECODE: YoloDecodeArgs, OP_DETR: DetrArgs, OP_QUANT: QuantArgs, OP_TAIL: TailArgs, OP_TEXTCOLOR: TextColorArgs}
+             OP_MASK_SELECT: MaskSelectArgs, OP_PREPROC: PreprocArgs, OP_YOLO_DECODE: YoloDecodeArgs, OP_DETR: DetrArgs, OP_QUANT: QuantArgs, OP_TAIL: TailArgs, OP_TEXTCOLOR: TextColorArgs,
+             OP_DECODE_ATTN: DecodeAttnArgs, OP_ROWLIN: RowLinArgs}
 UNION_FIELD = {OP_CONV2D: "conv", OP_GEMM: "gemm", OP_ATTN: "attn", OP_NORM: "norm",
                OP_GROUPNORM: "gn", OP_EW: "ew", OP_CA: "ca", OP_IMG: "img",
-               OP_RESIZE_THRESH: "rt", OP_MEMSET: "ms", OP_MASK_SELECT: "sel", OP_PREPROC: "pre", OP_YOLO_DECODE: "yd", OP_DETR: "detr", OP_QUANT: "quant", OP_TAIL: "tail", OP_TEXTCOLOR: "tc"}
+               OP_RESIZE_THRESH: "rt", OP_MEMSET: "ms", OP_MASK_SELECT: "sel", OP_PREPROC: "pre", OP_YOLO_DECODE: "yd", OP_DETR: "detr", OP_QUANT: "quant", OP_TAIL: "tail", OP_TEXTCOLOR: "tc",
+               OP_DECODE_ATTN: "dattn", OP_ROWLIN: "rowlin"}
 
 # every symbol include/mtx_hip.h declares (tests check the built library exports all of them)
 EXPORTS = [
     "mtx_abi_version", "mtx_abi_sizeof", "mtx_last_error", "mtx_init", "mtx_device_info",
     "mtx_conv2d", "mtx_conv2d_tiles", "mtx_gemm", "mtx_gemm_last_split", "mtx_attention", "mtx_norm", "mtx_groupnorm",
     "mtx_elementwise", "mtx_channel_attention", "mtx_image_convert", "mtx_resize_threshold",
-    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
+    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
     "mtx_plan_create", "mtx_plan_run", "mtx_plan_run_graph", "mtx_plan_num_ops",
     "mtx_plan_run_range", "mtx_plan_destroy", "mtx_plan_time", "mtx_plan_time_range", "mtx_plan_time_ops",
 ]

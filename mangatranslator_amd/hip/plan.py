@@ -396,6 +396,32 @@ class PlanBuilder:
         self._add(abi.OP_ATTN, a, label)
         return o
 
+    def decode_attention(self, qkv, k_cache, v_cache, pos, src, o, rows, slots, heads, d, max_len, scale, ld_qkv=None, ld_o=None,
+                         label="decode_attn"):
+        """MTX_OP_DECODE_ATTN: one query per (row, head) over the caches [max_len, slots, heads * d]; `pos` (int32 scalar) and `src` (int32
+        [max_len, slots], the slot that holds row r's history at position j) live on the device, so the recorded op serves every step"""
+        a = abi.DecodeAttnArgs()
+        a.qkv, a.k_cache, a.v_cache, a.pos, a.src, a.o = _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos), _ptr(src), _ptr(o)
+        a.rows, a.slots, a.heads, a.d, a.max_len = rows, slots, heads, d, max_len
+        a.ld_qkv, a.ld_o = (ld_qkv or 3 * heads * d), (ld_o or heads * d)
+        a.scale, a.dtype = scale, self.dtype
+        self._add(abi.OP_DECODE_ATTN, a, label)
+        return o
+
+    def row_linear(self, a_t, w_t, rows, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE, res=None, ldres=None,
+                   alpha=1.0, out_f32=False, label="rowlin"):
+        """MTX_OP_ROWLIN: the skinny-row (rows <= 8) linear of a decode step, same epilogue and rounding contract as `gemm`"""
+        if out is None:
+            out = self.buf((rows, n), torch.float32 if out_f32 else self.tdtype)
+        g = abi.RowLinArgs()
+        g.a, g.w, g.bias, g.res, g.c = _ptr(a_t), _ptr(w_t), _ptr(bias), _ptr(res), _ptr(out)
+        g.rows, g.n, g.k = rows, n, k
+        g.lda, g.ldw, g.ldc, g.ldres = (lda or k), (ldw or k), (ldc or n), (ldres or n)
+        g.act, g.act_param, g.alpha = act, 0.0, alpha
+        g.dtype, g.out_dtype = self.dtype, (abi.F32 if out_f32 else self.dtype)
+        self._add(abi.OP_ROWLIN, g, label)
+        return out
+
     def v_f8t(self, v, rows, heads, ldv, v_off=0, out=None, label="v_f8t"):
         """MTX_EW_V_F8T: the value rows [rows, heads * 128] (16-bit, row stride ldv) as e4m3 V^T [heads * 128, ld] with ld = rows padded to 64, keys in
         accumulator order inside every 64-key tile — the operand of `attention(pv_f8=...)`.  -> (tensor, ld)"""
@@ -569,9 +595,10 @@ class PlanBuilder:
         self._add(abi.OP_EW, e, label)
         return dst16
 
-    def cvt_f32(self, x: Act, src_dtype: int, label="cvt_f32") -> Act:
-        """fp32 copy of a 16-bit activation (`src_dtype` = its abi dtype)"""
-        out = self.act(x.n, x.h, x.w, x.c) if self.dtype == abi.F32 else Act(self.buf((x.n, x.h, x.w, x.c), torch.float32), x.n, x.h, x.w, x.c)
+    def cvt_f32(self, x: Act, src_dtype: int, label="cvt_f32", out: Optional[Act] = None) -> Act:
+        """fp32 copy of a 16-bit activation (`src_dtype` = its abi dtype); `out`: an fp32 activation of the same shape to write into"""
+        if out is None:
+            out = self.act(x.n, x.h, x.w, x.c) if self.dtype == abi.F32 else Act(self.buf((x.n, x.h, x.w, x.c), torch.float32), x.n, x.h, x.w, x.c)
         e = abi.EwArgs()
         e.a, e.b, e.s, e.y = x.ptr, None, None, out.ptr
         e.n, e.h, e.w, e.c = x.n, x.h, x.w, x.c

@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] ..."""
 import os
 import sys
 
@@ -389,9 +389,60 @@ def sam3(layers=32, boxes=8, iters=5):
         del hipm
 
 
+def mangaocr(dec_layers=2, beams=4, reps=3, iters=20):
+    """manga-ocr at the published widths (ViT-B/16 at 224 px, BERT decoder 768 / 12 heads, vocabulary 6144; seeded weights; the shipped decoder
+    depth is not known: `dec_layers`): encoder ms, ms per decode step with every linear on the skinny-row kernel, on the tile GEMM, and with ONE
+    shape moved to the GEMM — the step graphs built side by side in one process and timed in alternation (whole-graph replays) — and wall ms per
+    crop at 10 and at 300 tokens (encoder + steps with their upload / download, no search)."""
+    import time
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import manga_ocr_checks as mc
+    from mangatranslator_amd.core.ml import manga_ocr as mo
+    dims = dict(mc.REAL, d=dict(mc.REAL["d"], num_hidden_layers=dec_layers))
+    mc.REAL.update(dims)
+    model, pixels = mc.oracle(0, real=True)
+    C, M, V = 768, 3072, 6144
+    shapes = {"qkv": (3 * C, C), "proj": (C, C), "fc1": (M, C), "fc2": (C, M), "head": (V, C)}
+    routes = {"rowlin": lambda r, n, k: "rowlin", "gemm": lambda r, n, k: "gemm"}
+    for name, nk in shapes.items():
+        routes[f"rowlin, {name} on gemm"] = (lambda r, n, k, nk=nk: "gemm" if (n, k) == nk else "rowlin")
+    routes["shipped"] = mo.linear_route
+    models = {k: mc.hip_model(lib, model, abi.F16, rows=beams, gen=dict(max_length=300, num_beams=beams), route=f) for k, f in routes.items()}
+    first = next(iter(models.values()))
+    first.encode_pixels(pixels[0]); torch.cuda.synchronize()
+    enc = first._encoder()
+    enc.time(3, graph=True)
+    print(f"mangaocr f16, {dec_layers} decoder layers, {beams} rows: encoder {min(enc.time(iters, graph=True) for _ in range(reps)):.3f} ms ({len(enc.labels) if hasattr(enc, 'labels') else enc.n_ops} launches)", flush=True)
+    best = {k: 1e9 for k in models}
+    for k, m in models.items():
+        m.encode_pixels(pixels[0])
+        m.step(mo.BeamStep(0, [2] * beams, list(range(beams))))
+        m._stepper().ctl[0] = 150                                  # a mid-length history for the attention
+        m._stepper().time(3, graph=True)
+    for _ in range(reps):                                          # alternate the graphs: same process, same clocks
+        for k, m in models.items():
+            best[k] = min(best[k], m._stepper().time(iters, graph=True))
+    for k, ms in best.items():
+        print(f"  step graph, linears on {k}: {ms:.4f} ms per step ({models[k]._stepper().n_ops} launches)", flush=True)
+    m = models["shipped"]
+    for tokens in (10, 300):
+        walls = []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            m.encode_pixels(pixels[0])
+            for i in range(tokens - 1):
+                m.step(mo.BeamStep(i, [2 + i % 7] * beams, list(range(beams))))
+            walls.append((time.perf_counter() - t0) * 1e3)
+        print(f"  per crop at {tokens} tokens ({beams} beams): {min(walls):.1f} ms wall (encoder + {tokens - 1} steps with upload / download)", flush=True)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
+        if args[0] == "mangaocr":                     # mangaocr [DEC_LAYERS]
+            n = int(args[1]) if len(args) > 1 and args[1].isdigit() else 2
+            mangaocr(n); args = args[2 if len(args) > 1 and args[1].isdigit() else 1:]
+            continue
         if args[0] == "attn":
             attn(int(args[1])); args = args[2:]
         elif args[0] == "attn88":                       # fp8 scores + fp8 P V

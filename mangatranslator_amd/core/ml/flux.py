@@ -40,6 +40,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, PlanBuilder, PlanCache, residual_distance
 from ...utils.exceptions import ModelError
+from . import packing
 from .dit_graph import DiTStep, ModulationCache, Weight, _rows, quantize_weight
 
 
@@ -356,24 +357,19 @@ class FluxVAEHip:
     def _conv_w(self, name, cout_pad=0):
         if name not in self._w:
             w = self.p(name + ".weight").detach().float().cpu()
-            b = self.p(name + ".bias").detach().float().cpu()
-            co, ci, kh, kw = w.shape
-            ci_p, co_p = (ci + 7) // 8 * 8, max(co, cout_pad)
-            wt = torch.zeros(co_p, kh * kw, ci_p)
-            wt[:co, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-            bt = torch.zeros(co_p)
-            bt[:co] = b
-            self._w[name] = (wt.to(self.device, self.tdt).contiguous(), bt.to(self.device).contiguous(), co_p, kh)
+            wt = packing.conv_taps(w, cout_pad=cout_pad)
+            bt = packing.padded_bias(self.p(name + ".bias").detach().float().cpu(), cout_pad)
+            self._w[name] = (packing.on_device(wt, self.device, self.tdt), packing.on_device(bt, self.device), wt.shape[0], w.shape[2])
         return self._w[name]
 
     def _vec(self, name):
         if name not in self._w:
-            self._w[name] = self.p(name).detach().float().to(self.device).contiguous()
+            self._w[name] = packing.on_device(self.p(name).detach(), self.device)
         return self._w[name]
 
     def _lin(self, name):
         if name not in self._w:
-            self._w[name] = (self.p(name + ".weight").detach().to(self.device, self.tdt).contiguous(), self.p(name + ".bias").detach().float().to(self.device).contiguous())
+            self._w[name] = (packing.on_device(self.p(name + ".weight").detach(), self.device, self.tdt), packing.on_device(self.p(name + ".bias").detach(), self.device))
         return self._w[name]
 
     def _conv(self, pb, x, name, stride=1, res=None, pad_mode=0, cout_pad=0):

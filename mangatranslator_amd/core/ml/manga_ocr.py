@@ -41,6 +41,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, PlanBuilder, PlanCache
 from ...utils.exceptions import ModelError
+from . import packing, vit_common
 
 MAX_BEAMS = abi.DECODE_MAX_ROWS
 HEAD_DIM = 64
@@ -389,26 +390,24 @@ class MangaOcrHip:
 
     # ------------------------------------------------------------------------------------------
     def _c(self, t, dtype=None):
-        """a tensor of the model on the device, in storage of its own (a safetensors view may start at any byte; the kernels want 16-byte alignment)"""
-        return t.to(device=self.device, dtype=dtype if dtype is not None else self.tdt, copy=True).contiguous()
+        return packing.on_device(t, self.device, dtype if dtype is not None else self.tdt)
 
     def _pack(self, sd):
+        """every linear as the triple (W, None, bias) of core/ml/packing.py `linear` (no hi + lo weights here), every LayerNorm as (gamma, beta)"""
         hp = self.hp
         f32 = torch.float32
 
         def ln(key):
-            return (self._c(sd[key + ".weight"], f32), self._c(sd[key + ".bias"], f32))
+            return packing.layer_norm(sd, key, self.device)
 
         def lin(*keys):
-            return (self._c(torch.cat([sd[k + ".weight"] for k in keys], 0)), self._c(torch.cat([sd[k + ".bias"] for k in keys], 0), f32))
+            return packing.linear(sd, *keys, device=self.device, dtype=self.tdt)
 
         C, pk = hp["e_dim"], hp["patch"]
         g = hp["image"] // pk
         W = {}
-        wpe = sd["encoder.embeddings.patch_embeddings.projection.weight"]                   # [C, 3, p, p]
-        wk = torch.zeros(C, pk * pk, 8)
-        wk[:, :, :3] = wpe.permute(0, 2, 3, 1).reshape(C, pk * pk, 3)
-        W["pe"] = (self._c(wk.reshape(C, pk * pk * 8)), self._c(sd["encoder.embeddings.patch_embeddings.projection.bias"], f32))
+        W["pe"] = (self._c(packing.patch_embed_rows(sd["encoder.embeddings.patch_embeddings.projection.weight"])), None,       # [C, 3, p, p]
+                   self._c(sd["encoder.embeddings.patch_embeddings.projection.bias"], f32))
         pos = sd["encoder.embeddings.position_embeddings"].reshape(-1, C)
         if pos.shape[0] != g * g + 1:
             raise ModelError("manga-ocr: the encoder's position table does not match its image and patch size")
@@ -438,7 +437,7 @@ class MangaOcrHip:
         h = "decoder.cls.predictions."
         W["h_t"] = lin(h + "transform.dense")
         W["h_ln"] = ln(h + "transform.LayerNorm")
-        W["h_out"] = (self._c(sd[h + "decoder.weight"]), self._c(sd[h + "decoder.bias"], f32))
+        W["h_out"] = lin(h + "decoder")
         self.W = W
 
     # ---- encoder ---------------------------------------------------------------------------------
@@ -459,65 +458,32 @@ class MangaOcrHip:
             pb.row_gather(img.t, cols, pix, P * pk * pk, 8, label="patch_gather")
         else:
             pb.im2col(img, cols, pk, pk, K, pad=False, label="patch_im2col")
-        # the residual stream stays fp32 from the patch embedding to the final LayerNorm: the GEMMs that close a branch add the fp32 residual in
-        # their epilogue and write fp32, the LayerNorms read fp32 and round once to the next linear's operand type (as SAM's "stream32")
+        # the residual stream stays fp32 from the patch embedding to the final LayerNorm (SAM's "stream32", core/ml/vit_common.py)
+        layer_norm, linear, close_branch = vit_common.trunk_helpers(pb, eps, self.tdt, self.dtype, stream32=True)
         x = pb.buf((T, C), torch.float32)
         x[0].copy_(W["e_cls"][0])                                 # class token + its position: written once, the patch GEMM fills rows 1 ..
-        pb.gemm(cols, W["pe"][0], P, C, K, out=x, c_off=C, bias=W["pe"][1], res=W["e_pos"], out_f32=True, res_f32=True, label="patch_embed")
-
-        def norm(t, wb, label):
-            return pb.norm(t, pb.buf((T, C), self.tdt), T, C, gamma=wb[0], beta=wb[1], eps=eps, dtype=abi.F32, out_dtype=self.dtype, label=label)
-
+        close_branch(cols, W["pe"], P, C, K, W["e_pos"], "patch_embed", out=x, c_off=C)
         for i, L in enumerate(self.e_layers):
             tag = f"enc{i}"
-            qkv = pb.gemm(norm(x, L["ln1"], tag + ".ln1"), L["qkv"][0], T, 3 * C, C, bias=L["qkv"][1], label=tag + ".qkv")
+            qkv = linear(layer_norm(x, T, C, L["ln1"], tag + ".ln1"), L["qkv"], T, 3 * C, C, tag + ".qkv")
             o = pb.buf((T, C), self.tdt)
             st = (T * 3 * C, 3 * C, d)
             pb.attention(qkv, qkv, qkv, o, 1, heads, T, T, d, st, st, st, (T * C, C, d), 1.0 / math.sqrt(d), k_off=C, v_off=2 * C, label=tag + ".attn")
-            x1 = pb.gemm(o, L["proj"][0], T, C, C, bias=L["proj"][1], res=x, out_f32=True, res_f32=True, label=tag + ".proj")
-            h = pb.gemm(norm(x1, L["ln2"], tag + ".ln2"), L["fc1"][0], T, hp["e_mlp"], C, bias=L["fc1"][1], act=abi.ACT_GELU, label=tag + ".fc1")
-            x = pb.gemm(h, L["fc2"][0], T, C, hp["e_mlp"], bias=L["fc2"][1], res=x1, out_f32=True, res_f32=True, label=tag + ".fc2")
-        mem = norm(x, W["e_ln"], "enc.ln")
-        Cd = hp["d_dim"]
-        cross = [pb.gemm(mem, L["ckv"][0], T, 2 * Cd, C, bias=L["ckv"][1], label=f"dec{i}.cross_kv") for i, L in enumerate(self.d_layers)]
+            x1 = close_branch(o, L["proj"], T, C, C, x, tag + ".proj")
+            h = linear(layer_norm(x1, T, C, L["ln2"], tag + ".ln2"), L["fc1"], T, hp["e_mlp"], C, tag + ".fc1", act=abi.ACT_GELU)
+            x = close_branch(h, L["fc2"], T, C, hp["e_mlp"], x1, tag + ".fc2")
+        mem = layer_norm(x, T, C, W["e_ln"], "enc.ln")
+        cross = [linear(mem, L["ckv"], T, 2 * hp["d_dim"], C, f"dec{i}.cross_kv") for i, L in enumerate(self.d_layers)]
         plan = pb.build()
         plan.img, plan.mem, plan.cross, plan.tokens = img, mem, cross, T
         self._enc = plan
         return plan
 
     def _pre_plan(self, h, w):
-        """uint8 page -> the encoder's input, exactly as `SamHipBase._pre_plan` (ATen's antialiased uint8 resize, then rescale + normalise)"""
+        """uint8 page -> the encoder's input (ATen's antialiased uint8 resize, then rescale + normalise), as SAM's: core/ml/vit_common.py"""
         if (h, w) not in self._pre:
-            from ..image.device_tail import aten_aa_bilinear_tables
-            enc = self._encoder()
-            pb = PlanBuilder(self.lib, self.device, self.dtype)
-            S = enc.img.h
-            page = pb.buf((h, w, 3), torch.uint8)
-            cur, cur_w = page, w
-            if w != S:
-                b, t, k, bits = aten_aa_bilinear_tables(w, S)
-                tmp = pb.buf((h, S, 3), torch.uint8)
-                pb.resample_u8(cur, tmp, h, S, 3, cur_w * 3, S * 3, pb.const(torch.from_numpy(b.reshape(-1))), pb.const(torch.from_numpy(t.reshape(-1))), k, 0, bits,
-                               label="pre.resize_h")
-                cur, cur_w = tmp, S
-            if h != S:
-                b, t, k, bits = aten_aa_bilinear_tables(h, S)
-                tmp = pb.buf((S, cur_w, 3), torch.uint8)
-                pb.resample_u8(cur, tmp, S, cur_w, 3, cur_w * 3, cur_w * 3, pb.const(torch.from_numpy(b.reshape(-1))), pb.const(torch.from_numpy(t.reshape(-1))), k, 1, bits,
-                               label="pre.resize_v")
-                cur = tmp
-            if self.f32:        # the pre-processing kernel writes 16-bit pixels: normalised in f16, widened into the encoder's fp32 input
-                half = PlanBuilder(self.lib, self.device, abi.F16)
-                staged = half.act(1, S, S, 8, zero=True)
-                pb.hold(staged.t)
-                a = pb.preprocess(cur, staged, S, S, self.mean, self.std, label="pre.normalise")
-                pb.ops[-1].u.pre.dtype = abi.F16
-                pb.cvt_f32(a, abi.F16, label="pre.widen", out=enc.img)
-            else:
-                pb.preprocess(cur, enc.img, S, S, self.mean, self.std, label="pre.normalise")
-            plan = pb.build()
-            plan.page = page
-            self._pre[(h, w)] = plan
+            self._pre[(h, w)] = vit_common.resize_normalise_plan(self.lib, self.device, self.dtype, h, w, self._encoder().img, self.mean, self.std,
+                                                                 widen_f16=self.f32)
         return self._pre[(h, w)]
 
     # ---- decode step -----------------------------------------------------------------------------
@@ -535,8 +501,8 @@ class MangaOcrHip:
 
         def lin(a, wb, n, k, label, act=abi.ACT_NONE, res=None, out_f32=False):
             if self.route(R, n, k) == "rowlin":
-                return pb.row_linear(a, wb[0], R, n, k, bias=wb[1], act=act, res=res, out_f32=out_f32, label=label)
-            return pb.gemm(a, wb[0], R, n, k, bias=wb[1], act=act, res=res, out_f32=out_f32, label=label)
+                return pb.row_linear(a, wb[0], R, n, k, bias=wb[2], act=act, res=res, out_f32=out_f32, label=label)
+            return pb.gemm(a, wb[0], R, n, k, bias=wb[2], act=act, res=res, out_f32=out_f32, label=label)
 
         def norm(t, wb, label):
             """BERT is post-LN: the branch's sum arrives in fp32 (fp32-output linear + 16-bit residual) and is rounded once, after the norm"""

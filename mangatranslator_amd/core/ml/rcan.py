@@ -28,6 +28,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import PlanBuilder, PlanCache
 from ...utils.exceptions import ModelError
+from . import packing
 
 
 def derive_rcan_hparams(sd: dict) -> dict:
@@ -65,26 +66,9 @@ def derive_rcan_hparams(sd: dict) -> dict:
                 mean_shift=("sub_mean.weight" in sd))
 
 
-def pack_conv3x3(w: torch.Tensor, dtype, shuffle: bool = False, cout_pad: int = 0) -> torch.Tensor:
-    """[Cout, Cin, 3, 3] -> [Cout'][9][Cin8] (tap-major, channel-contiguous)."""
-    co, ci, kh, kw = w.shape
-    if shuffle:  # torch PixelShuffle(2) reads channel c*4 + dy*2 + dx; we emit (dy*2+dx)*C + c
-        c = co // 4
-        w = w.view(c, 4, ci, kh, kw).permute(1, 0, 2, 3, 4).reshape(co, ci, kh, kw)
-    ci8 = (ci + 7) // 8 * 8
-    co_p = max(co, cout_pad)
-    out = torch.zeros(co_p, kh * kw, ci8, dtype=torch.float32)
-    out[:co, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-    return out.to(dtype).contiguous()
-
-
-def pack_bias(b: torch.Tensor, shuffle: bool = False, cout_pad: int = 0) -> torch.Tensor:
-    if shuffle:
-        c = b.shape[0] // 4
-        b = b.view(c, 4).t().reshape(-1)
-    out = torch.zeros(max(b.shape[0], cout_pad), dtype=torch.float32)
-    out[:b.shape[0]] = b.float()
-    return out
+def shuffle_order(t: torch.Tensor) -> torch.Tensor:
+    """output channels (dim 0) of a conv that feeds PixelShuffle(2): torch reads channel c * 4 + dy * 2 + dx, the store wants (dy * 2 + dx) * C + c"""
+    return t.view(t.shape[0] // 4, 4, *t.shape[1:]).transpose(0, 1).reshape(t.shape)
 
 
 def read_safetensors_header(path) -> dict:
@@ -142,9 +126,11 @@ class RCANUpscaler:
         W = {}
 
         def conv(name, key, shuffle=False, cout_pad=0):
-            W[name] = (pack_conv3x3(f(sd[key + ".weight"]), dt, shuffle, cout_pad).to(dev),
-                       pack_bias(f(sd[key + ".bias"]), shuffle, cout_pad).to(dev) if key + ".bias" in sd
-                       else torch.zeros(max(sd[key + ".weight"].shape[0], cout_pad), device=dev))
+            w = f(sd[key + ".weight"])
+            b = f(sd[key + ".bias"]) if key + ".bias" in sd else torch.zeros(w.shape[0])
+            if shuffle:
+                w, b = shuffle_order(w), shuffle_order(b)
+            W[name] = (packing.on_device(packing.conv_taps(w, cout_pad=cout_pad), dev, dt), packing.on_device(packing.padded_bias(b, cout_pad), dev))
 
         conv("head", "head.0")
         for g in range(hp["n_resgroups"]):
@@ -152,7 +138,7 @@ class RCANUpscaler:
                 p = f"body.{g}.body.{b}.body"
                 conv(f"g{g}b{b}c1", p + ".0")
                 conv(f"g{g}b{b}c2", p + ".2")
-                W[f"g{g}b{b}ca"] = tuple(f(sd[p + k]).reshape(s).contiguous().to(dev) for k, s in (
+                W[f"g{g}b{b}ca"] = tuple(packing.on_device(f(sd[p + k]).reshape(s), dev) for k, s in (
                     (".3.conv_du.0.weight", (hp["cr"], hp["n_feats"])), (".3.conv_du.0.bias", (hp["cr"],)),
                     (".3.conv_du.2.weight", (hp["n_feats"], hp["cr"])), (".3.conv_du.2.bias", (hp["n_feats"],))))
             conv(f"g{g}tail", f"body.{g}.body.{hp['n_resblocks']}")

@@ -26,6 +26,8 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, AsyncLane, LaneTicket, PlanBuilder, PlanCache, result_tensors
 from ...utils.exceptions import ModelError
+from . import packing
+from .packing import on_device
 from .yolo import _Boxes
 
 
@@ -81,11 +83,7 @@ class RTDetrHip:
         dev, tdt = self.device, self.tdt
 
         def conv(name, w, b, act):
-            co, ci, kh, kw = w.shape
-            ci_p = (ci + 7) // 8 * 8
-            wt = torch.zeros(co, kh * kw, ci_p)
-            wt[:, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-            self.W[name] = (wt.to(dev, tdt).contiguous(), b.float().to(dev).contiguous(), co, kh, act)
+            self.W[name] = (on_device(packing.conv_taps(w), dev, tdt), on_device(b, dev), w.shape[0], w.shape[2], act)
 
         def bn(prefix):
             return {k: sd[f"{prefix}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")}
@@ -94,12 +92,15 @@ class RTDetrHip:
             w, b = sd[src + ".weight"].float(), sd[src + ".bias"].float()
             n, k = w.shape
             n_p, k_p = max(n, pad_out), max(k, pad_in)
-            wp, bp = torch.zeros(n_p, k_p), torch.zeros(n_p)
-            wp[:n, :k], bp[:n] = w, b
-            self.W[name] = (wp.to(dev, tdt).contiguous(), bp.to(dev).contiguous(), n_p, k_p)
+            wp = torch.zeros(n_p, k_p)
+            wp[:n, :k] = w
+            self.W[name] = (on_device(wp, dev, tdt), on_device(packing.padded_bias(b, n_p), dev), n_p, k_p)
 
         def ln(name, src):
-            self.W[name] = (sd[src + ".weight"].float().to(dev).contiguous(), sd[src + ".bias"].float().to(dev).contiguous())
+            self.W[name] = packing.layer_norm(sd, src, dev)
+
+        def stacked(name, *srcs):           # linears that share their input: one GEMM
+            self.W[name] = (on_device(torch.cat([sd[s + ".weight"] for s in srcs]), dev, tdt), on_device(torch.cat([sd[s + ".bias"] for s in srcs]), dev))
 
         relu = abi.ACT_RELU
         act_enc = {"silu": abi.ACT_SILU, "relu": abi.ACT_RELU, "gelu": abi.ACT_GELU}[self.cfg.activation_function]
@@ -148,8 +149,7 @@ class RTDetrHip:
                     w3[:, :, 1, 1] += w1[:, :, 0, 0]
                     conv(f"{blk}{i}.rep{k}", w3, b3 + b1, act_enc)
         a = f"{e}.aifi.0.layers.0"
-        self.W["aifi.qk"] = (torch.cat([sd[a + ".self_attn.q_proj.weight"], sd[a + ".self_attn.k_proj.weight"]]).to(dev, tdt).contiguous(),
-                             torch.cat([sd[a + ".self_attn.q_proj.bias"], sd[a + ".self_attn.k_proj.bias"]]).float().to(dev).contiguous())
+        stacked("aifi.qk", a + ".self_attn.q_proj", a + ".self_attn.k_proj")
         lin("aifi.v", a + ".self_attn.v_proj"); lin("aifi.o", a + ".self_attn.o_proj")
         lin("aifi.fc1", a + ".mlp.fc1"); lin("aifi.fc2", a + ".mlp.fc2")
         ln("aifi.ln1", a + ".self_attn_layer_norm"); ln("aifi.ln2", a + ".final_layer_norm")
@@ -161,15 +161,11 @@ class RTDetrHip:
         lin("qpos0", d + ".query_pos_head.layers.0", pad_in=8); lin("qpos1", d + ".query_pos_head.layers.1")
         for l in range(self.cfg.decoder_layers):
             p = f"{d}.layers.{l}"
-            self.W[f"d{l}.qk"] = (torch.cat([sd[p + ".self_attn.q_proj.weight"], sd[p + ".self_attn.k_proj.weight"]]).to(dev, tdt).contiguous(),
-                                  torch.cat([sd[p + ".self_attn.q_proj.bias"], sd[p + ".self_attn.k_proj.bias"]]).float().to(dev).contiguous())
+            stacked(f"d{l}.qk", p + ".self_attn.q_proj", p + ".self_attn.k_proj")
             lin(f"d{l}.v", p + ".self_attn.v_proj"); lin(f"d{l}.o", p + ".self_attn.o_proj")
             ln(f"d{l}.ln1", p + ".self_attn_layer_norm"); ln(f"d{l}.ln2", p + ".encoder_attn_layer_norm"); ln(f"d{l}.ln3", p + ".final_layer_norm")
-            # sampling offsets and attention weights share their input: one GEMM
-            wo, bo = sd[p + ".encoder_attn.sampling_offsets.weight"], sd[p + ".encoder_attn.sampling_offsets.bias"]
-            wa, ba = sd[p + ".encoder_attn.attention_weights.weight"], sd[p + ".encoder_attn.attention_weights.bias"]
-            self.n_off, self.n_aw = wo.shape[0], wa.shape[0]
-            self.W[f"d{l}.offaw"] = (torch.cat([wo, wa]).to(dev, tdt).contiguous(), torch.cat([bo, ba]).float().to(dev).contiguous())
+            self.n_off, self.n_aw = sd[p + ".encoder_attn.sampling_offsets.weight"].shape[0], sd[p + ".encoder_attn.attention_weights.weight"].shape[0]
+            stacked(f"d{l}.offaw", p + ".encoder_attn.sampling_offsets", p + ".encoder_attn.attention_weights")
             lin(f"d{l}.value", p + ".encoder_attn.value_proj"); lin(f"d{l}.out", p + ".encoder_attn.output_proj")
             lin(f"d{l}.fc1", p + ".mlp.fc1"); lin(f"d{l}.fc2", p + ".mlp.fc2")
             for j in range(3):

@@ -36,6 +36,7 @@ import torch.nn.functional as F
 from ...hip import abi
 from ...hip.plan import Act, PlanBuilder
 from ...utils.exceptions import ModelError
+from . import packing
 from .sam_common import SamHipBase, _cfg_get, window_order      # noqa: F401  (window_order is part of this module's surface)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -79,10 +80,8 @@ class Sam2Hip(SamHipBase):
         C0 = hp["embed"][0]
         bbp = "vision_encoder.backbone."
         # patch embed as GEMM over im2col rows: K = 49 taps x 8 channels (3 real)
-        wpe = sd[bbp + "patch_embed.projection.weight"]                      # [C0,3,7,7]
-        wk = torch.zeros(C0, 49, 8)
-        wk[:, :, :3] = wpe.permute(0, 2, 3, 1).reshape(C0, 49, 3)
-        W["pe"] = (*self._cw(wk.reshape(C0, 392)), self._c(sd[bbp + "patch_embed.projection.bias"], torch.float32))
+        W["pe"] = (*self._cw(packing.patch_embed_rows(sd[bbp + "patch_embed.projection.weight"])),          # [C0, 3, 7, 7] -> [C0, 392]
+                   self._c(sd[bbp + "patch_embed.projection.bias"], torch.float32))
         # position table (hf:638-644), stored in the first stage's window-major order
         pos = F.interpolate(sd[bbp + "pos_embed"], size=(g0, g0), mode="bicubic")
         win = sd[bbp + "pos_embed_window"]
@@ -105,12 +104,12 @@ class Sam2Hip(SamHipBase):
                 blk = dict(dim=dim, dim_out=dim_out, win=win_sz, pool=pool, heads=hp["heads"][si], idx=total,
                            stage_end=(bi == nb - 1))
                 for nm in ("layer_norm1", "layer_norm2"):
-                    blk[nm] = (self._c(sd[p + nm + ".weight"], torch.float32), self._c(sd[p + nm + ".bias"], torch.float32))
+                    blk[nm] = self._ln(sd, p + nm)
                 for nm, key in (("qkv", "attn.qkv"), ("proj", "attn.proj"), ("fc1", "mlp.proj_in"), ("fc2", "mlp.proj_out")):
-                    blk[nm] = (*self._cw(sd[p + key + ".weight"]), self._c(sd[p + key + ".bias"], torch.float32))
+                    blk[nm] = self._lin(sd, p + key)
                     blk[nm + "_n"] = sd[p + key + ".weight"].shape[0]
                 if dim != dim_out:
-                    blk["skip"] = (*self._cw(sd[p + "proj.weight"]), self._c(sd[p + "proj.bias"], torch.float32))
+                    blk["skip"] = self._lin(sd, p + "proj")
                 self.blocks.append(blk)
                 total += 1
         # neck (hf:216-265): convs[n-i] serves level i; levels 0/1 are folded with conv_s0/conv_s1

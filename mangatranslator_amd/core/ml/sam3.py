@@ -24,11 +24,11 @@ import math
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from ...hip import abi
 from ...hip.plan import Act, PlanBuilder
 from ...utils.exceptions import ModelError
+from . import packing
 from .sam_common import SamHipBase, _cfg_get, window_order
 
 SAM3_MEAN = (0.5, 0.5, 0.5)          # IMAGENET_STANDARD_MEAN / _STD of Sam3ImageProcessorFast
@@ -81,18 +81,6 @@ def rope_table(grid: int, window: int, layer_window: int, d: int, theta: float) 
     return tab[torch.from_numpy(window_order(grid, grid, window))].contiguous()
 
 
-def convt_as_conv1x1(wt: torch.Tensor, bt: torch.Tensor, then_w=None, then_b=None):
-    """ConvTranspose2d(k=2, s=2) weights [Cin, Cout, 2, 2] -> the 1x1 conv whose output rows ((dy * 2 + dx) * Cout' + co) the pixel-shuffle store
-    scatters; `then_w` [Cout', Cout] / `then_b`: a 1x1 conv applied right after it, folded in (two chained linear maps)."""
-    w = wt.permute(2, 3, 1, 0)                                         # [dy, dx, Cout, Cin]
-    b = bt
-    if then_w is not None:
-        w = torch.einsum("oc,yxci->yxoi", then_w, w)
-        b = then_w @ bt + then_b
-    co, ci = w.shape[2], w.shape[3]
-    return w.reshape(4 * co, 1, ci), b.repeat(4)
-
-
 class Sam3Hip(SamHipBase):
     NAME = "SAM 3"
     MEAN, STD = SAM3_MEAN, SAM3_STD
@@ -123,33 +111,21 @@ class Sam3Hip(SamHipBase):
         pk, win = hp["vit_patch"], hp["window"]
         bbp = "vision_encoder.backbone."
         # patch embed as GEMM over im2col rows: K = p * p taps x 8 channels (3 real), no bias
-        wpe = sd[bbp + "embeddings.patch_embeddings.projection.weight"]                      # [C, 3, p, p]
-        wk = torch.zeros(C, pk * pk, 8)
-        wk[:, :, :3] = wpe.permute(0, 2, 3, 1).reshape(C, pk * pk, 3)
-        W["pe"] = (*self._cw(wk.reshape(C, pk * pk * 8)), None)
+        W["pe"] = (*self._cw(packing.patch_embed_rows(sd[bbp + "embeddings.patch_embeddings.projection.weight"])), None)       # [C, 3, p, p]
         # position table: the pre-training grid TILED over the input grid (hf3:588-616), stored in window-major order
         pos = sd[bbp + "embeddings.position_embeddings"].reshape(P, P, C)
         idx = torch.arange(g) % P
         pos = pos[idx][:, idx].reshape(g * g, C)
         self.order = torch.from_numpy(window_order(g, g, win))
         W["pos"] = self._c(pos[self.order])
-
-        def ln(key):
-            return (self._c(sd[key + ".weight"], torch.float32), self._c(sd[key + ".bias"], torch.float32))
-
-        def lin(key):
-            return (*self._cw(sd[key + ".weight"]), self._c(sd[key + ".bias"], torch.float32))
-
-        W["ln_pre"] = ln(bbp + "layer_norm")
+        W["ln_pre"] = self._ln(sd, bbp + "layer_norm")
         self.layers = []
         for li in range(hp["layers"]):
             p = f"{bbp}layers.{li}."
             a = p + "attention."
-            qkv_w = torch.cat([sd[a + f"{n}_proj.weight"] for n in "qkv"], 0)
-            qkv_b = torch.cat([sd[a + f"{n}_proj.bias"] for n in "qkv"], 0)
-            self.layers.append(dict(idx=li, win=0 if li in hp["global_layers"] else win, ln1=ln(p + "layer_norm1"), ln2=ln(p + "layer_norm2"),
-                                    qkv=(*self._cw(qkv_w), self._c(qkv_b, torch.float32)), proj=lin(a + "o_proj"),
-                                    fc1=lin(p + "mlp.fc1"), fc2=lin(p + "mlp.fc2")))
+            self.layers.append(dict(idx=li, win=0 if li in hp["global_layers"] else win, ln1=self._ln(sd, p + "layer_norm1"), ln2=self._ln(sd, p + "layer_norm2"),
+                                    qkv=self._lin(sd, a + "q_proj", a + "k_proj", a + "v_proj"), proj=self._lin(sd, a + "o_proj"),
+                                    fc1=self._lin(sd, p + "mlp.fc1"), fc2=self._lin(sd, p + "mlp.fc2")))
         # rotary tables [2][T][2][d / 2]: the plain copy (k heads), then the one the q heads read (times softmax scale * log2(e))
         d = C // hp["heads"]
         fold = (1.0 / math.sqrt(d)) * LOG2E
@@ -161,22 +137,23 @@ class Sam3Hip(SamHipBase):
         D = hp["fpn_dim"]
         nk = "vision_encoder.neck.fpn_layers."
 
-        def conv3(w, b, then_w=None, then_b=None, pad_out=0):
+        def conv3(w, b, then_w=None, then_b=None, cout_round=1):
             """3x3 conv [Co, Ci, 3, 3] (+ a 1x1 conv applied right after it, folded in) in the conv kernel's packing [Co][tap][Ci]"""
             if then_w is not None:
                 w, b = torch.einsum("oc,cikl->oikl", then_w, w), then_w @ b + then_b
-            w, b = F.pad(w, (0, 0, 0, 0, 0, 0, 0, pad_out)), F.pad(b, (0, pad_out))
-            return (self._c(w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, w.shape[1])), self._c(b, torch.float32))
+            taps = packing.conv_taps(w, cout_round=cout_round)
+            return (self._c(taps), self._c(packing.padded_bias(b, taps.shape[0]), torch.float32))
 
-        def conv1(wb):
-            return (self._c(wb[0]), self._c(wb[1], torch.float32))
+        def conv1(wt, bt, then_w=None, then_b=None):
+            w, b = packing.convt2x2_as_conv1x1(wt, bt, then_w, then_b)
+            return (self._c(w), self._c(b, torch.float32))
 
         p1 = [(sd[f"{nk}{i}.proj1.weight"].reshape(D, -1), sd[f"{nk}{i}.proj1.bias"]) for i in range(3)]
         s0 = (sd["mask_decoder.conv_s0.weight"].reshape(-1, D), sd["mask_decoder.conv_s0.bias"])
         s1 = (sd["mask_decoder.conv_s1.weight"].reshape(-1, D), sd["mask_decoder.conv_s1.bias"])
-        W["n0_up1"] = conv1(convt_as_conv1x1(sd[f"{nk}0.scale_layers.0.weight"], sd[f"{nk}0.scale_layers.0.bias"]))
-        W["n0_up2"] = conv1(convt_as_conv1x1(sd[f"{nk}0.scale_layers.2.weight"], sd[f"{nk}0.scale_layers.2.bias"], *p1[0]))
-        W["n1_up"] = conv1(convt_as_conv1x1(sd[f"{nk}1.scale_layers.0.weight"], sd[f"{nk}1.scale_layers.0.bias"], *p1[1]))
+        W["n0_up1"] = conv1(sd[f"{nk}0.scale_layers.0.weight"], sd[f"{nk}0.scale_layers.0.bias"])
+        W["n0_up2"] = conv1(sd[f"{nk}0.scale_layers.2.weight"], sd[f"{nk}0.scale_layers.2.bias"], *p1[0])
+        W["n1_up"] = conv1(sd[f"{nk}1.scale_layers.0.weight"], sd[f"{nk}1.scale_layers.0.bias"], *p1[1])
         W["n2_p1"] = (*self._cw(p1[2][0]), self._c(p1[2][1], torch.float32))
         # what the decoder adds to the image embedding before its first layer: the no-mask dense prompt, and `no_memory_embedding` where the
         # tracker adds it to that level — hft:1007 adds it to the LAST level the neck built, which is the embedding only when the configuration
@@ -184,7 +161,7 @@ class Sam3Hip(SamHipBase):
         fold2 = sd["prompt_encoder.no_mask_embed.weight"].reshape(-1)
         if len(hp["scale_factors"]) == 3:
             fold2 = fold2 + sd["no_memory_embedding"].reshape(-1)
-        W["n0_p2"] = conv3(sd[f"{nk}0.proj2.weight"], sd[f"{nk}0.proj2.bias"], *s0, pad_out=-s0[0].shape[0] % 8)
+        W["n0_p2"] = conv3(sd[f"{nk}0.proj2.weight"], sd[f"{nk}0.proj2.bias"], *s0, cout_round=8)
         W["n1_p2"] = conv3(sd[f"{nk}1.proj2.weight"], sd[f"{nk}1.proj2.bias"], *s1)
         W["n2_p2"] = conv3(sd[f"{nk}2.proj2.weight"], sd[f"{nk}2.proj2.bias"] + fold2)
         self._pack_prompt_decoder(sd, W)

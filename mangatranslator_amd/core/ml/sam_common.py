@@ -17,6 +17,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import Act, AsyncLane, LaneTicket, PlanBuilder, PlanCache, result_tensors
 from ...utils.exceptions import ModelError
+from . import packing, vit_common
 
 
 def _cfg_get(cfg, name, default=None):
@@ -88,7 +89,7 @@ class SamHipBase:
 
     # ------------------------------------------------------------------------------------------
     def _c(self, t, dtype=None):
-        return t.to(device=self.device, dtype=dtype if dtype is not None else self.tdt).contiguous()
+        return packing.on_device(t, self.device, dtype if dtype is not None else self.tdt)
 
     def _cd(self, t):
         """a matrix of the mask decoder in ITS operand type"""
@@ -96,11 +97,14 @@ class SamHipBase:
 
     def _cw(self, w):
         """matrix [N, K] of a trunk / neck linear: (W, None) in the storage type, or with "hilo" the pair (W_hi, W_lo), W_lo = round(W - W_hi)"""
-        if not self.hilo:
-            return self._c(w), None
-        hi = w.to(self.tdt)
-        lo = (w - hi.float()).to(self.tdt)
-        return self._c(hi), self._c(lo)
+        return packing.hi_lo(w, self.device, self.tdt, self.hilo)
+
+    def _lin(self, sd, *keys):
+        """(W, W_lo, bias) of a trunk / neck linear"""
+        return packing.linear(sd, *keys, device=self.device, dtype=self.tdt, hilo=self.hilo)
+
+    def _ln(self, sd, key):
+        return packing.layer_norm(sd, key, self.device)
 
     def _pack_prompt_decoder(self, sd, W):
         """the tables and weights of everything after the encoder into `W` and this object (same key names in both networks' checkpoints)"""
@@ -141,10 +145,10 @@ class SamHipBase:
             sa = L["self_attn"]
             sa["qk"] = (torch.cat([sa["q"][0], sa["k"][0]], 0).contiguous(), torch.cat([sa["q"][1], sa["k"][1]], 0).contiguous())
             for i in (1, 2, 3, 4):
-                L[f"ln{i}"] = (self._c(sd[f"{p}layer_norm{i}.weight"], torch.float32), self._c(sd[f"{p}layer_norm{i}.bias"], torch.float32))
+                L[f"ln{i}"] = self._ln(sd, f"{p}layer_norm{i}")
             self.dec_layers.append(L)
         self.final_attn = attn(md + "final_attn_token_to_image", "k")
-        self.ln_final = (self._c(sd[md + "layer_norm_final_attn.weight"], torch.float32), self._c(sd[md + "layer_norm_final_attn.bias"], torch.float32))
+        self.ln_final = self._ln(sd, md + "layer_norm_final_attn")
         # the kernels move 8 channels at a time: a decoder narrower than 64 (test configurations) gets its last stage's D / 8 channels padded with
         # zero filters — upscale_conv2, the hypernetworks' output rows and the subclass's feat_s0 — which changes no value
         self.c2_pad = pad2 = -(D // 8) % 8
@@ -154,42 +158,21 @@ class SamHipBase:
         def lin_out_padded(key):
             return (self._cd(F.pad(sd[key + ".weight"], (0, 0, 0, pad2))), self._c(F.pad(sd[key + ".bias"], (0, pad2)), torch.float32))
 
-        # ConvTranspose2d(k=2,s=2) [Cin, Cout, 2, 2] -> 1x1 conv rows ((dy*2+dx)*Cout + co)
         for nm in ("upscale_conv1", "upscale_conv2"):
             wt, bt = sd[f"mask_decoder.{nm}.weight"], sd[f"mask_decoder.{nm}.bias"]
             if nm == "upscale_conv2":
                 wt, bt = F.pad(wt, (0, 0, 0, 0, 0, pad2)), F.pad(bt, (0, pad2))
-            ci, co = wt.shape[:2]
-            W[nm] = (self._cd(wt.permute(2, 3, 1, 0).reshape(4 * co, 1, ci)), self._c(bt.repeat(4), torch.float32))
-        W["up_ln"] = (self._c(sd["mask_decoder.upscale_layer_norm.weight"], torch.float32), self._c(sd["mask_decoder.upscale_layer_norm.bias"], torch.float32))
+            w1, b1 = packing.convt2x2_as_conv1x1(wt, bt)
+            W[nm] = (self._cd(w1), self._c(b1, torch.float32))
+        W["up_ln"] = self._ln(sd, "mask_decoder.upscale_layer_norm")
         W["hyper"] = [[lin(f"mask_decoder.output_hypernetworks_mlps.{i}.proj_in"), lin(f"mask_decoder.output_hypernetworks_mlps.{i}.layers.0"),
                        lin_out_padded(f"mask_decoder.output_hypernetworks_mlps.{i}.proj_out")] for i in range(4)]
         W["iou"] = [lin("mask_decoder.iou_prediction_head.proj_in"), lin("mask_decoder.iou_prediction_head.layers.0"),
                     lin("mask_decoder.iou_prediction_head.proj_out")]
 
     def _trunk_helpers(self, pb, eps):
-        """(layer_norm, linear, close_branch) of a pre-norm ViT trunk recorded on `pb`, in this model's arithmetic: every linear carries its weight
-        triple (w, w_lo, bias) from `_cw`; with "stream32" the projections that close a branch take the fp32 residual in their epilogue and write
-        fp32, and the LayerNorms read fp32 and round once, to the storage type of the GEMM that follows"""
-        s32 = self.stream32
-
-        def layer_norm(x, rows, c, wb, label):
-            """the operand of the linears that follow: [rows, c] of the storage type"""
-            y = pb.buf((rows, c), self.tdt)
-            if not s32:
-                return pb.norm(x, y, rows, c, ldy=c, gamma=wb[0], beta=wb[1], eps=eps, label=label)
-            return pb.norm(x, y, rows, c, gamma=wb[0], beta=wb[1], eps=eps, dtype=abi.F32, out_dtype=self.dtype, label=label)
-
-        def linear(a, wb, rows, n_out, k, label, **kw):
-            return pb.gemm(a, wb[0], rows, n_out, k, bias=wb[2], w_lo=wb[1], label=label, **kw)
-
-        def close_branch(a, wb, rows, n_out, k, res, label):
-            """stream <- res + a @ W^T + b"""
-            if not s32:
-                return linear(a, wb, rows, n_out, k, label, res=res)
-            return linear(a, wb, rows, n_out, k, label, res=res, res_f32=True, out_f32=True)
-
-        return layer_norm, linear, close_branch
+        """(layer_norm, linear, close_branch) of the trunk recorded on `pb`, in this model's arithmetic (core/ml/vit_common.py)"""
+        return vit_common.trunk_helpers(pb, eps, self.tdt, self.dtype, self.stream32)
 
     # ------------------------------------------------------------------------------------------
     def _gather_map(self, hs, ws_, win_from, win_to):
@@ -334,32 +317,7 @@ class SamHipBase:
 
     def _pre_plan(self, h, w):
         if (h, w) not in self._pre:
-            enc = self._encoder()
-            pb = PlanBuilder(self.lib, self.device, self.dtype)
-            page = pb.buf((h, w, 3), torch.uint8)
-            # Sam2ImageProcessorFast resizes the uint8 page with torchvision's antialiased bilinear `resize`, i.e. ATen's fixed-point
-            # uint8 kernel (horizontal pass, uint8 intermediate, vertical pass), then rescales and normalises in fp32: the two passes run
-            # with ATen's own taps (core/image/device_tail.py aten_aa_bilinear_tables, pinned against the installed torch), the
-            # normalisation in the preprocess kernel at identity size
-            from ..image.device_tail import aten_aa_bilinear_tables
-            S = enc.img.h
-            cur, cur_h, cur_w = page, h, w
-            if w != enc.img.w:
-                b, t, k, bits = aten_aa_bilinear_tables(w, enc.img.w)
-                tmp = pb.buf((h, enc.img.w, 3), torch.uint8)
-                pb.resample_u8(cur, tmp, h, enc.img.w, 3, cur_w * 3, enc.img.w * 3, pb.const(torch.from_numpy(b.reshape(-1))), pb.const(torch.from_numpy(t.reshape(-1))),
-                               k, 0, bits, label="pre.resize_h")
-                cur, cur_w = tmp, enc.img.w
-            if h != S:
-                b, t, k, bits = aten_aa_bilinear_tables(h, S)
-                tmp = pb.buf((S, cur_w, 3), torch.uint8)
-                pb.resample_u8(cur, tmp, S, cur_w, 3, cur_w * 3, cur_w * 3, pb.const(torch.from_numpy(b.reshape(-1))), pb.const(torch.from_numpy(t.reshape(-1))),
-                               k, 1, bits, label="pre.resize_v")
-                cur, cur_h = tmp, S
-            pb.preprocess(cur, enc.img, S, enc.img.w, self.MEAN, self.STD, label="pre.normalise")
-            plan = pb.build()
-            plan.page = page
-            self._pre[(h, w)] = plan
+            self._pre[(h, w)] = vit_common.resize_normalise_plan(self.lib, self.device, self.dtype, h, w, self._encoder().img, self.MEAN, self.STD)
         return self._pre[(h, w)]
 
     def _post_plan(self, n, h, w):

@@ -28,6 +28,7 @@ from ...hip import abi
 from ...hip.lib import get_library
 from ...hip.plan import AsyncLane, LaneTicket, PlanBuilder, PlanCache, result_tensors
 from ...utils.exceptions import ModelError
+from . import packing
 
 
 def fold_batchnorm(sd: dict) -> dict:
@@ -110,15 +111,14 @@ class YoloSegHip:
 
     def _put(self, name, w, b, cout_pad=0, cin_pad=0):
         """conv weight [co, ci, kh, kw] -> self.W[name] = (taps [co_p, kh * kw, ci_p] zero-padded, bias [co_p], co_p, kh)"""
-        co, ci, kh, kw = w.shape
-        ci_p = max((ci + 7) // 8 * 8, cin_pad)
-        r = self.COUT_ROUND
-        co_p = max((co + r - 1) // r * r, cout_pad)
-        wt = torch.zeros(co_p, kh * kw, ci_p)
-        wt[:co, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-        bt = torch.zeros(co_p)
-        bt[:co] = b
-        self.W[name] = (wt.to(self.device, self.tdt).contiguous(), bt.to(self.device).contiguous(), co_p, kh)
+        wt = packing.conv_taps(w, cin_pad, cout_pad, self.COUT_ROUND)
+        co_p = wt.shape[0]
+        self.W[name] = (packing.on_device(wt, self.device, self.tdt), packing.on_device(packing.padded_bias(b, co_p), self.device), co_p, w.shape[2])
+
+    def _put_convt(self, name, wt, bt):
+        """ConvTranspose2d(k=2, s=2) as the 1x1 conv of the pixel-shuffle store"""
+        w1, b1 = packing.convt2x2_as_conv1x1(wt, bt)
+        self._put(name, w1.reshape(w1.shape[0], -1, 1, 1), b1)              # [4 co, 1, ci] -> [4 co, ci, 1, 1]
 
     def _pack(self, sd):
         self.W = {}
@@ -131,10 +131,7 @@ class YoloSegHip:
             for br, pad in (("cv2", 0), ("cv3", 8), ("cv4", 0)):
                 base = f"model.22.{br}.{l}.2"
                 put(base, sd[base + ".weight"], sd[base + ".bias"], cout_pad=pad)
-        up = sd["model.22.proto.upsample.weight"]                      # [Cin, Cout, 2, 2]
-        ci, co = up.shape[:2]
-        w1 = up.permute(2, 3, 1, 0).reshape(4 * co, ci, 1, 1)
-        put("model.22.proto.upsample", w1, sd["model.22.proto.upsample.bias"].repeat(4))
+        self._put_convt("model.22.proto.upsample", sd["model.22.proto.upsample.weight"], sd["model.22.proto.upsample.bias"])
 
     # ---- graph --------------------------------------------------------------------------------------
     def _conv(self, pb, x, name, stride=1, act=abi.ACT_SILU, out=None, res=None, label=None):

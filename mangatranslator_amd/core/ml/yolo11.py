@@ -21,6 +21,7 @@ import torch
 from ...hip import abi
 from ...hip.plan import Act, PlanBuilder
 from ...utils.exceptions import ModelError
+from .packing import on_device
 from .yolo import YoloSegHip
 
 
@@ -56,7 +57,7 @@ class Yolo11Hip(YoloSegHip):
 
         def put_dw(name, w, b):          # depthwise [C, 1, k, k] -> taps [k*k, C]
             c, _, kh, kw = w.shape
-            self.DW[name] = (w.reshape(c, kh * kw).t().contiguous().to(self.device, self.tdt), b.to(self.device).contiguous(), kh)
+            self.DW[name] = (on_device(w.reshape(c, kh * kw).t(), self.device, self.tdt), on_device(b, self.device), kh)
 
         for k in sd:
             if not k.endswith(".conv.weight"):
@@ -74,9 +75,7 @@ class Yolo11Hip(YoloSegHip):
                 base = f"model.{hi}.{br}.{l}.2"
                 put(base, sd[base + ".weight"], sd[base + ".bias"], cout_pad=pad)
         if self.a["seg"]:
-            up = sd[f"model.{hi}.proto.upsample.weight"]                      # [Cin, Cout, 2, 2]
-            ci, co = up.shape[:2]
-            put(f"model.{hi}.proto.upsample", up.permute(2, 3, 1, 0).reshape(4 * co, ci, 1, 1), sd[f"model.{hi}.proto.upsample.bias"].repeat(4))
+            self._put_convt(f"model.{hi}.proto.upsample", sd[f"model.{hi}.proto.upsample.weight"], sd[f"model.{hi}.proto.upsample.bias"])
         # MLP widths that are not a multiple of 8 (YOLO12: int(1.2 c)): the consumer's input channels are padded to match
         for name in list(self.W):
             if name.endswith(".mlp.1") or name.endswith(".ffn.1"):
@@ -88,7 +87,7 @@ class Yolo11Hip(YoloSegHip):
                     self.W[name] = (wp.contiguous(), b, co, k)
         for k, v in sd.items():
             if k.endswith(".gamma"):
-                self.W[k] = v.to(self.device, self.tdt).contiguous()
+                self.W[k] = on_device(v, self.device, self.tdt)
 
     def _put_qkv(self, base, w, b):
         """1x1 qkv conv re-packed to [Q heads | K heads | V heads] output columns, q / k zero-padded to the head dim"""
@@ -111,7 +110,7 @@ class Yolo11Hip(YoloSegHip):
             wk[h * hd: h * hd + kd], bk[h * hd: h * hd + kd] = w2[o + kd: o + 2 * kd], b[o + kd: o + 2 * kd]
             wv[h * hd: (h + 1) * hd], bv[h * hd: (h + 1) * hd] = w2[o + 2 * kd: o + per], b[o + 2 * kd: o + per]
         wt = torch.cat([wq, wk, wv]).view(3 * nh * hd, 1, cin)
-        self.W[base] = (wt.to(self.device, self.tdt).contiguous(), torch.cat([bq, bk, bv]).to(self.device).contiguous(), 3 * nh * hd, 1)
+        self.W[base] = (on_device(wt, self.device, self.tdt), on_device(torch.cat([bq, bk, bv]), self.device), 3 * nh * hd, 1)
         self.W[base + "#geo"] = (nh, hd, kd)
 
     # ---- blocks ---------------------------------------------------------------------------------------------------------
@@ -197,12 +196,7 @@ class Yolo11Hip(YoloSegHip):
         if p + ".gamma" in self.W:
             g = self.W[p + ".gamma"]
             res = pb.act(x.n, x.h, x.w, out.c)
-            e = abi.EwArgs()
-            e.a, e.b, e.s, e.y = out.ptr, x.ptr, g.data_ptr(), res.ptr
-            e.n, e.h, e.w, e.c = 1, 1, x.n * x.h * x.w, out.c
-            e.lda, e.ldb, e.ldy, e.lds = out.ld, x.ld, res.ld, 0
-            e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_GATE_RES, 0, 0.0, 0, 0, self.dtype
-            pb._add(abi.OP_EW, e, p + ".gamma_res")
+            pb._ew_args(p + ".gamma_res", abi.EW_GATE_RES, out.ptr, res.ptr, (1, 1, x.n * x.h * x.w, out.c), b=x.ptr, s=g.data_ptr(), lda=out.ld, ldb=x.ld, ldy=res.ld)
             return res
         return out
 

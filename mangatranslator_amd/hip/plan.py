@@ -428,11 +428,7 @@ class PlanBuilder:
         ld = (rows + 63) // 64 * 64
         if out is None:
             out = self.buf((heads * 128, ld), torch.uint8, zero=True)
-        e = abi.EwArgs()
-        e.a, e.y8, e.ldy8 = _ptr(v, v_off), out.data_ptr(), ld
-        e.n, e.h, e.w, e.c = 1, 1, rows, heads * 128
-        e.lda, e.kind, e.dtype = ldv, abi.EW_V_F8T, self.dtype
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_V_F8T, _ptr(v, v_off), None, (1, 1, rows, heads * 128), lda=ldv, y8=(out.data_ptr(), ld, 0.0))
         return out, ld
 
     def norm(self, x, y, rows, c, ldx=None, ldy=None, gamma=None, beta=None, eps=1e-6, kind=0,
@@ -467,6 +463,18 @@ class PlanBuilder:
         self._add(abi.OP_GROUPNORM, a, label)
         return out
 
+    def _ew_args(self, label, kind, a, y, nhwc, b=None, s=None, lda=0, ldb=0, ldy=0, lds=0, act=0, act_param=0.0, i0=0, i1=0, dtype=None, y8=None):
+        """one MTX_OP_EW op: the argument block (include/mtx_hip.h mtx_ew_args) filled from pointers and numbers; what is not given stays zero.
+        dtype: None = the builder's; y8 = (pointer, ldy8, y8_mul)"""
+        e = abi.EwArgs()
+        e.a, e.b, e.s, e.y = a, b, s, y
+        e.n, e.h, e.w, e.c = nhwc
+        e.lda, e.ldb, e.ldy, e.lds = lda, ldb, ldy, lds
+        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = kind, act, act_param, i0, i1, (self.dtype if dtype is None else dtype)
+        if y8 is not None:
+            e.y8, e.ldy8, e.y8_mul = y8
+        self._add(abi.OP_EW, e, label)
+
     def ew(self, kind, a_: Act, b: Optional[Act] = None, s=None, out: Optional[Act] = None, lds=0,
            act=abi.ACT_NONE, act_param=0.0, i0=0, i1=0, label="ew", dtype=None) -> Act:
         if out is None:
@@ -479,12 +487,8 @@ class PlanBuilder:
                 out = self.act(a_.n, (a_.h + 2 * pd - i0) // i1 + 1, (a_.w + 2 * pd - i0) // i1 + 1, a_.c)
             else:
                 out = self.act(a_.n, a_.h, a_.w, a_.c)
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = a_.ptr, (b.ptr if b is not None else None), _ptr(s), out.ptr
-        e.n, e.h, e.w, e.c = a_.n, a_.h, a_.w, a_.c
-        e.lda, e.ldb, e.ldy, e.lds = a_.ld, (b.ld if b is not None else 0), out.ld, lds
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = kind, act, act_param, i0, i1, (self.dtype if dtype is None else dtype)
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, kind, a_.ptr, out.ptr, (a_.n, a_.h, a_.w, a_.c), b=(b.ptr if b is not None else None), s=_ptr(s), lda=a_.ld,
+                      ldb=(b.ld if b is not None else 0), ldy=out.ld, lds=lds, act=act, act_param=act_param, i0=i0, i1=i1, dtype=dtype)
         return out
 
     def qk_norm_rope(self, qk: Act, cs, ld_cs, gamma_qk, d, heads, eps=1e-6, y8=None, label="qk_norm_rope"):
@@ -492,50 +496,29 @@ class PlanBuilder:
         fp32 [2 d]: q's vector, then k's) and the rotary turn.  cs: fp32 [rows][2][d / 2] cos | sin rows of the same tokens; the q heads read
         the copy ld_cs floats behind it (pre-multiplied by softmax scale * log2(e), MTX_ATTN_Q_PRESCALED).
         y8 = (e4m3 bytes of the same rows, ldy8, q multiplier): also the plain e4m3 twin of the result (mtx_ew_args.y8; `attention(qk_f8=...)`)"""
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = qk.ptr, _ptr(cs), _ptr(gamma_qk), qk.ptr
-        e.n, e.h, e.w, e.c = 1, 1, qk.w, qk.c
-        e.lda, e.ldb, e.ldy, e.lds = qk.ld, ld_cs, qk.ld, 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_NORM_ROPE, 0, eps, d, heads, self.dtype
-        if y8 is not None:
-            e.y8, e.ldy8, e.y8_mul = _ptr(y8[0]), y8[1], y8[2]
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_QK_NORM_ROPE, qk.ptr, qk.ptr, (1, 1, qk.w, qk.c), b=_ptr(cs), s=_ptr(gamma_qk), lda=qk.ld, ldb=ld_cs, ldy=qk.ld,
+                      act_param=eps, i0=d, i1=heads, y8=None if y8 is None else (_ptr(y8[0]), y8[1], y8[2]))
 
     def qk_rope(self, qk: Act, cs, d, q_heads=0, ld_cs=0, label="qk_rope"):
         """MTX_EW_QK_ROPE in place over `qk`, the q | k column view ([rows, 2 * heads * d]) of some token rows: the rotary turn on interleaved
         pairs, nothing else.  cs: fp32 [rows][2][d / 2] cos | sin rows of the same tokens; with ld_cs > 0 the first `q_heads` heads read the copy
         ld_cs floats behind it (pre-multiplied by softmax scale * log2(e): the attention then runs with `q_prescaled`)"""
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = qk.ptr, _ptr(cs), None, qk.ptr
-        e.n, e.h, e.w, e.c = 1, 1, qk.w, qk.c
-        e.lda, e.ldb, e.ldy, e.lds = qk.ld, ld_cs, qk.ld, 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_QK_ROPE, 0, 0.0, d, q_heads, self.dtype
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_QK_ROPE, qk.ptr, qk.ptr, (1, 1, qk.w, qk.c), b=_ptr(cs), lda=qk.ld, ldb=ld_cs, ldy=qk.ld, i0=d, i1=q_heads)
 
     def residual_dist(self, after, before, prev, rows, c, parts=None, after_off=0, before_off=0, ld=None, label="residual_dist"):
         """first-block cache probe (include/mtx_hip.h MTX_EW_RESIDUAL_DIST): r = after - before (rounded to the storage type) against `prev`;
         -> fp32 [RESDIST_PARTS, 2]: per part (sum |prev - r|, sum |prev|); `residual_distance(parts)` adds them in index order"""
         if parts is None:
             parts = self.buf((abi.RESDIST_PARTS, 2), torch.float32, zero=True)
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = _ptr(after, after_off), _ptr(before, before_off), _ptr(prev), parts.data_ptr()
-        e.n, e.h, e.w, e.c = 1, 1, rows, c
-        e.lda = e.ldb = (ld or c)
-        e.lds, e.ldy = c, 2
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_RESIDUAL_DIST, 0, 0.0, 0, 0, self.dtype
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_RESIDUAL_DIST, _ptr(after, after_off), parts.data_ptr(), (1, 1, rows, c), b=_ptr(before, before_off), s=_ptr(prev),
+                      lda=(ld or c), ldb=(ld or c), ldy=2, lds=c)
         return parts
 
     def dwconv(self, x: Act, w_taps, bias, ksize: int, act=abi.ACT_NONE, out: Optional[Act] = None, label="dwconv") -> Act:
         """depthwise k x k, stride 1 (include/mtx_hip.h MTX_EW_DWCONV): w_taps T [k*k, C], bias fp32 [C] or None"""
         if out is None:
             out = self.act(x.n, x.h, x.w, x.c)
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = x.ptr, _ptr(bias), _ptr(w_taps), out.ptr
-        e.n, e.h, e.w, e.c = x.n, x.h, x.w, x.c
-        e.lda, e.ldb, e.ldy, e.lds = x.ld, 0, out.ld, 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_DWCONV, act, 0.0, ksize, 0, self.dtype
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_DWCONV, x.ptr, out.ptr, (x.n, x.h, x.w, x.c), b=_ptr(bias), s=_ptr(w_taps), lda=x.ld, ldy=out.ld, act=act, i0=ksize)
         return out
 
     def channel_attention(self, chan_sum, w1, b1, w2, b2, s_out, n, tiles, c, cr, inv_hw, label="ca", inv_hw_dev=None,
@@ -575,36 +558,21 @@ class PlanBuilder:
 
     def row_gather(self, src, dst, index_i32, rows, c, lda=None, ldy=None, label="row_gather", dtype=None):
         """dst[r, :c] = src[index[r], :c]  (token re-ordering between window layouts)"""
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = _ptr(src), None, _ptr(index_i32), _ptr(dst)
-        e.n, e.h, e.w, e.c = 1, 1, rows, c
-        e.lda, e.ldb, e.ldy, e.lds = (lda or c), 0, (ldy or c), 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_ROW_GATHER, 0, 0.0, 0, 0, (self.dtype if dtype is None else dtype)
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_ROW_GATHER, _ptr(src), _ptr(dst), (1, 1, rows, c), s=_ptr(index_i32), lda=(lda or c), ldy=(ldy or c), dtype=dtype)
         return dst
 
     # ---- fp32 ops (csrc/f32ops.hip) --------------------------------------------------------------------------------------------------
     def cvt16(self, src_f32, dst16, rows, c, copies=1, lda=None, label="cvt16"):
         """dst16 [rows, >= copies * c] (this builder's 16-bit type) <- src_f32 [rows, c] rounded, written `copies` times side by side"""
         assert self.dtype in (abi.F16, abi.BF16) and src_f32.dtype == torch.float32 and dst16.dtype == self.tdtype
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = _ptr(src_f32), None, None, _ptr(dst16)
-        e.n, e.h, e.w, e.c = 1, 1, rows, c
-        e.lda, e.ldb, e.ldy, e.lds = (lda or c), 0, dst16.shape[-1], 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_CVT_16, 0, 0.0, self.dtype, copies, abi.F32
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_CVT_16, _ptr(src_f32), _ptr(dst16), (1, 1, rows, c), lda=(lda or c), ldy=dst16.shape[-1], i0=self.dtype, i1=copies, dtype=abi.F32)
         return dst16
 
     def cvt_f32(self, x: Act, src_dtype: int, label="cvt_f32", out: Optional[Act] = None) -> Act:
         """fp32 copy of a 16-bit activation (`src_dtype` = its abi dtype); `out`: an fp32 activation of the same shape to write into"""
         if out is None:
             out = self.act(x.n, x.h, x.w, x.c) if self.dtype == abi.F32 else Act(self.buf((x.n, x.h, x.w, x.c), torch.float32), x.n, x.h, x.w, x.c)
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = x.ptr, None, None, out.ptr
-        e.n, e.h, e.w, e.c = x.n, x.h, x.w, x.c
-        e.lda, e.ldb, e.ldy, e.lds = x.ld, 0, out.ld, 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_CVT_F32, 0, 0.0, src_dtype, 0, abi.F32
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_CVT_F32, x.ptr, out.ptr, (x.n, x.h, x.w, x.c), lda=x.ld, ldy=out.ld, i0=src_dtype, dtype=abi.F32)
         return out
 
     def shuffle2_add(self, cols, n, h, w, c, skip: Optional[Act] = None, skip_broadcast: bool = True, label="shuffle2_add") -> Act:
@@ -612,23 +580,13 @@ class PlanBuilder:
         [n, 2h, 2w, c] plus an optional skip feature at output resolution (one image for every n when `skip_broadcast`)"""
         assert self.dtype == abi.F32
         out = self.act(n, 2 * h, 2 * w, c)
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = _ptr(cols), (skip.ptr if skip is not None else None), None, out.ptr
-        e.n, e.h, e.w, e.c = n, h, w, c
-        e.lda, e.ldb, e.ldy = 4 * c, (skip.ld if skip is not None else 0), out.ld
-        e.lds = 0 if (skip is None or skip_broadcast) else 4 * h * w * skip.ld
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = abi.EW_SHUFFLE2_ADD, 0, 0.0, 0, 0, abi.F32
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_SHUFFLE2_ADD, _ptr(cols), out.ptr, (n, h, w, c), b=(skip.ptr if skip is not None else None), lda=4 * c,
+                      ldb=(skip.ld if skip is not None else 0), ldy=out.ld, lds=0 if (skip is None or skip_broadcast) else 4 * h * w * skip.ld, dtype=abi.F32)
         return out
 
     def im2col(self, x: Act, dst, k, stride, ldy, row_map=None, label="im2col", pad=True):
         """pad: taps reach k / 2 pixels beyond the image (a padded convolution); False = MTX_EW_IM2COL_PATCH, patches inside the image only"""
-        e = abi.EwArgs()
-        e.a, e.b, e.s, e.y = x.ptr, None, _ptr(row_map), _ptr(dst)
-        e.n, e.h, e.w, e.c = x.n, x.h, x.w, x.c
-        e.lda, e.ldb, e.ldy, e.lds = x.ld, 0, ldy, 0
-        e.kind, e.act, e.act_param, e.i0, e.i1, e.dtype = (abi.EW_IM2COL if pad else abi.EW_IM2COL_PATCH), 0, 0.0, k, stride, self.dtype
-        self._add(abi.OP_EW, e, label)
+        self._ew_args(label, abi.EW_IM2COL if pad else abi.EW_IM2COL_PATCH, x.ptr, _ptr(dst), (x.n, x.h, x.w, x.c), s=_ptr(row_map), lda=x.ld, ldy=ldy, i0=k, i1=stride)
         return dst
 
     def mask_select(self, logits, iou, counts, sel, n, pix, delta=0.05, thresh=0.98, label="mask_select"):

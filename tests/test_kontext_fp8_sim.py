@@ -88,6 +88,30 @@ def test_plan_dump_names_every_pointer_and_repeats(emu_lib):
         pd.dump(plan, dit)
 
 
+def test_plan_dump_of_a_model_that_is_no_dit(emu_lib):
+    """the same for manga-ocr (f16), with the model object itself as the weight holder: two independent builds give the same text and the same
+    weights digest, a stray pointer raises, and the weights digest moves when one weight element does"""
+    import sys
+    from pathlib import Path
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
+    import plan_dump as pd
+    built = [pd.toy_plan("manga-ocr", emu_lib, variant="f16") for _ in range(2)]
+    dumps = [pd.dump(plans, model) for plans, model in built]
+    plans, model = built[0]
+    assert dumps[0] == dumps[1] and len(dumps[0]) == sum(len(p.ops) for p in plans)
+    assert {ln.split()[0] for ln in dumps[0]} == {"p0", "p1", "p2"} and "0x" not in "".join(dumps[0])
+    assert any(" w=b" in ln and "patch_embed" in ln for ln in dumps[0])                      # a weight of the model, named as a buffer
+    want = pd.weights_digest(model)
+    assert want == pd.weights_digest(built[1][1])
+    w = model.e_layers[1]["fc2"][0]
+    w[3, 5] = w[3, 5] + 1
+    assert pd.weights_digest(model) != want
+    stray = torch.zeros(64, dtype=torch.float16)
+    plans[1].ops[0].u.ew.s = stray.data_ptr()
+    with pytest.raises(LookupError):
+        pd.dump(plans, model)
+
+
 @pytest.fixture()
 def manager(emu_lib, tmp_path, monkeypatch):
     import mangatranslator_amd.hip.lib as libmod

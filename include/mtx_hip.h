@@ -36,7 +36,7 @@ extern "C" {
 #define MTX_API
 #endif
 
-#define MTX_ABI_VERSION 11
+#define MTX_ABI_VERSION 12
 
 typedef enum mtx_status {
   MTX_OK = 0,
@@ -279,7 +279,7 @@ typedef enum mtx_ew_kind {
                              < i1 (the q slice) read their table at b + ldb floats instead — a copy pre-multiplied by
                              the attention scale * log2(e), see MTX_ATTN_Q_PRESCALED                    */
   MTX_EW_QK_ROPE = 22,    /* the rotary turn alone, in place friendly (SAM 3's ViT trunk): a = y = the q | k column view [rows, c = heads * d] of token rows
-                             (16-bit, row strides lda / ldy), i0 = d (64 or 128), b = fp32 [rows][2][d/2] cos | sin, 16-byte aligned; per interleaved pair
+                             (16-bit, row strides lda / ldy), i0 = d (d % 8 == 0, 8 <= d <= 128; ABI 12, before: 64 or 128), b = fp32 [rows][2][d/2] cos | sin, 16-byte aligned; per interleaved pair
                              (x0, x1) -> (x0*cos - x1*sin, x1*cos + x0*sin) in fp32, rounded once.  i1 > 0 and ldb > 0: heads < i1 (the q slice) read the
                              table ldb floats (ldb % 4 == 0) behind b, a copy pre-multiplied by scale * log2(e) (MTX_ATTN_Q_PRESCALED).  Columns beyond c
                              (the v slice of a fused qkv row) are not touched.                                                             */
@@ -558,11 +558,55 @@ typedef struct mtx_rowlin_args {
   int32_t act; float act_param; float alpha; int32_t dtype; int32_t out_dtype;
 } mtx_rowlin_args;
 
+/* ---- ABI 12: causal grouped-query attention that appends to a key / value cache, and the device end of a greedy step (csrc/causal.hip;
+ * PaddleOCR-VL's text decoder, reference core/image/ocr_detection.py:886-962).  One op serves the prompt (rows > 1) and the step (rows == 1):
+ *   qkv      [rows][ q: heads * d | k: kv_heads * d | v: kv_heads * d ], 16-bit, row stride ld_qkv; q and k already rotated
+ *   k_cache, v_cache   [max_len][kv_heads * d]
+ *   pos      DEVICE int32: the number of positions already cached
+ * Effect: row i's k and v are written to cache[pos + i]; o[i, h] = softmax_{j <= pos + i}(scale * q[i, h] . K_j[g]) V_j[g] with
+ * g = h / (heads / kv_heads).  Keys pos .. pos + rows - 1 are taken from the launch's own rows, so no workgroup waits for another's cache
+ * write.  Scores, softmax and accumulation in fp32, ONE rounding to `dtype` (the matrix path of rows > 1 feeds the softmax weights to the
+ * matrix pipe as a high and a low 16-bit half, 16+ bits in all; its scores are fp32 sums of exact 16-bit products).  With pos < 0 or
+ * pos + rows > max_len the launch does nothing; nothing at or beyond pos + rows is read or written.  d == 128 and heads % kv_heads == 0
+ * (MTX_ERR_UNSUPPORTED otherwise); pointers 16-byte aligned, ld_qkv % 8 == 0, ld_o % 8 == 0; dtype MTX_BF16 / MTX_F16.
+ *   rows > 1   MTX_CAUSAL_TQ query rows of one head per workgroup, MTX_CAUSAL_TK-key tiles on the 16x16x32 MFMA; tiles wholly in the
+ *              future are skipped, the diagonal tile is masked.
+ *   rows == 1  a streaming kernel: one workgroup per (MTX_CAUSAL_S keys, kv head) reads each key / value once for all the query heads of
+ *              the group; the partial softmax states go through `workspace` and the workgroup that draws the last ticket merges them in
+ *              key order, so identical calls give identical bytes.  workspace: MTX_CAUSAL_WS_BYTES(heads, max_len) bytes, ZEROED once by
+ *              the caller (the kernel leaves its counters at zero); needed for rows == 1 only. */
+#define MTX_CAUSAL_TQ 64
+#define MTX_CAUSAL_TK 32
+#define MTX_CAUSAL_S 64
+#define MTX_CAUSAL_REC 132       /* floats per partial record: m, l, 2 unused, acc[128] */
+#define MTX_CAUSAL_WS_BYTES(heads, max_len) \
+  ((((int64_t)(heads) * 4 + 255) / 256) * 256 + (int64_t)(heads) * (((int64_t)(max_len) + MTX_CAUSAL_S - 1) / MTX_CAUSAL_S) * MTX_CAUSAL_REC * 4)
+typedef struct mtx_causal_attn_args {
+  const void* qkv; void* k_cache; void* v_cache; const int32_t* pos; void* o;
+  int32_t rows, heads, kv_heads, d, max_len;
+  int64_t ld_qkv, ld_o;
+  float scale; int32_t dtype;
+  void* workspace; int64_t workspace_bytes;
+} mtx_causal_attn_args;
+
+/* The device end of a greedy decode step, so that a run of step replays needs no host round trip.  state: DEVICE int32[4] = {pos, n_out,
+ * done, token}.  With done != 0 the call changes nothing.  Otherwise t = argmax(logits[0 .. vocab)) — the LOWEST index among equal maxima
+ * whatever the launch shape, a NaN never wins (all NaN: 0) — and out[n_out++] = t; token = t; pos += advance;
+ * done = (t in eos[0 .. n_eos)) || n_out == max_new.  vocab < 1, max_new < 1 or n_eos outside 0 .. 4 refuse the launch.
+ * scratch: MTX_GREEDY_SCRATCH_BYTES(vocab) bytes (one (value, index) pair per MTX_GREEDY_CHUNK logits). */
+#define MTX_GREEDY_CHUNK 4096
+#define MTX_GREEDY_SCRATCH_BYTES(vocab) ((((int64_t)(vocab) + MTX_GREEDY_CHUNK - 1) / MTX_GREEDY_CHUNK) * 8)
+typedef struct mtx_greedy_args {
+  const float* logits; int32_t* state; int32_t* out; void* scratch;
+  int32_t vocab, max_new, n_eos, advance;
+  int32_t eos[4];
+} mtx_greedy_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
   MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17,
-  MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19
+  MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19, MTX_OP_CAUSAL_ATTN = 20, MTX_OP_GREEDY = 21
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -579,7 +623,7 @@ typedef struct mtx_op {
     mtx_conv2d_args conv; mtx_gemm_args gemm; mtx_attn_args attn; mtx_norm_args norm;
     mtx_groupnorm_args gn; mtx_ew_args ew; mtx_ca_args ca; mtx_img_args img;
     mtx_resize_thresh_args rt; mtx_memset_args ms; mtx_mask_select_args sel; mtx_preproc_args pre; mtx_yolo_decode_args yd; mtx_detr_args detr; mtx_quant_args quant; mtx_tail_args tail; mtx_textcolor_args tc;
-    mtx_decode_attn_args dattn; mtx_rowlin_args rowlin;
+    mtx_decode_attn_args dattn; mtx_rowlin_args rowlin; mtx_causal_attn_args cattn; mtx_greedy_args greedy;
   } u;
 } mtx_op;
 
@@ -614,6 +658,8 @@ MTX_API int mtx_page_tail(const mtx_tail_args* a, void* stream);
 MTX_API int mtx_text_color(const mtx_textcolor_args* a, void* stream);
 MTX_API int mtx_decode_attention(const mtx_decode_attn_args* a, void* stream);
 MTX_API int mtx_row_linear(const mtx_rowlin_args* a, void* stream);
+MTX_API int mtx_causal_attention(const mtx_causal_attn_args* a, void* stream);
+MTX_API int mtx_greedy_pick(const mtx_greedy_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

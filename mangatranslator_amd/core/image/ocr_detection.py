@@ -340,10 +340,10 @@ class OutsideTextDetector:
 
 
 # ---- OCR recogniser drivers (reference :811-990) ------------------------------------------------------------------------------
-# The recognisers themselves (manga-ocr, PaddleOCR-VL) are the LLM / OCR side of the reference, outside the MI355X hot path (SURVEY.md §8
-# out-of-scope list).  The two drivers keep the reference's contract — one string per image, "[OCR FAILED]" for an image that could not be
-# read, the same marker for every image when the recogniser cannot be had — so `core.outside_text_processor` / `core.services.translation`
-# import and degrade exactly as they do when the reference fails to load the model.
+# Both recognisers are served on the HIP path when their checkpoint is staged (core/ml/manga_ocr.py, core/ml/paddle_ocr_vl.py; ModelManager
+# get_manga_ocr / get_paddle_ocr_vl).  The two drivers keep the reference's contract — one string per image, "[OCR FAILED]" for an image that
+# could not be read, the same marker for every image when the recogniser cannot be had (nothing staged, nothing in the slot) — so
+# `core.outside_text_processor` / `core.services.translation` import and degrade exactly as they do when the reference fails to load the model.
 OCR_FAILED = "[OCR FAILED]"
 
 

@@ -206,6 +206,7 @@ class ModelManager:
                 ModelType.FLUX_KLEIN_4B_PIPELINE: model_dir / "flux" / "klein-4b",
                 ModelType.FLUX_KLEIN_9B_PIPELINE: model_dir / "flux" / "klein-9b",
                 ModelType.MANGA_OCR: model_dir / "manga-ocr-base",                                             # reference :133
+                ModelType.PADDLE_OCR_VL: model_dir / "paddleocr-vl-1.6",                                       # reference :134
             }
             self.hf_token = None
             self.flux_hf_token = None
@@ -376,6 +377,8 @@ class ModelManager:
             old = self.models.get(model_type)
             if model_type is ModelType.MANGA_OCR and hasattr(old, "close"):
                 old.close()                                   # its plans and graphs (a recogniser a deployment put in the slot has none)
+            if model_type is ModelType.PADDLE_OCR_VL and isinstance(old, tuple) and hasattr(old[1], "close"):
+                old[1].close()                                # the pair this manager built: (processor, shim over the plans)
             self.models[model_type] = None
             for key in replicas:
                 del self.models[key]
@@ -396,6 +399,9 @@ class ModelManager:
         self.unload_model(ModelType.YOLO_OSBTEXT, force_gc=False, verbose=verbose)
         if hasattr(self.models.get(ModelType.MANGA_OCR), "close"):
             self.unload_model(ModelType.MANGA_OCR, force_gc=False, verbose=verbose)
+        pair = self.models.get(ModelType.PADDLE_OCR_VL)
+        if isinstance(pair, tuple) and hasattr(pair[1], "close"):      # the PaddleOCR-VL pair this manager built, on the same terms
+            self.unload_model(ModelType.PADDLE_OCR_VL, force_gc=False, verbose=verbose)
         empty_cache(self.device)
 
     def unload_flux_kontext_sdnq_models(self, verbose: bool = False):
@@ -678,12 +684,38 @@ class ModelManager:
             log_message("manga-ocr initialized", verbose=verbose)
             return model
 
+    def paddle_ocr_vl_available(self) -> bool:
+        """a pair sits in the slot, or a checkpoint is staged for `get_paddle_ocr_vl` to build one from"""
+        return self.is_loaded(ModelType.PADDLE_OCR_VL) or (self.model_paths[ModelType.PADDLE_OCR_VL] / "config.json").is_file()
+
     def get_paddle_ocr_vl(self, verbose: bool = False):
-        """(processor, model) slot of PaddleOCR-VL (reference :927-980); see `get_manga_ocr`"""
+        """(processor, model) pair of PaddleOCR-VL (reference :927-980): whatever pair a deployment put in the slot is handed out; otherwise
+        the wheel's processor and a `generate` shim over `PaddleOcrVlHip` (core/ml/paddle_ocr_vl.py: vision tower, projector and text decoder
+        as libmtx_hip plans, greedy decoding on the device) are built from the directory staged under models/paddleocr-vl-1.6 and cached in
+        the slot; nothing staged -> ModelError, which `extract_text_with_paddle_ocr_vl` turns into the reference's "[OCR FAILED]" markers.
+        `paddle_ocr_vl_storage` ("f16" | "bf16") picks the storage type before the first call."""
         with self._lock:
             if self.is_loaded(ModelType.PADDLE_OCR_VL):
                 return self.models[ModelType.PADDLE_OCR_VL]
-            raise ModelError("PaddleOCR-VL is not part of this build (OCR side); load the reference's pair into ModelType.PADDLE_OCR_VL")
+            root = self.model_paths[ModelType.PADDLE_OCR_VL]
+            if not (root / "config.json").is_file():
+                raise ModelError(f"PaddleOCR-VL is not staged ({root}); stage the checkpoint directory or load a (processor, model) pair into "
+                                 f"ModelType.PADDLE_OCR_VL")
+            log_message("Initializing PaddleOCR-VL...", verbose=verbose)
+            try:
+                from ...hip import abi
+                from .paddle_ocr_vl import load_pair
+                storage = getattr(self, "paddle_ocr_vl_storage", "f16")
+                if storage not in ("f16", "bf16"):
+                    raise ModelError(f"paddle_ocr_vl_storage must be 'f16' or 'bf16', not {storage!r}")
+                pair = load_pair(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16}[storage])
+            except ModelError:
+                raise
+            except Exception as e:
+                raise ModelError(f"Failed to load PaddleOCR-VL: {e}") from e
+            self.models[ModelType.PADDLE_OCR_VL] = pair
+            log_message("PaddleOCR-VL initialized", verbose=verbose)
+            return pair
 
     def load_rtdetr_conjoined_bubble(self, verbose: bool = False):
         """RT-DETR-v2 secondary detector as libmtx_hip graphs with the YOLO-shaped call of the reference's adapter

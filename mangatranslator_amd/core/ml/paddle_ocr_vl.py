@@ -1,0 +1,589 @@
+"""PaddleOCR-VL on the HIP path: the (processor, model) pair behind `ModelManager.get_paddle_ocr_vl()` (reference core/ml/model_manager.py:927-980,
+driven by core/image/ocr_detection.py:886-962 as `model.generate(**inputs, max_new_tokens=1024)`), after transformers'
+`PaddleOCRVLForConditionalGeneration`: a SigLIP-like vision tower with a 2-D rotary turn, a 2 x 2 merging projector and a grouped-query text
+decoder with multimodal rotary positions.
+
+    PaddleOcrVlHip(state_dict, hp).generate(input_ids=, pixel_values=, image_grid_thw=, max_new_tokens=) -> int64 [1, T + n]
+
+  * every size comes from the checkpoint's `config.json` / `generation_config.json` (`read_checkpoint`); what this build does not serve raises
+    ModelError by name: a rope type other than "default", sliding-window layers, sampling, beams, a repetition penalty, video, several images,
+    a batch;
+  * rotary turns without a new kernel: the wheel turns the pairs (i, i + d/2) (`rotate_half`), MTX_EW_QK_ROPE turns interleaved pairs, so the
+    output rows of every q_proj / k_proj (and their biases) are permuted per head at load so that pair (i, i + d/2) lands on (2i, 2i + 1) — the
+    same permutation on q and k leaves q . k unchanged, v and the output projection never see it.  The cos | sin rows are built on the host:
+    from (row, col) for the vision tower, from the 3-D position ids with the `mrope_section` selection for the text decoder;
+  * vision plan per (gh, gw), eager: patch rows (K zero-padded 588 -> 592) through the patch GEMM with the bias and the bilinearly resampled
+    position table in its epilogue, pre-LN blocks (rotary at head width 72, full attention), post LayerNorm, the projector's LayerNorm, the
+    2 x 2 merge as ONE row gather with a host-built index, Linear + erf-GELU + Linear into the fp32 image rows;
+  * prefill plan per (T, image span), eager: embedding gather, the image rows copied over the placeholder rows, per layer RMSNorm -> fused
+    q | k | v GEMM -> rotary -> MTX_OP_CAUSAL_ATTN (appends to the cache) -> o_proj + residual -> RMSNorm -> gate | up GEMM -> SwiGLU -> down +
+    residual; final RMSNorm and the tied head on the LAST row only, fp32 logits, MTX_OP_GREEDY with advance = T;
+  * ONE step plan, captured once and replayed per token: the same layer on one row (`linear_route`: skinny-row kernel or tile GEMM per shape),
+    MTX_OP_CAUSAL_ATTN with rows = 1, MTX_OP_GREEDY with advance = 1.  Token, cache length and the rotary row all come from the 16-byte device
+    state {pos, n_out, done, token}: the host replays `check_every` steps, then downloads the state and stops at `done`;
+  * storage: f16 by default, bf16 selectable — weights and the linears' operands in that type, the residual stream and every norm input fp32.
+
+PARITY UNPINNED (nothing on the build machine can pin them; DESIGN.md's oracle table says the same):
+  * pre-processing: the pair carries the wheel's own processor, with the PIL image processor where torchvision is absent — PIL's bicubic
+    resize against torchvision's;
+  * the hub checkpoint's key layout (the wheel's own renaming table and what its `save_pretrained` writes are both accepted; no hub file was
+    seen) and its `generation_config.json`;
+  * the 1.6 repository's actual sizes (the wheel's defaults were used to size the work)."""
+import json
+import math
+import threading
+from pathlib import Path
+from typing import Callable, Dict, List, Optional
+
+import torch
+
+from ...hip import abi
+from ...hip.lib import get_library
+from ...hip.plan import Act, PlanBuilder, PlanCache
+from ...utils.exceptions import ModelError
+from . import packing, vit_common
+
+HEAD_DIM = 128                      # the text decoder's head width MTX_OP_CAUSAL_ATTN is built for
+WHAT = "PaddleOCR-VL"
+
+
+# ---- checkpoint ---------------------------------------------------------------------------------------------------------------------------------
+def hparams_from_config(config: dict, generation: Optional[dict] = None) -> dict:
+    """every size the graphs need, from `config.json` (+ `generation_config.json`); ModelError names what is not served"""
+    vis, txt = config.get("vision_config"), config.get("text_config")
+    if not isinstance(vis, dict) or not isinstance(txt, dict):
+        raise ModelError(f"{WHAT}: config.json must hold a `vision_config` and a `text_config` section")
+    rope = txt.get("rope_parameters") or txt.get("rope_scaling") or {}
+    if rope.get("rope_type", rope.get("type", "default")) != "default":
+        raise ModelError(f"{WHAT}: rope_type {rope.get('rope_type', rope.get('type'))!r} is not built (only 'default')")
+    if any(t != "full_attention" for t in (txt.get("layer_types") or [])) or txt.get("use_sliding_window"):
+        raise ModelError(f"{WHAT}: sliding-window layers are not built")
+    gen = dict(generation or {})
+    if gen.get("do_sample"):
+        raise ModelError(f"{WHAT}: sampling (do_sample) is not built; decoding is greedy")
+    if int(gen.get("num_beams") or 1) > 1:
+        raise ModelError(f"{WHAT}: beam search (num_beams > 1) is not built; decoding is greedy")
+    if float(gen.get("repetition_penalty") or 1.0) != 1.0:
+        raise ModelError(f"{WHAT}: a repetition penalty is not built")
+    hp = dict(v_dim=int(vis["hidden_size"]), v_layers=int(vis["num_hidden_layers"]), v_heads=int(vis["num_attention_heads"]),
+              v_mlp=int(vis["intermediate_size"]), patch=int(vis.get("patch_size", 14)), image=int(vis.get("image_size", 384)),
+              v_eps=float(vis.get("layer_norm_eps", 1e-6)), v_act=vis.get("hidden_act", "gelu_pytorch_tanh"), merge=int(vis.get("spatial_merge_size", 2)),
+              channels=int(vis.get("num_channels", 3)),
+              t_dim=int(txt["hidden_size"]), t_layers=int(txt["num_hidden_layers"]), t_heads=int(txt["num_attention_heads"]),
+              t_kv=int(txt.get("num_key_value_heads") or txt["num_attention_heads"]), t_mlp=int(txt["intermediate_size"]), vocab=int(txt["vocab_size"]),
+              t_eps=float(txt.get("rms_norm_eps", 1e-5)), t_act=txt.get("hidden_act", "silu"), theta=float(rope.get("rope_theta", txt.get("rope_theta", 10000.0))),
+              image_token=int(config["image_token_id"]), tied=bool(config.get("tie_word_embeddings", txt.get("tie_word_embeddings", True))))
+    hp["t_hd"] = int(txt.get("head_dim") or hp["t_dim"] // hp["t_heads"])
+    section = rope.get("mrope_section")
+    if not section or len(section) != 3 or sum(section) != hp["t_hd"] // 2:
+        raise ModelError(f"{WHAT}: rope_parameters.mrope_section must hold three sizes that add up to head_dim / 2")
+    hp["mrope"] = [int(s) for s in section]
+    if hp["t_hd"] != HEAD_DIM or hp["t_heads"] % hp["t_kv"]:
+        raise ModelError(f"{WHAT}: text head width {hp['t_hd']} / {hp['t_heads']} query heads over {hp['t_kv']} key-value heads is not built "
+                         f"(head width {HEAD_DIM}, query heads a multiple of the key-value heads)")
+    if txt.get("use_bias"):
+        raise ModelError(f"{WHAT}: a text decoder with biased linears is not built")
+    if hp["v_dim"] % hp["v_heads"] or (hp["v_dim"] // hp["v_heads"]) % 8 or hp["v_dim"] // hp["v_heads"] > 128 or (hp["v_dim"] // hp["v_heads"]) % 4:
+        raise ModelError(f"{WHAT}: vision head width {hp['v_dim'] / hp['v_heads']:g} is not built (a multiple of 8 up to 128)")
+    if hp["v_act"] not in ("gelu_pytorch_tanh", "gelu") or hp["t_act"] != "silu":
+        raise ModelError(f"{WHAT}: activation {hp['v_act']!r} / {hp['t_act']!r} is not built")
+    if hp["channels"] != 3 or hp["merge"] != 2 or hp["image"] < hp["patch"]:          # (the wheel's 384 / 14 leaves a remainder: the learned grid is 27 x 27)
+        raise ModelError(f"{WHAT}: the vision tower must take 3 channels and merge 2 x 2")
+    eos = gen.get("eos_token_id", txt.get("eos_token_id", config.get("eos_token_id")))
+    if eos is None:
+        raise ModelError(f"{WHAT}: neither generation_config.json nor config.json gives eos_token_id")
+    hp["eos"] = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos])]
+    if not 1 <= len(hp["eos"]) <= 4:
+        raise ModelError(f"{WHAT}: {len(hp['eos'])} end-of-sequence tokens are not built (1 .. 4)")
+    return hp
+
+
+V, P, L = "model.visual.vision_model.", "model.projector.", "model.language_model."
+
+
+def expected_keys(hp: dict) -> List[str]:
+    keys = []
+
+    def wb(prefix):
+        keys.extend([prefix + ".weight", prefix + ".bias"])
+    wb(V + "embeddings.patch_embedding")
+    keys.append(V + "embeddings.position_embedding.weight")
+    for i in range(hp["v_layers"]):
+        for n in ("layer_norm1", "layer_norm2", "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "mlp.fc1", "mlp.fc2"):
+            wb(f"{V}encoder.layers.{i}.{n}")
+    wb(V + "post_layernorm")
+    for n in ("pre_norm", "linear_1", "linear_2"):
+        wb(P + n)
+    keys.append(L + "embed_tokens.weight")
+    for i in range(hp["t_layers"]):
+        for n in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj",
+                  "input_layernorm", "post_attention_layernorm"):
+            keys.append(f"{L}layers.{i}.{n}.weight")
+    keys.extend([L + "norm.weight", "lm_head.weight"])
+    return keys
+
+
+# tensors a hub checkpoint carries that the wheel itself drops on load (`_keys_to_ignore_on_load_unexpected`)
+IGNORED_KEYS = ("packing_position_embedding", "vision_model.head")
+
+
+def _rename_hub(key: str) -> str:
+    """the hub file's names -> `state_dict()`'s, as the wheel's conversion mapping for "paddleocr_vl" renames them on load (and back in
+    `save_pretrained`): mlp_AR.* -> model.projector.*, visual.* -> model.visual.*, model.<rest> -> model.language_model.<rest>"""
+    if key.startswith("mlp_AR"):
+        return "model.projector" + key[len("mlp_AR"):]
+    if key.startswith("visual"):
+        return "model." + key
+    if key.startswith("model") and not key.startswith(("model.visual", "model.projector", "model.language_model")):
+        return "model.language_model" + key[len("model"):]
+    return key
+
+
+def normalise_state_dict(sd: Dict[str, torch.Tensor], hp: dict) -> Dict[str, torch.Tensor]:
+    """both key layouts -> `state_dict()`'s names; a tied `lm_head.weight` that the file leaves out is filled in; every missing or unexpected
+    key is a ModelError"""
+    out = {_rename_hub(k): v for k, v in sd.items() if not any(skip in k for skip in IGNORED_KEYS)}
+    if "lm_head.weight" not in out and hp["tied"] and L + "embed_tokens.weight" in out:
+        out["lm_head.weight"] = out[L + "embed_tokens.weight"]
+    want = set(expected_keys(hp))
+    missing, unexpected = sorted(want - set(out)), sorted(set(out) - want)
+    if missing or unexpected:
+        raise ModelError(f"{WHAT} checkpoint: missing keys {missing[:6]}{' ...' if len(missing) > 6 else ''}, "
+                         f"unexpected keys {unexpected[:6]}{' ...' if len(unexpected) > 6 else ''}")
+    return out
+
+
+def read_checkpoint(root) -> dict:
+    """a staged `paddleocr-vl-1.6` directory -> dict(hp, state_dict): config.json + model.safetensors (or the shards its index names) +
+    generation_config.json"""
+    root = Path(root)
+    if not (root / "config.json").is_file():
+        raise ModelError(f"{WHAT} is not staged: {root / 'config.json'} not found")
+    config = json.loads((root / "config.json").read_text())
+    gen_path = root / "generation_config.json"
+    hp = hparams_from_config(config, json.loads(gen_path.read_text()) if gen_path.is_file() else None)
+    from safetensors.torch import load_file
+    if (root / "model.safetensors").is_file():
+        files = ["model.safetensors"]
+    elif (root / "model.safetensors.index.json").is_file():
+        files = sorted(set(json.loads((root / "model.safetensors.index.json").read_text())["weight_map"].values()))
+    else:
+        raise ModelError(f"{WHAT} is not staged: neither model.safetensors nor model.safetensors.index.json in {root}")
+    sd = {}
+    for f in files:
+        if not (root / f).is_file():
+            raise ModelError(f"{WHAT} is not staged: shard {root / f} not found")
+        sd.update(load_file(str(root / f)))
+    return dict(hp=hp, state_dict=normalise_state_dict(sd, hp))
+
+
+def interleave_rows(w: torch.Tensor, heads: int, d: int) -> torch.Tensor:
+    """rows (or entries) of a q / k projection [heads * d, ...] permuted per head so that the wheel's rotary pair (i, i + d/2) lands on the
+    interleaved pair (2i, 2i + 1) the kernel turns"""
+    idx = torch.stack([torch.arange(d // 2), torch.arange(d // 2) + d // 2], 1).reshape(-1)
+    return w.reshape(heads, d, *w.shape[1:])[:, idx].reshape(w.shape)
+
+
+def linear_route(rows: int, n: int, k: int) -> str:
+    """which kernel a linear of the decode step runs on: "rowlin" (MTX_OP_ROWLIN) or "gemm".  One activation row against 2 - 6 MB of weights per
+    linear (212 MB for the 103 424-row head at the published widths): weight streaming, as manga-ocr's step; the A/B of the whole step graph
+    (tools/bench_kernels.py paddleocr; docs/experiments.md) decides per shape."""
+    return "rowlin"
+
+
+# ---- host-side tables ---------------------------------------------------------------------------------------------------------------------------
+def vision_rope_table(gh: int, gw: int, d: int) -> torch.Tensor:
+    """fp32 [gh * gw][2][d / 2] cos | sin: the first d / 4 frequencies turn with the row, the next d / 4 with the column (wheel :627-638, :845-856)"""
+    q = d // 4
+    inv = 1.0 / (10000.0 ** (torch.arange(0, d // 2, 2, dtype=torch.float) / (d // 2)))
+    assert inv.numel() == q
+    rows, cols = torch.meshgrid(torch.arange(gh), torch.arange(gw), indexing="ij")
+    ang = torch.cat([rows.reshape(-1, 1).float() * inv, cols.reshape(-1, 1).float() * inv], 1)          # [N, d / 2]
+    return torch.stack([ang.cos(), ang.sin()], 1).contiguous()
+
+
+def rope_positions(token_is_image: torch.Tensor, gh: int, gw: int, merge: int) -> torch.Tensor:
+    """the 3-D position ids [3, T] of one prompt with one image (wheel get_rope_index / get_vision_position_ids): text tokens carry three
+    equal indices, image tokens (start, start + row, start + col) on the merged grid, text after the image starts at the running maximum + 1"""
+    T = int(token_is_image.numel())
+    img = token_is_image.nonzero().reshape(-1)
+    mh, mw = gh // merge, gw // merge
+    if img.numel() != mh * mw or (img.numel() and int(img[-1] - img[0]) + 1 != img.numel()):
+        raise ModelError(f"{WHAT}: the prompt's image placeholders ({img.numel()}) must be one run of {mh * mw} tokens")
+    start = int(img[0])
+    pos = torch.zeros(3, T, dtype=torch.long)
+    pos[:, :start] = torch.arange(start)
+    r, c = torch.meshgrid(torch.arange(mh), torch.arange(mw), indexing="ij")
+    pos[0, start:start + mh * mw] = start
+    pos[1, start:start + mh * mw] = start + r.reshape(-1)
+    pos[2, start:start + mh * mw] = start + c.reshape(-1)
+    after = start + max(mh, mw)
+    n_after = T - start - mh * mw
+    pos[:, start + mh * mw:] = after + torch.arange(n_after)
+    return pos
+
+
+def text_rope_table(pos3: torch.Tensor, section: List[int], theta: float, d: int) -> torch.Tensor:
+    """fp32 [T][2][d / 2] cos | sin from 3-D ids [3, T]: frequency i takes the axis its `mrope_section` names (wheel :239-281)"""
+    inv = 1.0 / (theta ** (torch.arange(0, d, 2, dtype=torch.float) / d))
+    axis = torch.repeat_interleave(torch.arange(3), torch.tensor(section))                              # [d / 2]
+    p = pos3.float()[axis, :].t()                                                                        # [T, d / 2]
+    ang = p * inv
+    return torch.stack([ang.cos(), ang.sin()], 1).contiguous()
+
+
+# ---- the model ----------------------------------------------------------------------------------------------------------------------------------
+class PaddleOcrVlHip:
+    def __init__(self, state_dict: dict, hp: dict, device="cuda", lib=None, dtype: int = abi.F16, graph: bool = True, max_new_tokens: int = 1024,
+                 max_prompt: int = 1280 + 64, check_every: int = 8, route: Optional[Callable[[int, int, int], str]] = None):
+        """hp: `hparams_from_config`; state_dict: `normalise_state_dict`'s names.  max_prompt: the longest prompt served (the processor's
+        max_pixels bound gives at most 1 280 image tokens; the chat template adds a few tens); the cache holds max_prompt + max_new_tokens."""
+        if dtype not in (abi.BF16, abi.F16):
+            raise ModelError(f"{WHAT}: storage dtype must be f16 or bf16")
+        self.lib = lib if lib is not None else get_library()
+        self.device = torch.device(device)
+        self.hp, self.dtype, self.tdt = hp, dtype, {abi.BF16: torch.bfloat16, abi.F16: torch.float16}[dtype]
+        self.max_new, self.max_prompt, self.check_every = int(max_new_tokens), int(max_prompt), max(1, int(check_every))
+        self.max_len = self.max_prompt + self.max_new
+        self.route = route or linear_route
+        self._graph = graph and not self.lib.is_simulator
+        self._lock = threading.Lock()
+        self._vis, self._pre = PlanCache(4), PlanCache(6)
+        self._step = None
+        self._pack({k: v.detach().float().cpu() for k, v in state_dict.items()})
+        f32, i32 = torch.float32, torch.int32
+        C, kvw = hp["t_dim"], hp["t_kv"] * HEAD_DIM
+        z = lambda *s, dt=f32: torch.zeros(*s, dtype=dt, device=self.device)
+        self.caches = [(z(self.max_len, kvw, dt=self.tdt), z(self.max_len, kvw, dt=self.tdt)) for _ in range(hp["t_layers"])]
+        self.state = z(4, dt=i32)                                    # {pos, n_out, done, token}
+        self.out = z(self.max_new, dt=i32)
+        self.img_rows = z(max(self.max_prompt, 8), C)                # the projector's output, read by the prefill plans
+        self.step_rope = z(self.max_len, HEAD_DIM)                   # cos | sin row of the token fed at cache position p (set per prompt)
+        self.logits = z(1, hp["vocab"])
+
+    @classmethod
+    def from_directory(cls, root, **kw):
+        ck = read_checkpoint(root)
+        return cls(ck["state_dict"], ck["hp"], **kw)
+
+    # ------------------------------------------------------------------------------------------
+    def _c(self, t, dtype=None):
+        return packing.on_device(t, self.device, dtype if dtype is not None else self.tdt)
+
+    def _pack(self, sd):
+        """every linear as the triple (W, None, bias or None) of core/ml/packing.py, LayerNorms as (gamma, beta), RMSNorms as (gamma, None)"""
+        hp = self.hp
+        f32 = torch.float32
+        Cv, vh = hp["v_dim"], hp["v_heads"]
+        vd = Cv // vh
+
+        def ln(key):
+            return packing.layer_norm(sd, key, self.device)
+
+        def lin(*keys):
+            return packing.linear(sd, *keys, device=self.device, dtype=self.tdt)
+
+        def lin_nb(*ws):
+            return (self._c(torch.cat(ws, 0)), None, None)
+
+        W = {}
+        pw = sd[V + "embeddings.patch_embedding.weight"]
+        k = pw[0].numel()
+        self.patch_k, self.patch_kp = k, (k + 7) // 8 * 8
+        pk = torch.zeros(Cv, self.patch_kp)
+        pk[:, :k] = pw.reshape(Cv, k)
+        W["pe"] = (self._c(pk), None, self._c(sd[V + "embeddings.patch_embedding.bias"], f32))
+        self.pos_table = sd[V + "embeddings.position_embedding.weight"]                       # fp32, host: resampled per grid
+        side = int(round(self.pos_table.shape[0] ** 0.5))
+        if side * side != self.pos_table.shape[0] or side != hp["image"] // hp["patch"]:
+            raise ModelError(f"{WHAT}: the vision position table does not match image_size / patch_size")
+        self.v_layers = []
+        for i in range(hp["v_layers"]):
+            p = f"{V}encoder.layers.{i}."
+            a = p + "self_attn."
+            qkv_w = torch.cat([interleave_rows(sd[a + "q_proj.weight"], vh, vd), interleave_rows(sd[a + "k_proj.weight"], vh, vd), sd[a + "v_proj.weight"]], 0)
+            qkv_b = torch.cat([interleave_rows(sd[a + "q_proj.bias"], vh, vd), interleave_rows(sd[a + "k_proj.bias"], vh, vd), sd[a + "v_proj.bias"]], 0)
+            self.v_layers.append(dict(ln1=ln(p + "layer_norm1"), ln2=ln(p + "layer_norm2"), qkv=(self._c(qkv_w), None, self._c(qkv_b, f32)),
+                                      proj=lin(a + "out_proj"), fc1=lin(p + "mlp.fc1"), fc2=lin(p + "mlp.fc2")))
+        W["v_ln"] = ln(V + "post_layernorm")
+        W["p_ln"] = ln(P + "pre_norm")
+        W["p1"], W["p2"] = lin(P + "linear_1"), lin(P + "linear_2")
+        if sd[L + "embed_tokens.weight"].shape != (hp["vocab"], hp["t_dim"]) or sd["lm_head.weight"].shape != (hp["vocab"], hp["t_dim"]):
+            raise ModelError(f"{WHAT}: the embedding table / head do not match vocab_size x hidden_size")
+        W["tok"] = self._c(sd[L + "embed_tokens.weight"])
+        W["head"] = (W["tok"] if torch.equal(sd["lm_head.weight"], sd[L + "embed_tokens.weight"]) else self._c(sd["lm_head.weight"]), None, None)
+        th, tkv = hp["t_heads"], hp["t_kv"]
+        self.t_layers = []
+        for i in range(hp["t_layers"]):
+            p = f"{L}layers.{i}."
+            a = p + "self_attn."
+            self.t_layers.append(dict(
+                n1=(self._c(sd[p + "input_layernorm.weight"], f32), None), n2=(self._c(sd[p + "post_attention_layernorm.weight"], f32), None),
+                qkv=lin_nb(interleave_rows(sd[a + "q_proj.weight"], th, HEAD_DIM), interleave_rows(sd[a + "k_proj.weight"], tkv, HEAD_DIM), sd[a + "v_proj.weight"]),
+                o=lin_nb(sd[a + "o_proj.weight"]), gu=lin_nb(sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]), down=lin_nb(sd[p + "mlp.down_proj.weight"])))
+        W["t_norm"] = (self._c(sd[L + "norm.weight"], f32), None)
+        self.W = W
+
+    # ---- vision ----------------------------------------------------------------------------------
+    def _vision(self, gh: int, gw: int):
+        if (gh, gw) in self._vis:
+            return self._vis[(gh, gw)]
+        from transformers.vision_utils import get_vision_interpolation_indices_and_weights
+        hp, W = self.hp, self.W
+        if gh % 2 or gw % 2 or gh * gw // 4 > self.img_rows.shape[0]:
+            raise ModelError(f"{WHAT}: an image grid of {gh} x {gw} patches is not served (even sides, at most {self.img_rows.shape[0]} merged tokens)")
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        N, C, heads, Ct = gh * gw, hp["v_dim"], hp["v_heads"], hp["t_dim"]
+        d = C // heads
+        side = hp["image"] // hp["patch"]
+        idx, wts = get_vision_interpolation_indices_and_weights(torch.tensor([[1, gh, gw]]), num_grid_per_side=side, mode="bilinear", align_corners=True,
+                                                                spatial_merge_size=1)
+        pos = pb.const((self.pos_table[idx] * wts[:, :, None].float()).sum(1), torch.float32)               # [N, C]
+        rope = pb.const(vision_rope_table(gh, gw, d))
+        patches = pb.buf((N, self.patch_kp), self.tdt, zero=True)
+        layer_norm, linear, close_branch = vit_common.trunk_helpers(pb, hp["v_eps"], self.tdt, self.dtype, stream32=True)
+        act = abi.ACT_GELU_TANH if hp["v_act"] == "gelu_pytorch_tanh" else abi.ACT_GELU
+        x = close_branch(patches, W["pe"], N, C, self.patch_kp, pos, "patch_embed")
+        for i, Lr in enumerate(self.v_layers):
+            tag = f"vis{i}"
+            qkv = linear(layer_norm(x, N, C, Lr["ln1"], tag + ".ln1"), Lr["qkv"], N, 3 * C, C, tag + ".qkv")
+            pb.qk_rope(Act(qkv.view(1, 1, N, 3 * C), 1, 1, N, 2 * C), rope, d, label=tag + ".rope")
+            o = pb.buf((N, C), self.tdt)
+            st = (N * 3 * C, 3 * C, d)
+            pb.attention(qkv, qkv, qkv, o, 1, heads, N, N, d, st, st, st, (N * C, C, d), 1.0 / math.sqrt(d), k_off=C, v_off=2 * C, label=tag + ".attn")
+            x1 = close_branch(o, Lr["proj"], N, C, C, x, tag + ".proj")
+            h = linear(layer_norm(x1, N, C, Lr["ln2"], tag + ".ln2"), Lr["fc1"], N, hp["v_mlp"], C, tag + ".fc1", act=act)
+            x = close_branch(h, Lr["fc2"], N, C, hp["v_mlp"], x1, tag + ".fc2")
+        y32 = pb.norm(x, pb.buf((N, C), torch.float32), N, C, gamma=W["v_ln"][0], beta=W["v_ln"][1], eps=hp["v_eps"], dtype=abi.F32, out_dtype=abi.F32, label="vis.post_ln")
+        y = pb.norm(y32, pb.buf((N, C), self.tdt), N, C, gamma=W["p_ln"][0], beta=W["p_ln"][1], eps=1e-5, dtype=abi.F32, out_dtype=self.dtype, label="proj.pre_norm")
+        # 2 x 2 merge: merged row (hb, wb) = the four source rows (2 hb + m1, 2 wb + m2) side by side, so [N / 4][4 C] is a plain view
+        hb, wb, m1, m2 = torch.meshgrid(torch.arange(gh // 2), torch.arange(gw // 2), torch.arange(2), torch.arange(2), indexing="ij")
+        src = pb.const(((hb * 2 + m1) * gw + wb * 2 + m2).reshape(-1).to(torch.int32))
+        merged = pb.row_gather(y, pb.buf((N, C), self.tdt), src, N, C, label="proj.merge")
+        M = N // 4
+        h1 = linear(merged, W["p1"], M, 4 * C, 4 * C, "proj.linear_1", act=abi.ACT_GELU)
+        linear(h1, W["p2"], M, Ct, 4 * C, "proj.linear_2", out=self.img_rows, out_f32=True)
+        plan = pb.build()
+        plan.patches, plan.tokens = patches, M
+        self._vis[(gh, gw)] = plan
+        return plan
+
+    # ---- the text decoder ------------------------------------------------------------------------
+    def _layers(self, pb, x, rows, rope, lin, close):
+        """the decoder layers on `rows` rows of the fp32 stream x; -> the stream after the last layer"""
+        hp = self.hp
+        C, heads, kv, I = hp["t_dim"], hp["t_heads"], hp["t_kv"], hp["t_mlp"]
+        qw = (heads + 2 * kv) * HEAD_DIM
+        ws = pb.buf((abi.causal_ws_bytes(heads, self.max_len),), torch.uint8, zero=True) if rows == 1 else None
+        for i, Lr in enumerate(self.t_layers):
+            tag = f"dec{i}"
+            kc, vc = self.caches[i]
+            a = pb.norm(x, pb.buf((rows, C), self.tdt), rows, C, gamma=Lr["n1"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm1")
+            qkv = lin(a, Lr["qkv"], qw, C, tag + ".qkv")
+            pb.qk_rope(Act(qkv.view(1, 1, rows, qw), 1, 1, rows, (heads + kv) * HEAD_DIM), rope, HEAD_DIM, label=tag + ".rope")
+            o = pb.causal_attention(qkv, kc, vc, self.state[0:1], pb.buf((rows, heads * HEAD_DIM), self.tdt), rows, heads, kv, HEAD_DIM, self.max_len,
+                                    HEAD_DIM ** -0.5, workspace=ws, label=tag + ".attn")
+            x1 = close(o, Lr["o"], C, heads * HEAD_DIM, x, tag + ".o_proj")
+            b = pb.norm(x1, pb.buf((rows, C), self.tdt), rows, C, gamma=Lr["n2"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm2")
+            gu = lin(b, Lr["gu"], 2 * I, C, tag + ".gate_up")
+            g4 = gu.view(1, 1, rows, 2 * I)
+            hmid = pb.ew(abi.EW_SWIGLU, Act(g4, 1, 1, rows, I, 0), b=Act(g4, 1, 1, rows, I, I), out=Act(pb.buf((1, 1, rows, I), self.tdt), 1, 1, rows, I),
+                         label=tag + ".swiglu").t.view(rows, I)
+            x = close(hmid, Lr["down"], C, I, x1, tag + ".down")
+        return x
+
+    def _head(self, pb, x_last, advance):
+        hp = self.hp
+        C = hp["t_dim"]
+        a = pb.norm(x_last, pb.buf((1, C), self.tdt), 1, C, gamma=self.W["t_norm"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label="final_norm")
+        if self.route(1, hp["vocab"], C) == "rowlin":
+            pb.row_linear(a, self.W["head"][0], 1, hp["vocab"], C, out=self.logits, out_f32=True, label="head")
+        else:
+            pb.gemm(a, self.W["head"][0], 1, hp["vocab"], C, out=self.logits, out_f32=True, label="head")
+        pb.greedy_pick(self.logits, self.state, self.out, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
+
+    def _prefill(self, T: int, start: int, n_img: int):
+        key = (T, start, n_img)
+        if key in self._pre:
+            return self._pre[key]
+        hp = self.hp
+        C = hp["t_dim"]
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        ids = pb.buf((T,), torch.int32, zero=True)
+        rope = pb.buf((T, 2, HEAD_DIM // 2), torch.float32, zero=True)
+        e16 = pb.row_gather(self.W["tok"], pb.buf((T, C), self.tdt), ids, T, C, label="embed")
+        x = pb.cvt_f32(Act(e16.view(1, 1, T, C), 1, 1, T, C), self.dtype, label="embed.f32").t.view(T, C)
+        if n_img:
+            pb.ew(abi.EW_COPY, Act(self.img_rows[:n_img].view(1, 1, n_img, C), 1, 1, n_img, C), out=Act(x[start:start + n_img].view(1, 1, n_img, C), 1, 1, n_img, C),
+                  label="embed.image_rows", dtype=abi.F32)
+        _, linear, close_branch = vit_common.trunk_helpers(pb, hp["t_eps"], self.tdt, self.dtype, stream32=True)
+        x = self._layers(pb, x, T, rope, lambda a, wb, n, k, label: linear(a, wb, T, n, k, label),
+                         lambda a, wb, n, k, res, label: close_branch(a, wb, T, n, k, res, label))
+        self._head(pb, x[T - 1:T], advance=T)
+        plan = pb.build()
+        plan.ids, plan.rope = ids, rope
+        self._pre[key] = plan
+        return plan
+
+    def _stepper(self):
+        if self._step is not None:
+            return self._step
+        hp = self.hp
+        C = hp["t_dim"]
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        e16 = pb.row_gather(self.W["tok"], pb.buf((1, C), self.tdt), self.state[3:4], 1, C, label="embed")
+        x = pb.cvt_f32(Act(e16.view(1, 1, 1, C), 1, 1, 1, C), self.dtype, label="embed.f32").t.view(1, C)
+        rope = pb.row_gather(self.step_rope, pb.buf((1, HEAD_DIM), torch.float32), self.state[0:1], 1, HEAD_DIM, label="rope.row", dtype=abi.F32)
+
+        def lin(a, wb, n, k, label):
+            if self.route(1, n, k) == "rowlin":
+                return pb.row_linear(a, wb[0], 1, n, k, label=label)
+            return pb.gemm(a, wb[0], 1, n, k, label=label)
+
+        def close(a, wb, n, k, res, label):
+            """stream <- res + a @ W^T in fp32 (the skinny-row kernel takes no fp32 residual: its fp32 output and one fp32 add)"""
+            if self.route(1, n, k) != "rowlin":
+                return pb.gemm(a, wb[0], 1, n, k, res=res, res_f32=True, out_f32=True, label=label)
+            y = pb.row_linear(a, wb[0], 1, n, k, out_f32=True, label=label)
+            return pb.ew(abi.EW_ADD, Act(y.view(1, 1, 1, n), 1, 1, 1, n), Act(res.view(1, 1, 1, n), 1, 1, 1, n),
+                         out=Act(pb.buf((1, 1, 1, n), torch.float32), 1, 1, 1, n), label=label + ".add", dtype=abi.F32).t.view(1, n)
+
+        x = self._layers(pb, x, 1, rope, lin, close)
+        self._head(pb, x, advance=1)
+        self._step = pb.build()
+        return self._step
+
+    # ---- running ---------------------------------------------------------------------------------
+    def _check_inputs(self, input_ids, pixel_values, image_grid_thw, kw):
+        if kw.get("pixel_values_videos") is not None or kw.get("video_grid_thw") is not None:
+            raise ModelError(f"{WHAT}: video inputs are not built")
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ModelError(f"{WHAT}: one prompt at a time (batch 1)")
+        if pixel_values is None or image_grid_thw is None or image_grid_thw.shape[0] != 1 or int(image_grid_thw[0, 0]) != 1:
+            raise ModelError(f"{WHAT}: exactly one image per prompt")
+        if kw.get("do_sample"):
+            raise ModelError(f"{WHAT}: sampling (do_sample) is not built; decoding is greedy")
+        for name in ("num_beams", "repetition_penalty"):
+            if kw.get(name) is not None and float(kw[name]) != 1.0:
+                raise ModelError(f"{WHAT}: {name}={kw[name]!r} is not built; decoding is greedy")
+
+    def prefill(self, input_ids, pixel_values, image_grid_thw) -> int:
+        """vision + prompt; leaves the first generated token in the device state.  Returns T"""
+        hp = self.hp
+        ids = input_ids[0].to(torch.long).cpu()
+        T = int(ids.numel())
+        gh, gw = int(image_grid_thw[0, 1]), int(image_grid_thw[0, 2])
+        if T > self.max_prompt:
+            raise ModelError(f"{WHAT}: a prompt of {T} tokens exceeds the {self.max_prompt} this model was built for")
+        if pixel_values.shape[0] != gh * gw or pixel_values[0].numel() != self.patch_k:
+            raise ModelError(f"{WHAT}: pixel_values {tuple(pixel_values.shape)} do not match the grid {gh} x {gw}")
+        is_img = ids == hp["image_token"]
+        pos3 = rope_positions(is_img, gh, gw, hp["merge"])
+        vis = self._vision(gh, gw)
+        vis.patches[:, :self.patch_k].copy_(pixel_values.reshape(gh * gw, self.patch_k).to(self.device, self.tdt))
+        vis.run()
+        start = int(is_img.nonzero()[0])
+        pre = self._prefill(T, start, vis.tokens)
+        pre.ids.copy_(ids.to(torch.int32))
+        pre.rope.copy_(text_rope_table(pos3, hp["mrope"], hp["theta"], HEAD_DIM))
+        # the token fed at cache position p >= T sits at rotary position p + delta, all three axes equal
+        delta = int(pos3.max()) + 1 - T
+        p = (torch.arange(self.max_len) + delta).clamp_min(0)
+        self.step_rope.copy_(text_rope_table(p[None].expand(3, -1), hp["mrope"], hp["theta"], HEAD_DIM).reshape(self.max_len, HEAD_DIM))
+        self.state.zero_()
+        pre.run()
+        return T
+
+    def read_state(self):
+        return [int(v) for v in self.state.cpu().tolist()]
+
+    def generate(self, input_ids=None, pixel_values=None, image_grid_thw=None, max_new_tokens: Optional[int] = None, check_every: Optional[int] = None, **ignored):
+        """greedy decoding, as `GenerationMixin.generate` returns it: int64 [1, T + n], the prompt then the generated tokens, EOS included"""
+        self._check_inputs(input_ids, pixel_values, image_grid_thw, ignored)
+        budget = self.max_new if max_new_tokens is None else int(max_new_tokens)
+        if not 1 <= budget <= self.max_new:
+            raise ModelError(f"{WHAT}: max_new_tokens {budget} is outside 1 .. {self.max_new} this model was built for")
+        every = self.check_every if check_every is None else max(1, int(check_every))
+        with self._lock:
+            self.prefill(input_ids, pixel_values, image_grid_thw)
+            step = self._stepper()
+            _, n_out, done, _ = self.read_state()
+            while not done and n_out < budget:
+                for _ in range(min(every, budget - n_out)):
+                    step.run(graph=self._graph)
+                _, n_out, done, _ = self.read_state()
+            n = min(n_out, budget)
+            new = self.out[:n].to(torch.long).cpu()
+        eos = [i for i, t in enumerate(new.tolist()) if t in self.hp["eos"]]
+        if eos:
+            new = new[:eos[0] + 1]
+        return torch.cat([input_ids[0].to(torch.long).cpu(), new])[None].to(input_ids.device)
+
+    def step_logits(self, token: int) -> torch.Tensor:
+        """teacher forcing (parity tests): feed `token` at the current position instead of the model's own pick -> fp32 logits [vocab] of the next"""
+        st = self.read_state()
+        self.state.copy_(torch.tensor([st[0], 0, 0, int(token)], dtype=torch.int32))
+        self._stepper().run(graph=self._graph)
+        return self.logits[0].float().cpu().clone()
+
+    def close(self):
+        for p in [self._step, *self._vis.values(), *self._pre.values()]:
+            if p is not None:
+                p.close()
+        self._step = None
+        self._vis.clear()
+        self._pre.clear()
+
+
+class GenerateShim:
+    """what `extract_text_with_paddle_ocr_vl` calls `model`: `.device` and `.generate(**inputs, max_new_tokens=)`"""
+
+    def __init__(self, model: PaddleOcrVlHip):
+        self.model = model
+        self.device = torch.device("cpu")          # the processor's tensors stay on the host: `generate` uploads what the plans need
+
+    def generate(self, **kw):
+        return self.model.generate(**kw)
+
+    def close(self):
+        self.model.close()
+
+
+def build_processor(root):
+    """the wheel's `PaddleOCRVLProcessor`, assembled by hand from the staged files (AutoProcessor demands torchvision through AutoImageProcessor):
+    image processor from the json's image-processor section — torchvision's when it imports, PIL's otherwise — the tokenizer and the chat
+    template, all with local_files_only"""
+    root = Path(root)
+    from transformers import AutoTokenizer
+    from transformers.models.paddleocr_vl.processing_paddleocr_vl import PaddleOCRVLProcessor
+    section = {}
+    for name in ("processor_config.json", "preprocessor_config.json"):
+        if (root / name).is_file():
+            js = json.loads((root / name).read_text())
+            section = js.get("image_processor", js) if name == "processor_config.json" else js
+            if section:
+                break
+    section = {k: v for k, v in section.items() if k not in ("image_processor_type", "processor_class", "auto_map")}
+    try:
+        import torchvision  # noqa: F401
+        from transformers.models.paddleocr_vl.image_processing_paddleocr_vl import PaddleOCRVLImageProcessor as IP
+    except Exception:
+        from transformers.models.paddleocr_vl.image_processing_pil_paddleocr_vl import PaddleOCRVLImageProcessorPil as IP
+    tok = AutoTokenizer.from_pretrained(str(root), local_files_only=True)
+    template = None
+    for name in ("chat_template.jinja", "chat_template.json"):
+        if (root / name).is_file():
+            text = (root / name).read_text()
+            template = json.loads(text)["chat_template"] if name.endswith(".json") else text
+            break
+    if template is None:
+        template = getattr(tok, "chat_template", None)
+    if template is None:
+        raise ModelError(f"{WHAT} is not staged: no chat template in {root}")
+    return PaddleOCRVLProcessor(image_processor=IP(**section), tokenizer=tok, chat_template=template)
+
+
+def load_pair(root, device="cuda", lib=None, dtype: int = abi.F16, **kw):
+    """(processor, model shim) from a staged directory"""
+    model = PaddleOcrVlHip.from_directory(root, device=device, lib=lib, dtype=dtype, **kw)
+    return build_processor(root), GenerateShim(model)

@@ -1060,13 +1060,13 @@ int yolo_decode_launch(const mtx_yolo_decode_args* a, void* stream, const char**
 // kernels before it keep their place in the code object: tools/isa_diff.py then shows them unchanged.)
 template <typename T>
 __global__ __launch_bounds__(256) void qk_rope_kernel(mtx_ew_args p) {
-  const int d = p.i0, lpr = d / 8;                                   // lanes per (token, head) row: 8 or 16
+  const int d = p.i0, lpr = d / 8;                                   // lanes per (token, head) row: 1 .. 16 (any d % 8 == 0 up to 128)
   const unsigned cpr = (unsigned)(p.c / 8);                          // 16-byte chunks per token row
   const unsigned rows = (unsigned)(p.n * p.h * p.w);
   const unsigned ch = blockIdx.x * 256u + threadIdx.x;               // grid.x = ceil(cpr / 256)
   if (ch >= cpr) return;
-  const int part = (int)(ch & (unsigned)(lpr - 1));
   const int hd = (int)(ch / (unsigned)lpr);
+  const int part = (int)(ch - (unsigned)hd * (unsigned)lpr);
   const float* cs = reinterpret_cast<const float*>(p.b);
   if (p.i1 > 0 && p.ldb > 0 && hd < p.i1) cs += p.ldb;               // q heads: the copy pre-multiplied by softmax scale * log2(e)
   const T* X = reinterpret_cast<const T*>(p.a);
@@ -1099,7 +1099,7 @@ __global__ __launch_bounds__(256) void qk_rope_kernel(mtx_ew_args p) {
 
 int qk_rope_launch(const mtx_ew_args* a, void* stream, const char** err) {
   const int d = a->i0;
-  if (!a->a || !a->y || !a->b || (d != 64 && d != 128) || a->c < d || a->c % d || a->lda % 8 || a->ldy % 8 || a->lda < a->c || a->ldy < a->c) { *err = "qk_rope: head dim must be 64 or 128, c = heads * d, row strides multiples of 8 that cover c"; return MTX_ERR_INVALID; }
+  if (!a->a || !a->y || !a->b || d < 8 || d > 128 || d % 8 || a->c < d || a->c % d || a->lda % 8 || a->ldy % 8 || a->lda < a->c || a->ldy < a->c) { *err = "qk_rope: head dim must be a multiple of 8 from 8 to 128, c = heads * d, row strides multiples of 8 that cover c"; return MTX_ERR_INVALID; }
   if (((size_t)a->b & 15) || a->ldb % 4 || a->ldb < 0 || a->i1 < 0) { *err = "qk_rope: the cos | sin table must be 16-byte aligned (ldb % 4 == 0)"; return MTX_ERR_INVALID; }
   const long rows = a->n * a->h * a->w;
   if (rows < 1) return MTX_OK;

@@ -336,6 +336,7 @@ int attn_f32_launch(const mtx_attn_args* a, void* stream, const char** err) {
 }
 
 // ---- LayerNorm over the last dim, one wave per row (two passes over the row: mean, then centred variance) ------------------------------------
+// kind 1 (RMSNorm, the fp32 residual stream of PaddleOCR-VL's text decoder) is the same walk with the mean taken as zero.
 // TO = float, or (round 6, mtx_norm_args.out_dtype) the 16-bit type of the linear that follows: the fp32 residual stream of SAM's precision
 // "high" is normalised in fp32 and rounded ONCE here — no fp32 result, no conversion pass.  Rows of up to 64 x 4 x NCH values stay in registers
 // between the passes (16-byte loads); wider or unaligned rows take the element loop.
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(256) void norm_f32_kernel(mtx_norm_args p) {
       xv[ch] = c < p.c ? *reinterpret_cast<const f32x4*>(X + c) : f32x4{0.f, 0.f, 0.f, 0.f};
       s += (xv[ch][0] + xv[ch][1]) + (xv[ch][2] + xv[ch][3]);
     }
-    const float mean = wave_sum(s) / (float)p.c;
+    const float mean = p.kind == 1 ? 0.f : wave_sum(s) / (float)p.c;
     float v = 0.f;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
@@ -390,7 +391,7 @@ __global__ __launch_bounds__(256) void norm_f32_kernel(mtx_norm_args p) {
   }
   float s = 0.f;
   for (long c = lane; c < p.c; c += 64) s += X[c];
-  const float mean = wave_sum(s) / (float)p.c;
+  const float mean = p.kind == 1 ? 0.f : wave_sum(s) / (float)p.c;
   float v = 0.f;
   for (long c = lane; c < p.c; c += 64) { const float d = X[c] - mean; v = fmaf(d, d, v); }
   const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)p.c + p.eps);
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(256) void norm_f32_kernel(mtx_norm_args p) {
 
 int norm_f32_launch(const mtx_norm_args* a, void* stream, const char** err) {
   if (!a->x || !a->y) { *err = "norm f32: null operand"; return MTX_ERR_INVALID; }
-  if (a->kind != 0 || a->mod_scale || a->mod_shift || a->q) { *err = "norm f32: LayerNorm without modulation / fp8 twin only"; return MTX_ERR_UNSUPPORTED; }
+  if ((a->kind != 0 && a->kind != 1) || a->mod_scale || a->mod_shift || a->q) { *err = "norm f32: LayerNorm / RMSNorm without modulation / fp8 twin only"; return MTX_ERR_UNSUPPORTED; }
   if (a->rows < 1 || a->c < 1) return MTX_OK;
   const dim3 grid((unsigned)((a->rows + 3) / 4));
   if (a->out_dtype == MTX_F32) MTX_LAUNCH(norm_f32_kernel<float>, grid, dim3(256), 0, stream, *a);

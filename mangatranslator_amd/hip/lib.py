@@ -49,7 +49,8 @@ class MtxLibrary:
                         ("mtx_yolo_decode", abi.YoloDecodeArgs), ("mtx_bubble_clean", abi.CleanArgs), ("mtx_detr", abi.DetrArgs),
                         ("mtx_quantize_mx", abi.QuantArgs), ("mtx_page_tail", abi.TailArgs),
                         ("mtx_text_color", abi.TextColorArgs),
-                        ("mtx_decode_attention", abi.DecodeAttnArgs), ("mtx_row_linear", abi.RowLinArgs)):
+                        ("mtx_decode_attention", abi.DecodeAttnArgs), ("mtx_row_linear", abi.RowLinArgs),
+                        ("mtx_causal_attention", abi.CausalAttnArgs), ("mtx_greedy_pick", abi.GreedyArgs)):
             getattr(d, name).argtypes = [C.POINTER(t), C.c_void_p]
         d.mtx_host_text_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.c_void_p, C.POINTER(C.c_int)]

@@ -408,6 +408,40 @@ class PlanBuilder:
         self._add(abi.OP_DECODE_ATTN, a, label)
         return o
 
+    def causal_attention(self, qkv, k_cache, v_cache, pos, o, rows, heads, kv_heads, d, max_len, scale, ld_qkv=None, ld_o=None,
+                         workspace=None, label="causal_attn"):
+        """MTX_OP_CAUSAL_ATTN: causal grouped-query attention of `rows` new rows [q | k | v] that appends them to the caches [max_len,
+        kv_heads * d]; `pos` (int32, positions already cached) lives on the device, so the recorded op serves every step.  The step (rows == 1)
+        merges its key splits through a zeroed workspace, made here unless one is passed (layers of one plan may share it: they run in order)"""
+        a = abi.CausalAttnArgs()
+        a.qkv, a.k_cache, a.v_cache, a.pos, a.o = _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos), _ptr(o)
+        a.rows, a.heads, a.kv_heads, a.d, a.max_len = rows, heads, kv_heads, d, max_len
+        a.ld_qkv, a.ld_o = (ld_qkv or (heads + 2 * kv_heads) * d), (ld_o or heads * d)
+        a.scale, a.dtype = scale, self.dtype
+        if rows == 1:
+            need = abi.causal_ws_bytes(heads, max_len)
+            if workspace is None:
+                workspace = self.buf((need,), torch.uint8, zero=True)
+            assert workspace.numel() * workspace.element_size() >= need
+            a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        self._add(abi.OP_CAUSAL_ATTN, a, label)
+        return o
+
+    def greedy_pick(self, logits, state, out, vocab, max_new, eos=(), advance=1, label="greedy_pick"):
+        """MTX_OP_GREEDY: the device end of a greedy step on fp32 `logits` [vocab].  `state` (int32 [4] = pos, n_out, done, token) and `out`
+        (int32 [max_new]) live on the device; unless done: out[n_out++] = token = arg max (lowest index among equals), pos += advance,
+        done = token in eos or n_out == max_new"""
+        eos = [int(e) for e in eos]
+        assert len(eos) <= 4 and logits.dtype == torch.float32 and state.dtype == torch.int32 and out.dtype == torch.int32
+        a = abi.GreedyArgs()
+        scratch = self.buf((max(abi.greedy_scratch_bytes(vocab), 8),), torch.uint8)
+        a.logits, a.state, a.out, a.scratch = _ptr(logits), _ptr(state), _ptr(out), scratch.data_ptr()
+        a.vocab, a.max_new, a.n_eos, a.advance = vocab, max_new, len(eos), advance
+        for i, e in enumerate(eos):
+            a.eos[i] = e
+        self._add(abi.OP_GREEDY, a, label)
+        return state
+
     def row_linear(self, a_t, w_t, rows, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE, res=None, ldres=None,
                    alpha=1.0, out_f32=False, label="rowlin"):
         """MTX_OP_ROWLIN: the skinny-row (rows <= 8) linear of a decode step, same epilogue and rounding contract as `gemm`"""

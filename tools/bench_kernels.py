@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [paddleocr] ..."""
 import os
 import sys
 
@@ -436,9 +436,40 @@ def mangaocr(dec_layers=2, beams=4, reps=3, iters=20):
         print(f"  per crop at {tokens} tokens ({beams} beams): {min(walls):.1f} ms wall (encoder + {tokens - 1} steps with upload / download)", flush=True)
 
 
+def paddleocr(reps=3, iters=20):
+    """PaddleOCR-VL at the wheel's default widths with the vocabulary cut to 8 192 (seeded weights): prefill ms at T = 300 / 1 300, ms per decode
+    step at a cache of 300 / 2 300 positions with the step's linears on the skinny-row kernel and on the tile GEMM, tokens/s of the shipped route"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import paddle_ocr_vl_checks as pc
+    routes = {"rowlin": lambda r, n, k: "rowlin", "gemm": lambda r, n, k: "gemm"}
+    models = {k: pc.hip_model(lib, abi.F16, 0, real=True, max_new_tokens=1024, max_prompt=1344, route=f) for k, f in routes.items()}
+    m = models["rowlin"]
+    for T, grid in ((300, (28, 40)), (1300, (64, 80))):
+        n_img = grid[0] * grid[1] // 4
+        pre = m._prefill(T, 4, n_img)
+        m.state.zero_(); pre.run(); torch.cuda.synchronize()
+        best = 1e9
+        for _ in range(reps):
+            m.state.zero_()
+            best = min(best, pre.time(1))
+        print(f"paddleocr f16: prefill T = {T}: {best:.3f} ms ({pre.n_ops} launches)", flush=True)
+    for k, mm in models.items():
+        step = mm._stepper()
+        for cache in (300, 2300):
+            best = 1e9
+            for _ in range(reps):
+                mm.state.copy_(torch.tensor([cache, 0, 0, 5], dtype=torch.int32)); step.run(graph=True); torch.cuda.synchronize()
+                mm.state.copy_(torch.tensor([cache, 0, 1, 5], dtype=torch.int32))          # done: the state stands still while the graph is timed
+                best = min(best, step.time(iters, graph=True))
+            print(f"  step graph, linears on {k}, cache {cache}: {best:.4f} ms per step = {1e3 / best:.0f} tokens/s ({step.n_ops} launches)", flush=True)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
+        if args[0] == "paddleocr":
+            paddleocr(); args = args[1:]
+            continue
         if args[0] == "mangaocr":                     # mangaocr [DEC_LAYERS]
             n = int(args[1]) if len(args) > 1 and args[1].isdigit() else 2
             mangaocr(n); args = args[2 if len(args) > 1 and args[1].isdigit() else 1:]

@@ -602,11 +602,50 @@ typedef struct mtx_greedy_args {
   int32_t eos[4];
 } mtx_greedy_args;
 
+/* ---- ABI 12, additive: the decode step for up to MTX_SLOTS_MAX independent sequences ("slots") in one launch (csrc/causal.hip; PaddleOCR-VL
+ * decodes a page's bubbles together).  The slots share one DEVICE int32 state block [MTX_SLOT_FIELDS][MTX_SLOTS_MAX], a structure of arrays
+ *   state[MTX_SLOT_POS][s]  state[MTX_SLOT_NOUT][s]  state[MTX_SLOT_DONE][s]  state[MTX_SLOT_TOKEN][s]  state[MTX_SLOT_ROPE][s]
+ * so that token[0 .. slots) and rope_row[0 .. slots) are the index vectors of two row gathers.  An empty slot holds done = 1.
+ *
+ * mtx_causal_step_batch: the rows == 1 step of mtx_causal_attention for `slots` sequences.  qkv [slots][ld_qkv], o [slots][ld_o]; slot s
+ * owns the caches k_cache + s * cache_stride, v_cache + s * cache_stride (elements, a multiple of 8) and the workspace region
+ * workspace + s * MTX_CAUSAL_WS_BYTES(heads, max_len); the workspace is ZEROED once by the caller and every counter is zero again when the
+ * launch ends.  Slot s takes part iff done[s] == 0 and 0 <= pos[s] < max_len; a slot that does not reads and writes nothing of its cache,
+ * its o row or its workspace region.  A slot that takes part gets, bit for bit, the o row and the cache row mtx_causal_attention(rows = 1)
+ * produces on that slot's operands alone.  Limits of the single op (d == 128, heads % kv_heads == 0, bf16 / f16, 16-byte alignment);
+ * slots outside 1 .. MTX_SLOTS_MAX: MTX_ERR_INVALID. */
+#define MTX_SLOTS_MAX 8
+#define MTX_SLOT_FIELDS 5
+#define MTX_SLOT_POS 0
+#define MTX_SLOT_NOUT 1
+#define MTX_SLOT_DONE 2
+#define MTX_SLOT_TOKEN 3
+#define MTX_SLOT_ROPE 4
+typedef struct mtx_causal_step_batch_args {
+  const void* qkv; void* k_cache; void* v_cache; const int32_t* state; void* o;
+  int32_t slots, heads, kv_heads, d, max_len;
+  int64_t ld_qkv, ld_o, cache_stride;
+  float scale; int32_t dtype;
+  void* workspace; int64_t workspace_bytes;
+} mtx_causal_step_batch_args;
+
+/* mtx_greedy_pick_batch: mtx_greedy_pick for `slots` rows of fp32 logits [slots][ld_logits] into out [slots][max_new], on the state block
+ * above; per slot the rules and the result of the single op (done changes nothing; lowest index among equal maxima; a NaN never wins, all
+ * NaN gives 0; n_out outside 0 .. max_new - 1 sets done and writes nothing), and rope_row += advance beside pos += advance.
+ * scratch: slots * MTX_GREEDY_SCRATCH_BYTES(vocab) bytes. */
+typedef struct mtx_greedy_batch_args {
+  const float* logits; int32_t* state; int32_t* out; void* scratch;
+  int64_t ld_logits;
+  int32_t slots, vocab, max_new, n_eos, advance;
+  int32_t eos[4];
+} mtx_greedy_batch_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
   MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17,
-  MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19, MTX_OP_CAUSAL_ATTN = 20, MTX_OP_GREEDY = 21
+  MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19, MTX_OP_CAUSAL_ATTN = 20, MTX_OP_GREEDY = 21,
+  MTX_OP_CAUSAL_STEP_BATCH = 22, MTX_OP_GREEDY_BATCH = 23
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -624,6 +663,7 @@ typedef struct mtx_op {
     mtx_groupnorm_args gn; mtx_ew_args ew; mtx_ca_args ca; mtx_img_args img;
     mtx_resize_thresh_args rt; mtx_memset_args ms; mtx_mask_select_args sel; mtx_preproc_args pre; mtx_yolo_decode_args yd; mtx_detr_args detr; mtx_quant_args quant; mtx_tail_args tail; mtx_textcolor_args tc;
     mtx_decode_attn_args dattn; mtx_rowlin_args rowlin; mtx_causal_attn_args cattn; mtx_greedy_args greedy;
+    mtx_causal_step_batch_args cstepb; mtx_greedy_batch_args greedyb;
   } u;
 } mtx_op;
 
@@ -660,6 +700,8 @@ MTX_API int mtx_decode_attention(const mtx_decode_attn_args* a, void* stream);
 MTX_API int mtx_row_linear(const mtx_rowlin_args* a, void* stream);
 MTX_API int mtx_causal_attention(const mtx_causal_attn_args* a, void* stream);
 MTX_API int mtx_greedy_pick(const mtx_greedy_args* a, void* stream);
+MTX_API int mtx_causal_step_batch(const mtx_causal_step_batch_args* a, void* stream);
+MTX_API int mtx_greedy_pick_batch(const mtx_greedy_batch_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ...utils.exceptions import ImageProcessingError
+from ...utils.exceptions import ImageProcessingError, ModelError
 from ...utils.logging import log_message
 from ..caching import detector_memo_path, get_cache, osb_text_memo_path
 from ..device import get_best_device
@@ -376,7 +376,12 @@ def extract_text_with_manga_ocr(images: List[Image.Image], verbose: bool = False
 
 
 def extract_text_with_paddle_ocr_vl(images: List[Image.Image], verbose: bool = False) -> List[str]:
-    def read_one(pair, img):
+    """One crop at a time through `model.generate`, as the reference — or, when the model decodes several sequences together (a shim with
+    `generate_many` and `slots` > 1: `ModelManager.paddle_ocr_vl_slots`) and the page has two or more readable crops, all of them through ONE
+    `generate_many` call.  Order, markers, stripping and decoding are the same on both paths, and so are the texts."""
+    what = "PaddleOCR-VL-1.6"
+
+    def prepare(pair, img):
         processor, model = pair
         messages = [{"role": "user", "content": [{"type": "image", "image": img}, {"type": "text", "text": "OCR:"}]}]
         ip = processor.image_processor
@@ -385,9 +390,69 @@ def extract_text_with_paddle_ocr_vl(images: List[Image.Image], verbose: bool = F
         for key in ("shortest_edge", "min_pixels"):
             if lo is None:
                 lo = size.get(key) if isinstance(size, dict) else getattr(size, key, None)
-        inputs = processor.apply_chat_template(messages, add_generation_prompt=True, tokenize=True, return_dict=True, return_tensors="pt",
-                                               processor_kwargs={"images_kwargs": {"size": {"shortest_edge": lo if lo is not None else 28 * 28 * 130,
-                                                                                             "longest_edge": 1280 * 28 * 28}}}).to(model.device)
-        outputs = model.generate(**inputs, max_new_tokens=1024)
-        return processor.decode(outputs[0][inputs["input_ids"].shape[-1]: -1])
-    return _run_recogniser(images, "PaddleOCR-VL-1.6", lambda: get_model_manager().get_paddle_ocr_vl(verbose=verbose), read_one, verbose)
+        return processor.apply_chat_template(messages, add_generation_prompt=True, tokenize=True, return_dict=True, return_tensors="pt",
+                                             processor_kwargs={"images_kwargs": {"size": {"shortest_edge": lo if lo is not None else 28 * 28 * 130,
+                                                                                           "longest_edge": 1280 * 28 * 28}}}).to(model.device)
+
+    def decode(pair, inputs, outputs):
+        return pair[0].decode(outputs[0][inputs["input_ids"].shape[-1]: -1])
+
+    def read_one(pair, img):
+        inputs = prepare(pair, img)
+        return decode(pair, inputs, pair[1].generate(**inputs, max_new_tokens=1024))
+
+    def get_pair():
+        return get_model_manager().get_paddle_ocr_vl(verbose=verbose)
+
+    def finish(text):
+        return text.strip() if text else ""
+
+    def read_together(pair):
+        """-> the texts, or None when fewer than two crops could be prepared (the per-image loop then serves the page)"""
+        texts, prepared = [None] * len(images), []
+        for i, img in enumerate(images):
+            if img is None:
+                log_message(f"Image {i + 1} is None (decode failure), skipping", always_print=True)
+                texts[i] = OCR_FAILED
+                continue
+            try:
+                prepared.append((i, prepare(pair, img)))
+            except Exception as e:
+                log_message(f"{what} failed for image {i + 1}: {e}", always_print=True)
+                texts[i] = OCR_FAILED
+        if len(prepared) < 2:
+            return None
+        log_message(f"Processing {len(prepared)} images together with {what}", verbose=verbose)
+        try:
+            results = pair[1].generate_many([dict(inputs) for _, inputs in prepared], max_new_tokens=1024)
+            if len(results) != len(prepared):
+                raise ModelError(f"generate_many returned {len(results)} results for {len(prepared)} prompts")
+        except Exception as e:                                   # one bad batch must not cost the page its text
+            log_message(f"{what} failed on the batch ({e}); reading the images one by one", always_print=True)
+            results = []
+            for _, inputs in prepared:
+                try:
+                    results.append(pair[1].generate(**inputs, max_new_tokens=1024))
+                except Exception as e1:
+                    results.append(e1)
+        for (i, inputs), out in zip(prepared, results):
+            try:
+                if isinstance(out, Exception):
+                    raise out
+                texts[i] = finish(decode(pair, inputs, out))
+            except Exception as e:
+                log_message(f"{what} failed for image {i + 1}: {e}", always_print=True)
+                texts[i] = OCR_FAILED
+        return texts
+
+    if sum(img is not None for img in images) >= 2:
+        try:
+            pair = get_pair()
+            model = pair[1]
+            if callable(getattr(model, "generate_many", None)) and int(getattr(model, "slots", 1) or 1) > 1:
+                texts = read_together(pair)
+                if texts is not None:
+                    return texts
+        except Exception:
+            pass                                                 # the loop below meets the same failure and reports it as it always has
+    return _run_recogniser(images, what, get_pair, read_one, verbose)

@@ -693,7 +693,10 @@ class ModelManager:
         the wheel's processor and a `generate` shim over `PaddleOcrVlHip` (core/ml/paddle_ocr_vl.py: vision tower, projector and text decoder
         as libmtx_hip plans, greedy decoding on the device) are built from the directory staged under models/paddleocr-vl-1.6 and cached in
         the slot; nothing staged -> ModelError, which `extract_text_with_paddle_ocr_vl` turns into the reference's "[OCR FAILED]" markers.
-        `paddle_ocr_vl_storage` ("f16" | "bf16") picks the storage type before the first call."""
+        `paddle_ocr_vl_storage` ("f16" | "bf16") picks the storage type before the first call, `paddle_ocr_vl_slots` (1 .. 8) how
+        many crops `extract_text_with_paddle_ocr_vl` decodes together (`PaddleOcrVlHip(slots=)`: a set of key / value caches per slot, about
+        44 MB at the published sizes; 1 = one crop at a time, nothing allocated).  The default is 8: of B = 1, 2, 4, 8 it gave the most tokens
+        per second on the MI355X, 5.0 x the single step at a 300-position cache (docs/experiments.md); the texts do not depend on it."""
         with self._lock:
             if self.is_loaded(ModelType.PADDLE_OCR_VL):
                 return self.models[ModelType.PADDLE_OCR_VL]
@@ -708,7 +711,10 @@ class ModelManager:
                 storage = getattr(self, "paddle_ocr_vl_storage", "f16")
                 if storage not in ("f16", "bf16"):
                     raise ModelError(f"paddle_ocr_vl_storage must be 'f16' or 'bf16', not {storage!r}")
-                pair = load_pair(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16}[storage])
+                slots = getattr(self, "paddle_ocr_vl_slots", 8)
+                if not isinstance(slots, int) or not 1 <= slots <= abi.SLOTS_MAX:
+                    raise ModelError(f"paddle_ocr_vl_slots must be an integer 1 .. {abi.SLOTS_MAX}, not {slots!r}")
+                pair = load_pair(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16}[storage], slots=slots)
             except ModelError:
                 raise
             except Exception as e:

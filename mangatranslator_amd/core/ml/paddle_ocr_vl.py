@@ -4,10 +4,11 @@ driven by core/image/ocr_detection.py:886-962 as `model.generate(**inputs, max_n
 decoder with multimodal rotary positions.
 
     PaddleOcrVlHip(state_dict, hp).generate(input_ids=, pixel_values=, image_grid_thw=, max_new_tokens=) -> int64 [1, T + n]
+    PaddleOcrVlHip(state_dict, hp, slots=B).generate_many([dict(input_ids=, pixel_values=, image_grid_thw=), ...]) -> [int64 [1, T + n] | ModelError]
 
   * every size comes from the checkpoint's `config.json` / `generation_config.json` (`read_checkpoint`); what this build does not serve raises
-    ModelError by name: a rope type other than "default", sliding-window layers, sampling, beams, a repetition penalty, video, several images,
-    a batch;
+    ModelError by name: a rope type other than "default", sliding-window layers, sampling, beams, a repetition penalty, video, several images;
+    `generate` itself stays batch 1;
   * rotary turns without a new kernel: the wheel turns the pairs (i, i + d/2) (`rotate_half`), MTX_EW_QK_ROPE turns interleaved pairs, so the
     output rows of every q_proj / k_proj (and their biases) are permuted per head at load so that pair (i, i + d/2) lands on (2i, 2i + 1) — the
     same permutation on q and k leaves q . k unchanged, v and the output projection never see it.  The cos | sin rows are built on the host:
@@ -21,6 +22,17 @@ decoder with multimodal rotary positions.
   * ONE step plan, captured once and replayed per token: the same layer on one row (`linear_route`: skinny-row kernel or tile GEMM per shape),
     MTX_OP_CAUSAL_ATTN with rows = 1, MTX_OP_GREEDY with advance = 1.  Token, cache length and the rotary row all come from the 16-byte device
     state {pos, n_out, done, token}: the host replays `check_every` steps, then downloads the state and stops at `done`;
+  * `slots = B` (2 .. 8): a page's crops decode together.  Each slot has its own key / value caches, its lane of the int32 [5][8] state
+    block (pos | n_out | done | token | rope_row, include/mtx_hip.h) and its row of `out`; ONE batched step plan on B rows, captured once:
+    token and rotary row gathered over token[0 .. B) and rope_row[0 .. B), the same layers with every linear on B rows (the skinny-row
+    kernel reads the weights once for all of them), MTX_OP_CAUSAL_STEP_BATCH, the head on B rows, MTX_OP_GREEDY_BATCH.  Finished and empty
+    slots ride along in the linears (rows are independent); attention and the pick skip them.  Vision and prefill stay per sequence on the
+    plans and the staging set above (the plan caches stay as bounded as they are); device copies then move cache rows [0, T) and the state
+    into the slot.  `generate_many` keeps the slots full from its list ("in-flight batching") and returns, item by item, exactly the tokens
+    `generate` returns: every op of the step is per row, and the two batched ops are bit-identical per slot to the single ones.
+    Memory per slot: t_layers * 2 * (max_prompt + max_new_tokens) * t_kv * 128 * 2 bytes of cache + 4 * vocab of logits + 4 * max_new_tokens
+    of output + (heads * 4 rounded up to 256) + heads * ceil(max_len / 64) * 528 bytes of attention workspace — at the wheel's default sizes
+    (18 layers, 16 / 2 heads, vocabulary 103 424) and the default 1 344 + 1 024 positions 43.6 MB + 0.4 MB + 0.3 MB = 44.4 MB per slot;
   * storage: f16 by default, bf16 selectable — weights and the linears' operands in that type, the residual stream and every norm input fp32.
 
 PARITY UNPINNED (nothing on the build machine can pin them; DESIGN.md's oracle table says the same):
@@ -235,11 +247,16 @@ def text_rope_table(pos3: torch.Tensor, section: List[int], theta: float, d: int
 # ---- the model ----------------------------------------------------------------------------------------------------------------------------------
 class PaddleOcrVlHip:
     def __init__(self, state_dict: dict, hp: dict, device="cuda", lib=None, dtype: int = abi.F16, graph: bool = True, max_new_tokens: int = 1024,
-                 max_prompt: int = 1280 + 64, check_every: int = 8, route: Optional[Callable[[int, int, int], str]] = None):
+                 max_prompt: int = 1280 + 64, check_every: int = 8, route: Optional[Callable[[int, int, int], str]] = None, slots: int = 1):
         """hp: `hparams_from_config`; state_dict: `normalise_state_dict`'s names.  max_prompt: the longest prompt served (the processor's
-        max_pixels bound gives at most 1 280 image tokens; the chat template adds a few tens); the cache holds max_prompt + max_new_tokens."""
+        max_pixels bound gives at most 1 280 image tokens; the chat template adds a few tens); the cache holds max_prompt + max_new_tokens.
+        slots: how many sequences `generate_many` decodes together (1 .. 8; 1 allocates nothing new), 2 * t_layers * max_len * t_kv * 128
+        elements of cache per slot plus a row of logits and of output (the module docstring has the sum)."""
         if dtype not in (abi.BF16, abi.F16):
             raise ModelError(f"{WHAT}: storage dtype must be f16 or bf16")
+        if not 1 <= int(slots) <= abi.SLOTS_MAX:
+            raise ModelError(f"{WHAT}: slots must be 1 .. {abi.SLOTS_MAX}, not {slots!r}")
+        self.slots = int(slots)
         self.lib = lib if lib is not None else get_library()
         self.device = torch.device(device)
         self.hp, self.dtype, self.tdt = hp, dtype, {abi.BF16: torch.bfloat16, abi.F16: torch.float16}[dtype]
@@ -249,7 +266,8 @@ class PaddleOcrVlHip:
         self._graph = graph and not self.lib.is_simulator
         self._lock = threading.Lock()
         self._vis, self._pre = PlanCache(4), PlanCache(6)
-        self._step = None
+        self._step = self._step_b = None
+        self.fill_log = []                                           # (item, slot, [(item, n_out) of the other live slots]) per fill of the last generate_many
         self._pack({k: v.detach().float().cpu() for k, v in state_dict.items()})
         f32, i32 = torch.float32, torch.int32
         C, kvw = hp["t_dim"], hp["t_kv"] * HEAD_DIM
@@ -260,6 +278,16 @@ class PaddleOcrVlHip:
         self.img_rows = z(max(self.max_prompt, 8), C)                # the projector's output, read by the prefill plans
         self.step_rope = z(self.max_len, HEAD_DIM)                   # cos | sin row of the token fed at cache position p (set per prompt)
         self.logits = z(1, hp["vocab"])
+        if self.slots > 1:
+            B = self.slots
+            self.slot_caches = [(z(B, self.max_len, kvw, dt=self.tdt), z(B, self.max_len, kvw, dt=self.tdt)) for _ in range(hp["t_layers"])]
+            self.slot_state = z(abi.SLOT_FIELDS, abi.SLOTS_MAX, dt=i32)          # pos | n_out | done | token | rope_row, one lane per slot
+            self.slot_state[abi.SLOT_DONE] = 1                       # empty slots sit out
+            self.slot_out = z(B, self.max_new, dt=i32)
+            self.slot_logits = z(B, hp["vocab"])
+            # cos | sin row of rotary position r, all three axes equal: the token fed at cache position p of a prompt sits at r = p + delta
+            p = torch.arange(self.max_len)
+            self.slot_rope = self._c(text_rope_table(p[None].expand(3, -1), hp["mrope"], hp["theta"], HEAD_DIM).reshape(self.max_len, HEAD_DIM), f32)
 
     @classmethod
     def from_directory(cls, root, **kw):
@@ -369,20 +397,30 @@ class PaddleOcrVlHip:
         return plan
 
     # ---- the text decoder ------------------------------------------------------------------------
-    def _layers(self, pb, x, rows, rope, lin, close):
-        """the decoder layers on `rows` rows of the fp32 stream x; -> the stream after the last layer"""
+    def _layers(self, pb, x, rows, rope, lin, close, slots: int = 0):
+        """the decoder layers on `rows` rows of the fp32 stream x; -> the stream after the last layer.  slots = B > 0: the rows are the
+        steps of B independent sequences on the slot caches (MTX_OP_CAUSAL_STEP_BATCH)"""
         hp = self.hp
         C, heads, kv, I = hp["t_dim"], hp["t_heads"], hp["t_kv"], hp["t_mlp"]
         qw = (heads + 2 * kv) * HEAD_DIM
-        ws = pb.buf((abi.causal_ws_bytes(heads, self.max_len),), torch.uint8, zero=True) if rows == 1 else None
+        ws = None
+        if slots:
+            ws = pb.buf((slots * abi.causal_ws_bytes(heads, self.max_len),), torch.uint8, zero=True)
+        elif rows == 1:
+            ws = pb.buf((abi.causal_ws_bytes(heads, self.max_len),), torch.uint8, zero=True)
         for i, Lr in enumerate(self.t_layers):
             tag = f"dec{i}"
             kc, vc = self.caches[i]
             a = pb.norm(x, pb.buf((rows, C), self.tdt), rows, C, gamma=Lr["n1"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm1")
             qkv = lin(a, Lr["qkv"], qw, C, tag + ".qkv")
             pb.qk_rope(Act(qkv.view(1, 1, rows, qw), 1, 1, rows, (heads + kv) * HEAD_DIM), rope, HEAD_DIM, label=tag + ".rope")
-            o = pb.causal_attention(qkv, kc, vc, self.state[0:1], pb.buf((rows, heads * HEAD_DIM), self.tdt), rows, heads, kv, HEAD_DIM, self.max_len,
-                                    HEAD_DIM ** -0.5, workspace=ws, label=tag + ".attn")
+            if slots:
+                skc, svc = self.slot_caches[i]
+                o = pb.causal_step_batch(qkv, skc, svc, self.slot_state, pb.buf((rows, heads * HEAD_DIM), self.tdt), slots, heads, kv, HEAD_DIM, self.max_len,
+                                         HEAD_DIM ** -0.5, workspace=ws, label=tag + ".attn")
+            else:
+                o = pb.causal_attention(qkv, kc, vc, self.state[0:1], pb.buf((rows, heads * HEAD_DIM), self.tdt), rows, heads, kv, HEAD_DIM, self.max_len,
+                                        HEAD_DIM ** -0.5, workspace=ws, label=tag + ".attn")
             x1 = close(o, Lr["o"], C, heads * HEAD_DIM, x, tag + ".o_proj")
             b = pb.norm(x1, pb.buf((rows, C), self.tdt), rows, C, gamma=Lr["n2"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm2")
             gu = lin(b, Lr["gu"], 2 * I, C, tag + ".gate_up")
@@ -392,15 +430,20 @@ class PaddleOcrVlHip:
             x = close(hmid, Lr["down"], C, I, x1, tag + ".down")
         return x
 
-    def _head(self, pb, x_last, advance):
+    def _head(self, pb, x_last, advance, slots: int = 0):
+        """final norm, the head and the pick on the last row — or, with slots = B > 0, on the B rows of the batched step"""
         hp = self.hp
         C = hp["t_dim"]
-        a = pb.norm(x_last, pb.buf((1, C), self.tdt), 1, C, gamma=self.W["t_norm"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label="final_norm")
+        rows, logits = (slots, self.slot_logits) if slots else (1, self.logits)
+        a = pb.norm(x_last, pb.buf((rows, C), self.tdt), rows, C, gamma=self.W["t_norm"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label="final_norm")
         if self.route(1, hp["vocab"], C) == "rowlin":
-            pb.row_linear(a, self.W["head"][0], 1, hp["vocab"], C, out=self.logits, out_f32=True, label="head")
+            pb.row_linear(a, self.W["head"][0], rows, hp["vocab"], C, out=logits, out_f32=True, label="head")
         else:
-            pb.gemm(a, self.W["head"][0], 1, hp["vocab"], C, out=self.logits, out_f32=True, label="head")
-        pb.greedy_pick(self.logits, self.state, self.out, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
+            pb.gemm(a, self.W["head"][0], rows, hp["vocab"], C, out=logits, out_f32=True, label="head")
+        if slots:
+            pb.greedy_pick_batch(logits, self.slot_state, self.slot_out, slots, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
+        else:
+            pb.greedy_pick(logits, self.state, self.out, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
 
     def _prefill(self, T: int, start: int, n_img: int):
         key = (T, start, n_img)
@@ -434,24 +477,44 @@ class PaddleOcrVlHip:
         e16 = pb.row_gather(self.W["tok"], pb.buf((1, C), self.tdt), self.state[3:4], 1, C, label="embed")
         x = pb.cvt_f32(Act(e16.view(1, 1, 1, C), 1, 1, 1, C), self.dtype, label="embed.f32").t.view(1, C)
         rope = pb.row_gather(self.step_rope, pb.buf((1, HEAD_DIM), torch.float32), self.state[0:1], 1, HEAD_DIM, label="rope.row", dtype=abi.F32)
-
-        def lin(a, wb, n, k, label):
-            if self.route(1, n, k) == "rowlin":
-                return pb.row_linear(a, wb[0], 1, n, k, label=label)
-            return pb.gemm(a, wb[0], 1, n, k, label=label)
-
-        def close(a, wb, n, k, res, label):
-            """stream <- res + a @ W^T in fp32 (the skinny-row kernel takes no fp32 residual: its fp32 output and one fp32 add)"""
-            if self.route(1, n, k) != "rowlin":
-                return pb.gemm(a, wb[0], 1, n, k, res=res, res_f32=True, out_f32=True, label=label)
-            y = pb.row_linear(a, wb[0], 1, n, k, out_f32=True, label=label)
-            return pb.ew(abi.EW_ADD, Act(y.view(1, 1, 1, n), 1, 1, 1, n), Act(res.view(1, 1, 1, n), 1, 1, 1, n),
-                         out=Act(pb.buf((1, 1, 1, n), torch.float32), 1, 1, 1, n), label=label + ".add", dtype=abi.F32).t.view(1, n)
-
+        lin, close = self._step_linears(pb, 1)
         x = self._layers(pb, x, 1, rope, lin, close)
         self._head(pb, x, advance=1)
         self._step = pb.build()
         return self._step
+
+    def _step_linears(self, pb, rows):
+        """(lin, close) of a step plan on `rows` rows; the kernel per shape is the single step's (`route(1, n, k)`), whatever `rows`"""
+        def lin(a, wb, n, k, label):
+            if self.route(1, n, k) == "rowlin":
+                return pb.row_linear(a, wb[0], rows, n, k, label=label)
+            return pb.gemm(a, wb[0], rows, n, k, label=label)
+
+        def close(a, wb, n, k, res, label):
+            """stream <- res + a @ W^T in fp32 (the skinny-row kernel takes no fp32 residual: its fp32 output and one fp32 add)"""
+            if self.route(1, n, k) != "rowlin":
+                return pb.gemm(a, wb[0], rows, n, k, res=res, res_f32=True, out_f32=True, label=label)
+            y = pb.row_linear(a, wb[0], rows, n, k, out_f32=True, label=label)
+            return pb.ew(abi.EW_ADD, Act(y.view(1, 1, rows, n), 1, 1, rows, n), Act(res.view(1, 1, rows, n), 1, 1, rows, n),
+                         out=Act(pb.buf((1, 1, rows, n), torch.float32), 1, 1, rows, n), label=label + ".add", dtype=abi.F32).t.view(rows, n)
+        return lin, close
+
+    def _stepper_batch(self):
+        """ONE plan on B = slots rows, captured once: row s is slot s's step, fed from its lane of the state block"""
+        if self._step_b is not None:
+            return self._step_b
+        hp, B = self.hp, self.slots
+        C = hp["t_dim"]
+        st = self.slot_state
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        e16 = pb.row_gather(self.W["tok"], pb.buf((B, C), self.tdt), st[abi.SLOT_TOKEN], B, C, label="embed")
+        x = pb.cvt_f32(Act(e16.view(1, 1, B, C), 1, 1, B, C), self.dtype, label="embed.f32").t.view(B, C)
+        rope = pb.row_gather(self.slot_rope, pb.buf((B, HEAD_DIM), torch.float32), st[abi.SLOT_ROPE], B, HEAD_DIM, label="rope.row", dtype=abi.F32)
+        lin, close = self._step_linears(pb, B)
+        x = self._layers(pb, x, B, rope, lin, close, slots=B)
+        self._head(pb, x, advance=1, slots=B)
+        self._step_b = pb.build()
+        return self._step_b
 
     # ---- running ---------------------------------------------------------------------------------
     def _check_inputs(self, input_ids, pixel_values, image_grid_thw, kw):
@@ -519,6 +582,108 @@ class PaddleOcrVlHip:
             new = new[:eos[0] + 1]
         return torch.cat([input_ids[0].to(torch.long).cpu(), new])[None].to(input_ids.device)
 
+    def _check_item(self, item, budget):
+        """everything `generate` would refuse about one item of `generate_many`, before any device work"""
+        if not isinstance(item, dict):
+            raise ModelError(f"{WHAT}: generate_many takes dicts with input_ids, pixel_values and image_grid_thw")
+        ids, pix, thw = item.get("input_ids"), item.get("pixel_values"), item.get("image_grid_thw")
+        self._check_inputs(ids, pix, thw, {k: v for k, v in item.items() if k not in ("input_ids", "pixel_values", "image_grid_thw")})
+        T = int(ids.shape[1])
+        gh, gw = int(thw[0, 1]), int(thw[0, 2])
+        if T > self.max_prompt:
+            raise ModelError(f"{WHAT}: a prompt of {T} tokens exceeds the {self.max_prompt} this model was built for")
+        if gh % 2 or gw % 2 or gh * gw // 4 > self.img_rows.shape[0]:
+            raise ModelError(f"{WHAT}: an image grid of {gh} x {gw} patches is not served (even sides, at most {self.img_rows.shape[0]} merged tokens)")
+        if pix.shape[0] != gh * gw or pix[0].numel() != self.patch_k:
+            raise ModelError(f"{WHAT}: pixel_values {tuple(pix.shape)} do not match the grid {gh} x {gw}")
+        if not 1 <= budget <= self.max_new:
+            raise ModelError(f"{WHAT}: max_new_tokens {budget} is outside 1 .. {self.max_new} this model was built for")
+
+    def _fill_slot(self, slot: int, item) -> int:
+        """vision + prefill on the staging set, then device copies (same stream) of cache rows [0, T) and the state into the slot.  -> T"""
+        ids = item["input_ids"]
+        T = self.prefill(ids, item["pixel_values"], item["image_grid_thw"])
+        for (kc, vc), (skc, svc) in zip(self.caches, self.slot_caches):
+            skc[slot, :T].copy_(kc[:T])
+            svc[slot, :T].copy_(vc[:T])
+        self.slot_state[:4, slot].copy_(self.state)
+        # the token fed at cache position T sits at rotary position T + delta = the prompt's largest position id + 1 (as `prefill`'s step_rope)
+        tok = ids[0].to(torch.long).cpu()
+        gh, gw = int(item["image_grid_thw"][0, 1]), int(item["image_grid_thw"][0, 2])
+        delta = int(rope_positions(tok == self.hp["image_token"], gh, gw, self.hp["merge"]).max()) + 1 - T
+        self.slot_state[abi.SLOT_ROPE, slot] = max(T + delta, 0)
+        self.slot_out[slot, 0:1].copy_(self.out[0:1])
+        return T
+
+    def generate_many(self, items, max_new_tokens: Optional[int] = None, check_every: Optional[int] = None) -> list:
+        """`generate` for a list of prompts, up to `slots` of them in flight in one batched step plan: -> [int64 [1, T + n] | ModelError], in
+        the order given, each tensor exactly what `generate` returns for that item.  A refused item leaves its ModelError in its place and
+        does not stop the others.  The host reads 20 bytes of state per slot every `check_every` steps."""
+        budget = self.max_new if max_new_tokens is None else int(max_new_tokens)
+        every = self.check_every if check_every is None else max(1, int(check_every))
+        items = list(items)
+        results = [None] * len(items)
+        pending = []
+        for i, item in enumerate(items):
+            try:
+                self._check_item(item, budget)
+                pending.append(i)
+            except ModelError as e:
+                results[i] = e
+        if self.slots == 1:
+            for i in pending:
+                try:
+                    it = items[i]
+                    results[i] = self.generate(input_ids=it["input_ids"], pixel_values=it["pixel_values"], image_grid_thw=it["image_grid_thw"],
+                                               max_new_tokens=budget, check_every=every)
+                except ModelError as e:
+                    results[i] = e
+            return results
+        B = self.slots
+        pending.reverse()                                            # pop() takes them in the order given
+        with self._lock:
+            step = self._stepper_batch()
+            owner = [None] * B                                       # slot -> item index
+            n_out = [0] * B
+            self.fill_log = []
+            self.slot_state[abi.SLOT_DONE] = 1
+            while pending or any(o is not None for o in owner):
+                for s in range(B):
+                    while owner[s] is None and pending:
+                        i = pending.pop()
+                        try:
+                            self._fill_slot(s, items[i])
+                        except ModelError as e:                      # (a prompt whose placeholders do not match its grid: the slot stays free)
+                            results[i] = e
+                            self.slot_state[abi.SLOT_DONE, s] = 1
+                            continue
+                        self.fill_log.append((i, s, [(owner[t], n_out[t]) for t in range(B) if t != s and owner[t] is not None]))
+                        owner[s], n_out[s] = i, 1
+                st = self.slot_state[:, :B].cpu()
+                harvested = False
+                for s in range(B):
+                    if owner[s] is None:
+                        continue
+                    n_out[s] = int(st[abi.SLOT_NOUT, s])
+                    if not int(st[abi.SLOT_DONE, s]) and n_out[s] < budget:
+                        continue
+                    ids = items[owner[s]]["input_ids"]
+                    new = self.slot_out[s, :min(n_out[s], budget)].to(torch.long).cpu()
+                    eos = [k for k, t in enumerate(new.tolist()) if t in self.hp["eos"]]
+                    if eos:
+                        new = new[:eos[0] + 1]
+                    results[owner[s]] = torch.cat([ids[0].to(torch.long).cpu(), new])[None].to(ids.device)
+                    self.slot_state[abi.SLOT_DONE, s] = 1
+                    owner[s], harvested = None, True
+                if harvested and pending:
+                    continue                                         # refill before stepping
+                live = [budget - n_out[s] for s in range(B) if owner[s] is not None]
+                if not live:
+                    continue
+                for _ in range(min(every, max(live))):
+                    step.run(graph=self._graph)
+        return results
+
     def step_logits(self, token: int) -> torch.Tensor:
         """teacher forcing (parity tests): feed `token` at the current position instead of the model's own pick -> fp32 logits [vocab] of the next"""
         st = self.read_state()
@@ -527,10 +692,10 @@ class PaddleOcrVlHip:
         return self.logits[0].float().cpu().clone()
 
     def close(self):
-        for p in [self._step, *self._vis.values(), *self._pre.values()]:
+        for p in [self._step, self._step_b, *self._vis.values(), *self._pre.values()]:
             if p is not None:
                 p.close()
-        self._step = None
+        self._step = self._step_b = None
         self._vis.clear()
         self._pre.clear()
 
@@ -544,6 +709,13 @@ class GenerateShim:
 
     def generate(self, **kw):
         return self.model.generate(**kw)
+
+    @property
+    def slots(self) -> int:
+        return self.model.slots
+
+    def generate_many(self, items, **kw):
+        return self.model.generate_many(items, **kw)
 
     def close(self):
         self.model.close()

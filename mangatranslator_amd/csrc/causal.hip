@@ -15,6 +15,10 @@
 //                       write-through; the workgroup that draws the last ticket merges the records in key order (mtx_device.h, hand-offs).
 //   greedy pick         arg max of the fp32 logits in 4096-wide chunks (value, lowest index), then one wave that folds the chunks and
 //                       advances the 16-byte decode state.  Two launches: the second starts a launch boundary after the first.
+//   slot-batched step   the step and the pick for up to MTX_SLOTS_MAX independent sequences in one launch each (mtx_causal_step_batch_args /
+//                       mtx_greedy_batch_args): the slot is folded into the grid, every slot has its own cache, workspace region and lane of
+//                       the int32 [5][8] state block; the step's body is causal_step_body.inc, included in both step kernels, so a slot's
+//                       result is bit for bit the single op's.  A finished or empty slot leaves before any barrier or ticket.
 #include "mtx_device.h"
 #include <limits.h>
 
@@ -197,132 +201,13 @@ __device__ __forceinline__ void ca_merge(float& m, float& l, float (&acc)[8], fl
 // grid (splits of CA_S keys, kv heads, chunks of G query heads); gfull = heads / kv_heads = gridDim.z * G
 template <typename T, int G>
 __global__ __launch_bounds__(256) void causal_step_kernel(mtx_causal_attn_args p, int gfull) {
-  __shared__ float part[4][G][CA_REC];
-  __shared__ int last_flag;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int sub = tid & 15;                  // which 8 of the head's 128 elements
-  const int grp = tid >> 4;                  // 0..15: the keys j = j0 + grp
-  const int pos = *p.pos;
-  if (pos < 0 || pos >= p.max_len) return;   // (workgroup-uniform)
-  const int split = blockIdx.x, n_active = pos / CA_S + 1;
-  if (split >= n_active) return;             // splits wholly in the future draw no ticket
-  const int kvh = blockIdx.y;
-  const int h0 = kvh * gfull + (int)blockIdx.z * G;
-  const int nsplit = (int)gridDim.x;
-  const long kvw = (long)p.kv_heads * CA_D;
-  const T* row = reinterpret_cast<const T*>(p.qkv);
-  T* KC = reinterpret_cast<T*>(p.k_cache) + (long)kvh * CA_D + sub * 8;
-  T* VC = reinterpret_cast<T*>(p.v_cache) + (long)kvh * CA_D + sub * 8;
-  float q[G][8], k_own[8], v_own[8];
-#pragma unroll
-  for (int g = 0; g < G; ++g) ca_load8(row + (long)(h0 + g) * CA_D + sub * 8, q[g]);
-  ca_load8(row + (long)p.heads * CA_D + (long)kvh * CA_D + sub * 8, k_own);
-  ca_load8(row + (long)p.heads * CA_D + kvw + (long)kvh * CA_D + sub * 8, v_own);
-  if (split == n_active - 1 && blockIdx.z == 0 && grp == 0) {      // the row's k and v go to cache[pos] (nobody reads that position in this launch)
-    *reinterpret_cast<u32x4*>(KC + (long)pos * kvw) = pack8<T>(k_own);            // (values of the storage type: the round trip through float is exact)
-    *reinterpret_cast<u32x4*>(VC + (long)pos * kvw) = pack8<T>(v_own);
-  }
-  float m[G], l[G], acc[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    m[g] = CA_NEG; l[g] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
-  }
-  const int jbeg = split * CA_S;
-  const int jend = jbeg + CA_S < pos + 1 ? jbeg + CA_S : pos + 1;
-  for (int j0 = jbeg; j0 < jend; j0 += 16) {                        // workgroup-uniform trip count: every lane reaches the shuffles
-    const int j = j0 + grp;
-    float kf[8], vf[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { kf[e] = k_own[e]; vf[e] = v_own[e]; }
-    if (j < pos) {
-      ca_load8(KC + (long)j * kvw, kf);
-      ca_load8(VC + (long)j * kvw, vf);
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += q[g][e] * kf[e];
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
-      if (j < jend) {
-        s *= p.scale;
-        const float mn = s > m[g] ? s : m[g];
-        const float f = __expf(m[g] - mn), w = __expf(s - mn);
-        l[g] = l[g] * f + w;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[g][e] = acc[g][e] * f + w * vf[e];
-        m[g] = mn;
-      }
-    }
-  }
-  // the 4 lane groups of a wave, then the 4 waves
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-#pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {
-      const float m2 = __shfl_xor(m[g], off, 64), l2 = __shfl_xor(l[g], off, 64);
-      float a2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a2[e] = __shfl_xor(acc[g][e], off, 64);
-      ca_merge(m[g], l[g], acc[g], m2, l2, a2);
-    }
-    if (lane < 16) {
-      if (sub == 0) { part[wave][g][0] = m[g]; part[wave][g][1] = l[g]; }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) part[wave][g][4 + sub * 8 + e] = acc[g][e];
-    }
-  }
-  __syncthreads();
-  unsigned* counter = reinterpret_cast<unsigned*>(p.workspace) + (kvh * (int)gridDim.z + (int)blockIdx.z);
-  float* recs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(p.workspace) + (((long)p.heads * 4 + 255) / 256) * 256);
-  const int g = tid >> 4;                    // threads 0 .. 16 G - 1 finish: 16 lanes per query head
-  float fm = CA_NEG, fl = 0.f, facc[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) facc[e] = 0.f;
-  if (g < G) {
-    fm = part[0][g][0]; fl = part[0][g][1];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) facc[e] = part[0][g][4 + sub * 8 + e];
-    for (int w = 1; w < 4; ++w) {
-      float a2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a2[e] = part[w][g][4 + sub * 8 + e];
-      ca_merge(fm, fl, facc, part[w][g][0], part[w][g][1], a2);
-    }
-    float* rec = recs + ((long)(h0 + g) * nsplit + split) * CA_REC;
-    if (sub == 0) { agent_store(rec, fm); agent_store(rec + 1, fl); }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) agent_store(rec + 4 + sub * 8 + e, facc[e]);
-  }
-  MTX_WAIT_VMEM();                                       // every storing wave drains its write-through stores
-  __syncthreads();
-  if (tid == 0) last_flag = agent_ticket(counter) + 1 == (unsigned)n_active;
-  __syncthreads();
-  if (!last_flag) return;                                // (workgroup-uniform)
-  // ---- the last arriver: the records of this head chunk, merged in key order whoever came last
-  if (tid == 0) { agent_acquire(); agent_store(counter, 0u); }      // zero again for the next launch (a launch boundary away)
-  __syncthreads();
-  if (g < G) {
-    const float* r0 = recs + (long)(h0 + g) * nsplit * CA_REC;
-    fm = r0[0]; fl = r0[1];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) facc[e] = r0[4 + sub * 8 + e];
-    for (int s = 1; s < n_active; ++s) {
-      const float* r = r0 + (long)s * CA_REC;
-      float a2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a2[e] = r[4 + sub * 8 + e];
-      ca_merge(fm, fl, facc, r[0], r[1], a2);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) facc[e] = facc[e] / fl;           // fl >= 1: the key at the running maximum weighs exp(0)
-    *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.o) + (long)(h0 + g) * CA_D + sub * 8) = pack8<T>(facc);
-  }
+#define CA_STEP_Z (int)blockIdx.z
+#define CA_STEP_Z_IS_0 blockIdx.z == 0
+#define CA_STEP_NZ (int)gridDim.z
+#include "causal_step_body.inc"
+#undef CA_STEP_Z
+#undef CA_STEP_Z_IS_0
+#undef CA_STEP_NZ
 }
 
 int causal_attn_launch(const mtx_causal_attn_args* a, void* stream, const char** err) {
@@ -370,7 +255,8 @@ __device__ __forceinline__ void gp_wave(float& bv, int& bi) {
   }
 }
 
-__global__ __launch_bounds__(256) void greedy_chunk_kernel(mtx_greedy_args p) {
+// one chunk of one row of logits -> its (value, lowest index) record
+__device__ __forceinline__ void gp_chunk(const float* logits, int vocab, void* scratch) {
   __shared__ float wv[4];
   __shared__ int wi[4];
   const int tid = threadIdx.x;
@@ -380,41 +266,53 @@ __global__ __launch_bounds__(256) void greedy_chunk_kernel(mtx_greedy_args p) {
 #pragma unroll 4
   for (int k = 0; k < MTX_GREEDY_CHUNK / 256; ++k) {
     const long i = base + tid + 256 * k;
-    if (i < p.vocab) gp_take(bv, bi, p.logits[i], (int)i);
+    if (i < vocab) gp_take(bv, bi, logits[i], (int)i);
   }
   gp_wave(bv, bi);
   if ((tid & 63) == 0) { wv[tid >> 6] = bv; wi[tid >> 6] = bi; }
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < 4; ++w) gp_take(bv, bi, wv[w], wi[w]);
-    float* rec = reinterpret_cast<float*>(p.scratch) + 2 * blockIdx.x;
+    float* rec = reinterpret_cast<float*>(scratch) + 2 * blockIdx.x;
     rec[0] = bv;
     reinterpret_cast<int*>(rec)[1] = bi;
   }
 }
 
+// One wave folds a row's chunk records and advances the sequence's state {pos, n_out, done, token}, whose fields lie ST words apart (1: the
+// single op's int32[4]; MTX_SLOTS_MAX: one lane of the slot block).  The body of greedy_final_kernel and of its slot-batched twin, stamped
+// into each (a macro, so that the single kernel stays the code it was): `p` = the kernel's args, SCRATCH / STATE / OUT = this row's record
+// run, state and output row, ALSO = what else advances with pos.
+#define GP_FINAL_BODY(ST, SCRATCH, STATE, OUT, ALSO)                                                                   \
+  const int lane = threadIdx.x;                                                                                        \
+  float bv = -INFINITY;                                                                                                \
+  int bi = INT_MAX;                                                                                                    \
+  for (int c = lane; c < chunks; c += 64) {                                                                            \
+    const float* rec = reinterpret_cast<const float*>(SCRATCH) + 2 * c;                                                \
+    gp_take(bv, bi, rec[0], reinterpret_cast<const int*>(rec)[1]);                                                     \
+  }                                                                                                                    \
+  gp_wave(bv, bi);                                                                                                     \
+  if (lane != 0) return;                                                                                               \
+  int* st = STATE;                           /* {pos, n_out, done, token} */                                           \
+  if (st[2 * ST]) return;                    /* a finished sequence changes nothing */                                 \
+  int n_out = st[1 * ST];                                                                                              \
+  if (n_out < 0 || n_out >= p.max_new) { st[2 * ST] = 1; return; }      /* (a damaged state must not leave `out`) */    \
+  const int t = bi == INT_MAX ? 0 : bi;      /* all NaN */                                                             \
+  (OUT)[n_out++] = t;                                                                                                  \
+  int done = n_out == p.max_new;                                                                                       \
+  for (int e = 0; e < p.n_eos; ++e) done |= t == p.eos[e];                                                             \
+  st[0] += p.advance;                                                                                                  \
+  st[1 * ST] = n_out;                                                                                                  \
+  st[2 * ST] = done;                                                                                                   \
+  st[3 * ST] = t;                                                                                                      \
+  ALSO
+
+__global__ __launch_bounds__(256) void greedy_chunk_kernel(mtx_greedy_args p) {
+  gp_chunk(p.logits, p.vocab, p.scratch);
+}
+
 __global__ __launch_bounds__(64) void greedy_final_kernel(mtx_greedy_args p, int chunks) {
-  const int lane = threadIdx.x;
-  float bv = -INFINITY;
-  int bi = INT_MAX;
-  for (int c = lane; c < chunks; c += 64) {
-    const float* rec = reinterpret_cast<const float*>(p.scratch) + 2 * c;
-    gp_take(bv, bi, rec[0], reinterpret_cast<const int*>(rec)[1]);
-  }
-  gp_wave(bv, bi);
-  if (lane != 0) return;
-  int* st = p.state;                         // {pos, n_out, done, token}
-  if (st[2]) return;                         // a finished sequence changes nothing
-  int n_out = st[1];
-  if (n_out < 0 || n_out >= p.max_new) { st[2] = 1; return; }      // (a damaged state must not leave `out`)
-  const int t = bi == INT_MAX ? 0 : bi;      // all NaN
-  p.out[n_out++] = t;
-  int done = n_out == p.max_new;
-  for (int e = 0; e < p.n_eos; ++e) done |= t == p.eos[e];
-  st[0] += p.advance;
-  st[1] = n_out;
-  st[2] = done;
-  st[3] = t;
+  GP_FINAL_BODY(1, p.scratch, p.state, p.out, ;)
 }
 
 int greedy_launch(const mtx_greedy_args* a, void* stream, const char** err) {
@@ -423,6 +321,90 @@ int greedy_launch(const mtx_greedy_args* a, void* stream, const char** err) {
   const int chunks = (int)(((long)a->vocab + MTX_GREEDY_CHUNK - 1) / MTX_GREEDY_CHUNK);
   MTX_LAUNCH(greedy_chunk_kernel, dim3((unsigned)chunks), dim3(256), 0, stream, *a);
   MTX_LAUNCH(greedy_final_kernel, dim3(1), dim3(64), 0, stream, *a, chunks);
+  return MTX_OK;
+}
+
+// ---- the slot-batched step (MTX_OP_CAUSAL_STEP_BATCH, MTX_OP_GREEDY_BATCH) -----------------------------------------------------------------
+// the same step for `slots` sequences: grid (splits, kv heads, slots * nz), nz = gfull / G chunks of query heads; slot s owns cache s,
+// row s of qkv and o, and region s of the workspace (its own counters and records), so the slots never meet
+template <typename T, int G>
+__global__ __launch_bounds__(256) void causal_step_batch_kernel(mtx_causal_step_batch_args b, int gfull, int nz) {
+  const int slot = (int)blockIdx.z / nz, zc = (int)blockIdx.z - slot * nz;
+  if (b.state[MTX_SLOT_DONE * MTX_SLOTS_MAX + slot] != 0) return;      // (workgroup-uniform, before any barrier or ticket) a finished or empty slot sits out
+  mtx_causal_attn_args p;
+  p.qkv = reinterpret_cast<const T*>(b.qkv) + (long)slot * b.ld_qkv;
+  p.k_cache = reinterpret_cast<T*>(b.k_cache) + (long)slot * b.cache_stride;
+  p.v_cache = reinterpret_cast<T*>(b.v_cache) + (long)slot * b.cache_stride;
+  p.pos = b.state + MTX_SLOT_POS * MTX_SLOTS_MAX + slot;               // the body reads it and leaves (as uniformly) unless 0 <= pos < max_len
+  p.o = reinterpret_cast<T*>(b.o) + (long)slot * b.ld_o;
+  p.rows = 1; p.heads = b.heads; p.kv_heads = b.kv_heads; p.d = b.d; p.max_len = b.max_len;
+  p.ld_qkv = b.ld_qkv; p.ld_o = b.ld_o;
+  p.scale = b.scale; p.dtype = b.dtype;
+  p.workspace = reinterpret_cast<unsigned char*>(b.workspace) + (long)slot * (long)MTX_CAUSAL_WS_BYTES(b.heads, b.max_len);
+  p.workspace_bytes = (int64_t)MTX_CAUSAL_WS_BYTES(b.heads, b.max_len);
+#define CA_STEP_Z zc
+#define CA_STEP_Z_IS_0 zc == 0
+#define CA_STEP_NZ nz
+#include "causal_step_body.inc"
+#undef CA_STEP_Z
+#undef CA_STEP_Z_IS_0
+#undef CA_STEP_NZ
+}
+
+int causal_step_batch_launch(const mtx_causal_step_batch_args* a, void* stream, const char** err) {
+  if (!a->qkv || !a->k_cache || !a->v_cache || !a->state || !a->o) { *err = "causal_step_batch: null operand"; return MTX_ERR_INVALID; }
+  if (a->slots < 1 || a->slots > MTX_SLOTS_MAX) { *err = "causal_step_batch: needs 1 <= slots <= MTX_SLOTS_MAX"; return MTX_ERR_INVALID; }
+  if (a->d != CA_D) { *err = "causal_step_batch: only head width 128 is built"; return MTX_ERR_UNSUPPORTED; }
+  if (a->heads < 1 || a->kv_heads < 1 || a->heads % a->kv_heads) { *err = "causal_step_batch: heads must be a multiple of kv_heads"; return MTX_ERR_UNSUPPORTED; }
+  if (a->heads > 65535 || a->max_len < 1) { *err = "causal_step_batch: needs max_len >= 1, heads <= 65535"; return MTX_ERR_INVALID; }
+  const long qkv_w = ((long)a->heads + 2L * a->kv_heads) * CA_D;
+  if (a->ld_qkv % 8 || a->ld_o % 8 || a->ld_qkv < qkv_w || a->ld_o < (long)a->heads * CA_D) { *err = "causal_step_batch: row strides must be multiples of 8 and cover the row"; return MTX_ERR_INVALID; }
+  if (a->cache_stride % 8 || a->cache_stride < (long)a->max_len * a->kv_heads * CA_D) { *err = "causal_step_batch: cache_stride must be a multiple of 8 and cover one cache"; return MTX_ERR_INVALID; }
+  if ((((size_t)a->qkv | (size_t)a->k_cache | (size_t)a->v_cache | (size_t)a->o) & 15) != 0) { *err = "causal_step_batch: operands must be 16-byte aligned"; return MTX_ERR_INVALID; }
+  if (a->dtype != MTX_BF16 && a->dtype != MTX_F16) { *err = "causal_step_batch: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (!a->workspace || ((size_t)a->workspace & 15) || a->workspace_bytes < (int64_t)a->slots * (int64_t)MTX_CAUSAL_WS_BYTES(a->heads, a->max_len)) {
+    *err = "causal_step_batch: needs a zeroed workspace of slots * MTX_CAUSAL_WS_BYTES(heads, max_len)"; return MTX_ERR_INVALID;
+  }
+  const int gfull = a->heads / a->kv_heads;
+  const int g = gfull % 8 == 0 ? 8 : (gfull % 4 == 0 ? 4 : (gfull % 2 == 0 ? 2 : 1));      // as the single step: the same instantiation per head layout
+  const int nz = gfull / g;
+  const dim3 grid((unsigned)((a->max_len + CA_S - 1) / CA_S), (unsigned)a->kv_heads, (unsigned)(nz * a->slots));
+  if (grid.y > 65535u || grid.z > 65535u) { *err = "causal_step_batch: too many heads"; return MTX_ERR_INVALID; }
+  with_storage_type(a->dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if (g == 8) MTX_LAUNCH((causal_step_batch_kernel<T, 8>), grid, dim3(256), 0, stream, *a, gfull, nz);
+    else if (g == 4) MTX_LAUNCH((causal_step_batch_kernel<T, 4>), grid, dim3(256), 0, stream, *a, gfull, nz);
+    else if (g == 2) MTX_LAUNCH((causal_step_batch_kernel<T, 2>), grid, dim3(256), 0, stream, *a, gfull, nz);
+    else MTX_LAUNCH((causal_step_batch_kernel<T, 1>), grid, dim3(256), 0, stream, *a, gfull, nz);
+  });
+  return MTX_OK;
+}
+
+// grid (chunks, slots): row blockIdx.y of the logits, its own run of `chunks` records.  (LANES = MTX_SLOTS_MAX; templates so that the
+// module emits the two after every kernel it held before)
+template <int LANES>
+__global__ __launch_bounds__(256) void greedy_chunk_batch_kernel(mtx_greedy_batch_args p, int chunks) {
+  const int slot = blockIdx.y;
+  gp_chunk(p.logits + (long)slot * p.ld_logits, p.vocab, reinterpret_cast<float*>(p.scratch) + 2L * slot * chunks);
+}
+
+// grid (slots): one wave per slot
+template <int LANES>
+__global__ __launch_bounds__(64) void greedy_final_batch_kernel(mtx_greedy_batch_args p, int chunks) {
+  const int slot = blockIdx.x;
+  GP_FINAL_BODY(LANES, reinterpret_cast<const float*>(p.scratch) + 2L * slot * chunks, p.state + slot, p.out + (long)slot * p.max_new,
+                st[MTX_SLOT_ROPE * LANES] += p.advance;)
+}
+
+int greedy_batch_launch(const mtx_greedy_batch_args* a, void* stream, const char** err) {
+  if (!a->logits || !a->state || !a->out || !a->scratch) { *err = "greedy_pick_batch: null operand"; return MTX_ERR_INVALID; }
+  if (a->slots < 1 || a->slots > MTX_SLOTS_MAX) { *err = "greedy_pick_batch: needs 1 <= slots <= MTX_SLOTS_MAX"; return MTX_ERR_INVALID; }
+  if (a->vocab < 1 || a->max_new < 1 || a->n_eos < 0 || a->n_eos > 4 || a->ld_logits < a->vocab) {
+    *err = "greedy_pick_batch: needs vocab >= 1, max_new >= 1, 0 <= n_eos <= 4, ld_logits >= vocab"; return MTX_ERR_INVALID;
+  }
+  const int chunks = (int)(((long)a->vocab + MTX_GREEDY_CHUNK - 1) / MTX_GREEDY_CHUNK);
+  MTX_LAUNCH(greedy_chunk_batch_kernel<MTX_SLOTS_MAX>, dim3((unsigned)chunks, (unsigned)a->slots), dim3(256), 0, stream, *a, chunks);
+  MTX_LAUNCH(greedy_final_batch_kernel<MTX_SLOTS_MAX>, dim3((unsigned)a->slots), dim3(64), 0, stream, *a, chunks);
   return MTX_OK;
 }
 

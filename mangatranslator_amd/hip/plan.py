@@ -442,6 +442,41 @@ class PlanBuilder:
         self._add(abi.OP_GREEDY, a, label)
         return state
 
+    def causal_step_batch(self, qkv, k_cache, v_cache, state, o, slots, heads, kv_heads, d, max_len, scale, cache_stride=None, ld_qkv=None,
+                          ld_o=None, workspace=None, label="causal_step_batch"):
+        """MTX_OP_CAUSAL_STEP_BATCH: the rows == 1 step of `causal_attention` for `slots` sequences in one launch.  qkv [slots, ld_qkv],
+        o [slots, ld_o], caches [slots, max_len, kv_heads * d] (slot stride `cache_stride` elements); `state` is the int32
+        [SLOT_FIELDS, SLOTS_MAX] block: a slot with done != 0 or pos outside [0, max_len) sits out.  One zeroed workspace of
+        slots * causal_ws_bytes, made here unless one is passed (layers of one plan may share it: they run in order)"""
+        assert state.dtype == torch.int32 and state.numel() >= abi.SLOT_FIELDS * abi.SLOTS_MAX and state.is_contiguous()
+        a = abi.CausalStepBatchArgs()
+        a.qkv, a.k_cache, a.v_cache, a.state, a.o = _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(state), _ptr(o)
+        a.slots, a.heads, a.kv_heads, a.d, a.max_len = slots, heads, kv_heads, d, max_len
+        a.ld_qkv, a.ld_o = (ld_qkv or (heads + 2 * kv_heads) * d), (ld_o or heads * d)
+        a.cache_stride = cache_stride if cache_stride is not None else max_len * kv_heads * d
+        a.scale, a.dtype = scale, self.dtype
+        need = max(slots, 0) * abi.causal_ws_bytes(heads, max_len)
+        if workspace is None:
+            workspace = self.buf((max(need, 16),), torch.uint8, zero=True)
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        self._add(abi.OP_CAUSAL_STEP_BATCH, a, label)
+        return o
+
+    def greedy_pick_batch(self, logits, state, out, slots, vocab, max_new, eos=(), advance=1, ld_logits=None, label="greedy_pick_batch"):
+        """MTX_OP_GREEDY_BATCH: `greedy_pick` for `slots` rows of fp32 `logits` [slots, ld_logits] into `out` [slots, max_new] on the int32
+        [SLOT_FIELDS, SLOTS_MAX] state block; a slot that advances also moves its rotary row by `advance`"""
+        eos = [int(e) for e in eos]
+        assert len(eos) <= 4 and logits.dtype == torch.float32 and state.dtype == torch.int32 and out.dtype == torch.int32
+        a = abi.GreedyBatchArgs()
+        scratch = self.buf((max(max(slots, 1) * abi.greedy_scratch_bytes(max(vocab, 1)), 8),), torch.uint8)
+        a.logits, a.state, a.out, a.scratch = _ptr(logits), _ptr(state), _ptr(out), scratch.data_ptr()
+        a.ld_logits = ld_logits if ld_logits is not None else vocab
+        a.slots, a.vocab, a.max_new, a.n_eos, a.advance = slots, vocab, max_new, len(eos), advance
+        for i, e in enumerate(eos):
+            a.eos[i] = e
+        self._add(abi.OP_GREEDY_BATCH, a, label)
+        return state
+
     def row_linear(self, a_t, w_t, rows, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE, res=None, ldres=None,
                    alpha=1.0, out_f32=False, label="rowlin"):
         """MTX_OP_ROWLIN: the skinny-row (rows <= 8) linear of a decode step, same epilogue and rounding contract as `gemm`"""

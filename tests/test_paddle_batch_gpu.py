@@ -1,0 +1,75 @@
+"""GPU tier of the slot-batched PaddleOCR-VL decode step: MTX_OP_CAUSAL_STEP_BATCH, MTX_OP_GREEDY_BATCH and `generate_many` on the product
+library (checks in paddle_batch_checks.py)."""
+import pytest
+
+import paddle_batch_checks as bc
+from mangatranslator_amd.hip import abi
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = [abi.BF16, abi.F16]
+
+
+def test_new_ops_are_additive_to_abi_12(hip_lib):
+    assert abi.ABI_VERSION == 12 and hip_lib.mtx_abi_version() == 12
+    assert hip_lib.mtx_abi_sizeof(22) > 0 and hip_lib.mtx_abi_sizeof(23) > 0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", bc.HEADS)
+@pytest.mark.parametrize("slots", [1, 2, 3, 8])
+def test_batched_step_equals_the_single_step(hip_lib, dtype, heads, kv, slots):
+    bc.check_batch_equals_single(hip_lib, dtype, heads, kv, slots)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", bc.HEADS)
+def test_slots_that_sit_out(hip_lib, dtype, heads, kv):
+    bc.check_sitting_out(hip_lib, dtype, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", bc.HEADS)
+def test_batched_step_selects_exactly_per_slot(hip_lib, dtype, heads, kv):
+    bc.check_batch_selection(hip_lib, dtype, heads, kv)
+
+
+@pytest.mark.parametrize("vocab", bc.BATCH_VOCABS)
+@pytest.mark.parametrize("slots", [1, 3, 8])
+def test_greedy_batch_equals_the_single_pick(hip_lib, vocab, slots):
+    for shift in (range(len(bc.ROLES)) if slots == 1 else (0, 3)):
+        bc.check_greedy_batch(hip_lib, vocab, slots, shift)
+
+
+def test_greedy_batch_damaged_state(hip_lib):
+    bc.check_greedy_batch_damaged_state(hip_lib)
+
+
+def test_greedy_batch_run_of_steps(hip_lib):
+    bc.check_greedy_batch_run(hip_lib)
+
+
+def test_batched_ops_refuse_bad_arguments(hip_lib):
+    bc.check_batch_refusals(hip_lib)
+
+
+@pytest.mark.parametrize("check_every", [1, 8])
+def test_generate_many_equals_generate(hip_lib, check_every):
+    lens = bc.check_generate_many_equals_generate(hip_lib, check_every)
+    print(f"generated lengths {lens}")
+
+
+def test_generate_many_other_slot_counts(hip_lib):
+    bc.check_other_slot_counts(hip_lib)
+
+
+def test_generate_many_refused_items(hip_lib):
+    bc.check_refused_items(hip_lib)
+
+
+def test_driver_reads_a_page_together(hip_lib, tmp_path, monkeypatch):
+    bc.check_driver(hip_lib, tmp_path, monkeypatch)
+
+
+def test_generate_many_at_the_published_widths(hip_lib):
+    bc.check_published_widths(hip_lib)

@@ -464,11 +464,60 @@ def paddleocr(reps=3, iters=20):
             print(f"  step graph, linears on {k}, cache {cache}: {best:.4f} ms per step = {1e3 / best:.0f} tokens/s ({step.n_ops} launches)", flush=True)
 
 
+def paddleocr_batch(reps=3, windows=4, iters=60):
+    """the slot-batched step graph (`PaddleOcrVlHip(slots=B)._stepper_batch()`) at B = 1, 2, 4, 8 beside the single-sequence step graph, same
+    widths as `paddleocr`, caches of 300 and 2 300 positions.  Finished slots skip attention, so nothing is timed at done = 1: every window is a
+    run of `iters` LIVE steps from the same start position, the state reset before it; a repetition is the mean of `windows` windows, the graphs
+    alternate inside a repetition, the figure is the best repetition and the spread (max - min over the repetitions) is printed beside it."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import paddle_ocr_vl_checks as pc
+    kw = dict(real=True, max_new_tokens=1024, max_prompt=1344)
+    single = pc.hip_model(lib, abi.F16, 0, **kw)
+    batched = {}
+    for B in (1, 2, 4, 8):
+        batched[B] = pc.hip_model(lib, abi.F16, 0, slots=max(B, 2), **kw)
+        batched[B].slots = B                                       # (B = 1: the batched plan on one row of a two-slot model's buffers)
+
+    def reset(m, B, cache):
+        if B == 0:
+            m.state.copy_(torch.tensor([cache, 0, 0, 5], dtype=torch.int32))
+            return
+        st = torch.zeros(abi.SLOT_FIELDS, abi.SLOTS_MAX, dtype=torch.int32)
+        st[abi.SLOT_DONE] = 1
+        st[abi.SLOT_POS, :B], st[abi.SLOT_DONE, :B], st[abi.SLOT_ROPE, :B] = cache, 0, cache
+        st[abi.SLOT_TOKEN, :B] = 5 + torch.arange(B, dtype=torch.int32)
+        m.slot_state.copy_(st)
+
+    plans = {0: (single, single._stepper())}
+    plans.update({B: (m, m._stepper_batch()) for B, m in batched.items()})
+    for cache in (300, 2300):
+        assert cache + iters < single.max_len
+        for B, (m, plan) in plans.items():                         # warm every graph at this start position
+            reset(m, B, cache)
+            for _ in range(3):
+                plan.run(graph=True)
+            torch.cuda.synchronize()
+        runs = {B: [] for B in plans}
+        for _ in range(reps):
+            for B, (m, plan) in plans.items():
+                ms = []
+                for _ in range(windows):
+                    reset(m, B, cache); torch.cuda.synchronize()
+                    ms.append(plan.time(iters, graph=True))
+                runs[B].append(sum(ms) / len(ms))
+        base = min(runs[0])
+        for B, (m, plan) in plans.items():
+            best, spread, n = min(runs[B]), max(runs[B]) - min(runs[B]), max(B, 1)
+            name = "single step graph" if B == 0 else f"batched step graph B = {B}"
+            print(f"  {name}, cache {cache}: {best:.4f} ms per step (spread {spread:.4f} over {reps} repetitions) = {n * 1e3 / best:.0f} tokens/s aggregate, "
+                  f"{n * base / best:.2f} x the single step ({plan.n_ops} launches)", flush=True)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
         if args[0] == "paddleocr":
-            paddleocr(); args = args[1:]
+            paddleocr(); paddleocr_batch(); args = args[1:]
             continue
         if args[0] == "mangaocr":                     # mangaocr [DEC_LAYERS]
             n = int(args[1]) if len(args) > 1 and args[1].isdigit() else 2

@@ -6,7 +6,8 @@ sharing code between them has changed register allocation and instruction order 
 
 A and B are csrc directories or git revisions (extracted with `git archive` into a temporary directory).  Before the comparison comment
 lines and the .file / .loc / .ident directives are dropped; the text is cut at every `_Z...:` symbol (a kernel's piece holds its code, its
-descriptor and its resource figures) and ends at the module's tail (the compilation-unit id, a hash of the file's path, and the metadata).
+descriptor and its resource figures, not the preamble of the function emitted after it, so a kernel added behind it does not show) and
+ends at the module's tail (the end-of-code padding, the compilation-unit id, a hash of the file's path, and the metadata).
 Prints `same` or `DIFF` with both line counts per symbol.
 Exit status 1 if a symbol outside --allow differs or the two trees do not define the same symbols."""
 import argparse
@@ -51,6 +52,13 @@ def symbols(asm: Path):
             continue
         if "__hip_cuid_" in t or t.startswith(".amdgpu_metadata"):
             break
+        if t.startswith(".p2alignl"):                          # the padding behind the module's last function: the tail starts here
+            if cur and cur[-1] == ".text":
+                cur.pop()
+            break
+        if re.match(r"\.section\s+\.text\.", t):               # the next function's preamble (section, visibility, alignment, type) names
+            cur = None                                         # THAT function: it is no part of the piece before it
+            continue
         m = re.match(r"^(_Z\w+):", line)
         if m:
             cur = out.setdefault(m.group(1), [])

@@ -640,12 +640,94 @@ typedef struct mtx_greedy_batch_args {
   int32_t eos[4];
 } mtx_greedy_batch_args;
 
+/* ---- ABI 12, additive: manga-ocr's decode step for S crops ("groups") of B beams in one launch, with the beam search on the device
+ * (csrc/decode.hip, csrc/beam.hip).  rows = S * B <= MTX_WIDE_ROWS_MAX; row g * B + b is beam b of group g.
+ *
+ * MTX_OP_ROWLIN_WIDE (mtx_row_linear_wide): mtx_row_linear's arguments, epilogue and rounding contract for 1 <= rows <= 32.  A wave owns a few
+ * output columns for ALL rows, so every weight byte is read once per launch whatever `rows` is; every output runs the single op's
+ * arithmetic (16-byte K chunks, lane-strided, eight sequential multiply-adds per chunk, then the wave sum), so row r of the result is, bit
+ * for bit, what mtx_row_linear gives for that row alone.  Refusals as the single op's, with 32 in place of 8. */
+#define MTX_WIDE_ROWS_MAX 32
+
+/* The group state block: DEVICE int32 [groups][state_stride], state_stride >= MTX_BEAM_STATE_WORDS(beams, max_len); fp32 fields are stored
+ * in the same words.  Per group, with B = beams and L = max_len:
+ *   [MTX_BEAM_POS]      pos: positions already cached = length of the running sequences - 1
+ *   [MTX_BEAM_DONE]     0 = searching, 1 = finished (the hypothesis is in `out`), 2 = failed (a logits row held no finite value, or pos
+ *                       left the range 0 <= pos, pos + 2 <= min(max_len, max_length)); an empty slot holds 1
+ *   [MTX_BEAM_UNSAT]    beam_search's `unsatisfied`
+ *   [MTX_BEAM_OUT_LEN]  length of the chosen hypothesis
+ *   [MTX_BEAM_RSCORE .. + 8)   fp32 running scores          [MTX_BEAM_FSCORE .. + 8)   fp32 scores of the finished hypotheses
+ *   [MTX_BEAM_FDONE .. + 8)    their done flags             [MTX_BEAM_FLEN .. + 8)     their lengths
+ *   [MTX_BEAM_PARENT .. + 8)   the parents chosen by the last iteration (written, never read)
+ *   [MTX_BEAM_OUT .. + L)      the chosen hypothesis, start token included
+ *   then running [B][L], finished [B][L], a staging area [B][L] of the op's own, and the ancestry table src [L][B]
+ *   (MTX_BEAM_RUNNING / _FIN / _SRC give the word offsets). */
+#define MTX_BEAM_MAX 8
+#define MTX_BEAM_POS 0
+#define MTX_BEAM_DONE 1
+#define MTX_BEAM_UNSAT 2
+#define MTX_BEAM_OUT_LEN 3
+#define MTX_BEAM_RSCORE 8
+#define MTX_BEAM_FSCORE 16
+#define MTX_BEAM_FDONE 24
+#define MTX_BEAM_FLEN 32
+#define MTX_BEAM_PARENT 40
+#define MTX_BEAM_OUT 48
+#define MTX_BEAM_RUNNING(B, L) (MTX_BEAM_OUT + (int64_t)(L))
+#define MTX_BEAM_FIN(B, L) (MTX_BEAM_RUNNING(B, L) + (int64_t)(B) * (L))
+#define MTX_BEAM_STAGE(B, L) (MTX_BEAM_FIN(B, L) + (int64_t)(B) * (L))
+#define MTX_BEAM_SRC(B, L) (MTX_BEAM_STAGE(B, L) + (int64_t)(B) * (L))
+#define MTX_BEAM_STATE_WORDS(B, L) (MTX_BEAM_SRC(B, L) + (int64_t)(B) * (L))
+
+/* MTX_OP_DECODE_ATTN_BATCH (mtx_decode_attention_batch): mtx_decode_attention for `groups` groups, each at its own position.  qkv
+ * [groups * beams][ld_qkv], o [groups * beams][ld_o]; group g owns the caches k_cache + g * cache_stride, v_cache + g * cache_stride
+ * ([max_len][beams][heads * d], stride in elements, a multiple of 8) and the table src + g * src_stride (int32 [max_len][beams]), and reads
+ * pos and done from state + g * state_stride.  Group g takes part iff done == 0 and 0 <= pos < max_len; it then gets, bit for bit, the o rows
+ * and cache rows mtx_decode_attention(rows = slots = beams) produces on its operands alone (the kernels share one body).  A group that does
+ * not take part reads and writes nothing of its cache or its o rows.  Limits of the single op (d == 64, alignment, bf16 / f16 / f32);
+ * groups outside 1 .. MTX_SLOTS_MAX or beams outside 1 .. MTX_BEAM_MAX: MTX_ERR_INVALID. */
+typedef struct mtx_decode_attn_batch_args {
+  const void* qkv; void* k_cache; void* v_cache; const int32_t* state; const int32_t* src; void* o;
+  int32_t groups, beams, heads, d, max_len;
+  int64_t ld_qkv, ld_o, cache_stride, src_stride, state_stride;
+  float scale; int32_t dtype;
+} mtx_decode_attn_batch_args;
+
+/* MTX_OP_BEAM_STEP (mtx_beam_step): for every group with done == 0, exactly ONE iteration of transformers' beam search as
+ * core/ml/manga_ocr.py `beam_search` restates it, in the same fp32 operations in the same order, on fp32 logits [groups * beams][ld_logits]:
+ * log_softmax per row ((x - max) - log(sum exp(x - max))), the no-repeat-n-gram ban from the running sequences, + running score, the top
+ * keep = max(2, 1 + n_eos) * beams of the beams * vocab candidates, `hits`, the masked second top-beams, the merge into the finished set,
+ * `unsatisfied` and the go_on rule with early = 0 (False), 1 (True) or 2 ("never"); -1.0e9 enters as an fp32 addend as there.  The length
+ * penalty divisors come from len_pow[j - 1] = float32(float(j) ** length_penalty), j = 1 .. max_len, uploaded by the host (no powf on the
+ * device); lp_positive = (length_penalty > 0).  A caller with one beam passes early = 1, as beam_search does.
+ * After the iteration: tok_idx[g * B + r] / pos_idx[g * B + r] = the next token and position of every row (the index vectors of the step's
+ * two embedding gathers, int32 [groups * beams] each); the running sequences reordered by parent and extended; src'[j][r] = src[j][parent[r]]
+ * for j <= pos with src[pos][r] counting as r (in place: one thread owns a position's B entries; entries outside 0 .. B - 1 are clamped);
+ * pos += 1; when the search ends: done = 1, out = finished[0] with its length.  done != 0 changes nothing for that group.
+ * SELECTION RULE of all three selections: the larger value first; among equal values the lower position in the list selected from (for the
+ * first selection the flat index beam * vocab + token; for the second the rank in the first; for the merge, finished entries before
+ * candidates).  A NaN logit counts as -inf.  A row whose maximum is not finite ends the group with done = 2.
+ * A group's result is independent of `groups` and of the slot it sits in; identical inputs give identical bytes (fixed merge order, no
+ * floating-point atomics).  Refused: groups outside 1 .. MTX_SLOTS_MAX, beams outside 1 .. MTX_BEAM_MAX, n_eos outside 1 .. 4, vocab < 2 or
+ * beams * vocab < keep, max_length outside 2 .. max_len, early outside 0 .. 2, ld_logits < vocab, a short state_stride.
+ * scratch: MTX_BEAM_SCRATCH_BYTES(groups * beams, vocab, keep) bytes. */
+#define MTX_BEAM_CHUNK 512         /* logits per wave of the candidate pass */
+#define MTX_BEAM_SCRATCH_BYTES(rows, vocab, keep) \
+  ((int64_t)(rows) * 8 + (int64_t)(rows) * (((int64_t)(vocab) + MTX_BEAM_CHUNK - 1) / MTX_BEAM_CHUNK) * (keep) * 8)
+typedef struct mtx_beam_step_args {
+  const float* logits; int32_t* state; int32_t* tok_idx; int32_t* pos_idx; const float* len_pow; void* scratch;
+  int64_t ld_logits, state_stride;
+  int32_t groups, beams, vocab, max_len, max_length, n_eos, ngram, early, lp_positive;
+  int32_t eos[4];
+} mtx_beam_step_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
   MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17,
   MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19, MTX_OP_CAUSAL_ATTN = 20, MTX_OP_GREEDY = 21,
-  MTX_OP_CAUSAL_STEP_BATCH = 22, MTX_OP_GREEDY_BATCH = 23
+  MTX_OP_CAUSAL_STEP_BATCH = 22, MTX_OP_GREEDY_BATCH = 23,
+  MTX_OP_ROWLIN_WIDE = 24, MTX_OP_DECODE_ATTN_BATCH = 25, MTX_OP_BEAM_STEP = 26
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -664,6 +746,7 @@ typedef struct mtx_op {
     mtx_resize_thresh_args rt; mtx_memset_args ms; mtx_mask_select_args sel; mtx_preproc_args pre; mtx_yolo_decode_args yd; mtx_detr_args detr; mtx_quant_args quant; mtx_tail_args tail; mtx_textcolor_args tc;
     mtx_decode_attn_args dattn; mtx_rowlin_args rowlin; mtx_causal_attn_args cattn; mtx_greedy_args greedy;
     mtx_causal_step_batch_args cstepb; mtx_greedy_batch_args greedyb;
+    mtx_decode_attn_batch_args dattnb; mtx_beam_step_args beam;      /* MTX_OP_ROWLIN_WIDE takes `rowlin` */
   } u;
 } mtx_op;
 
@@ -702,6 +785,9 @@ MTX_API int mtx_causal_attention(const mtx_causal_attn_args* a, void* stream);
 MTX_API int mtx_greedy_pick(const mtx_greedy_args* a, void* stream);
 MTX_API int mtx_causal_step_batch(const mtx_causal_step_batch_args* a, void* stream);
 MTX_API int mtx_greedy_pick_batch(const mtx_greedy_batch_args* a, void* stream);
+MTX_API int mtx_row_linear_wide(const mtx_rowlin_args* a, void* stream);
+MTX_API int mtx_decode_attention_batch(const mtx_decode_attn_batch_args* a, void* stream);
+MTX_API int mtx_beam_step(const mtx_beam_step_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

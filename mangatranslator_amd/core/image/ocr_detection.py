@@ -372,7 +372,40 @@ def _run_recogniser(images, what: str, get_recogniser, read_one, verbose: bool) 
 
 
 def extract_text_with_manga_ocr(images: List[Image.Image], verbose: bool = False) -> List[str]:
-    return _run_recogniser(images, "manga-ocr", lambda: get_model_manager().get_manga_ocr(verbose=verbose), lambda ocr, img: ocr(img), verbose)
+    """One crop at a time through the recogniser's `__call__`, as the reference — or, when the recogniser reads several crops together
+    (`recognise_many` and `slots` > 1: `ModelManager.manga_ocr_slots`) and the list holds two or more readable images, all of them through ONE
+    `recognise_many` call.  Order, markers and stripping are the same on both paths; a recogniser object without `recognise_many` is used
+    exactly as before.  If the joint call itself fails, the per-image loop serves the page."""
+    what = "manga-ocr"
+
+    def get_ocr():
+        return get_model_manager().get_manga_ocr(verbose=verbose)
+
+    readable = [i for i, img in enumerate(images or []) if img is not None]
+    if len(readable) >= 2:
+        try:
+            ocr = get_ocr()
+            if callable(getattr(ocr, "recognise_many", None)) and int(getattr(ocr, "slots", 1) or 1) > 1:
+                log_message(f"Processing {len(readable)} images together with {what}", verbose=verbose)
+                results = ocr.recognise_many([images[i] for i in readable])
+                if len(results) != len(readable):
+                    raise ModelError(f"recognise_many returned {len(results)} results for {len(readable)} images")
+                texts = []
+                for i, img in enumerate(images):
+                    if img is None:
+                        log_message(f"Image {i + 1} is None (decode failure), skipping", always_print=True)
+                        texts.append(OCR_FAILED)
+                        continue
+                    out = results[readable.index(i)]
+                    if isinstance(out, Exception) or not isinstance(out, str):
+                        log_message(f"{what} failed for image {i + 1}: {out}", always_print=True)
+                        texts.append(OCR_FAILED)
+                    else:
+                        texts.append(out.strip() if out else "")
+                return texts
+        except Exception as e:                                   # one bad batch must not cost the page its text
+            log_message(f"{what} failed on the batch ({e}); reading the images one by one", always_print=True)
+    return _run_recogniser(images, what, get_ocr, lambda ocr, img: ocr(img), verbose)
 
 
 def extract_text_with_paddle_ocr_vl(images: List[Image.Image], verbose: bool = False) -> List[str]:

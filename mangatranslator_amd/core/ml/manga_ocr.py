@@ -45,6 +45,10 @@ from . import packing, vit_common
 
 MAX_BEAMS = abi.DECODE_MAX_ROWS
 HEAD_DIM = 64
+MAX_BATCH_ROWS = abi.WIDE_ROWS_MAX
+# crops `ModelManager.get_manga_ocr()` reads together unless `manga_ocr_slots` says otherwise: decided by the page measurement of
+# tools/bench_kernels.py mangaocr_batch (docs/experiments.md, "manga-ocr: a page's crops together")
+DEFAULT_SLOTS = 8
 
 
 # ---- generation settings and the host-side search ----------------------------------------------------------------------------------------------
@@ -361,9 +365,11 @@ def linear_route(rows: int, n: int, k: int) -> str:
 
 class MangaOcrHip:
     def __init__(self, state_dict: dict, hp: dict, vocab: Sequence[str], device="cuda", lib=None, dtype: int = abi.F16, graph: bool = True,
-                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rows: Optional[int] = None, route: Optional[Callable[[int, int, int], str]] = None):
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rows: Optional[int] = None, route: Optional[Callable[[int, int, int], str]] = None,
+                 slots: int = 1):
         """hp: `hparams_from_config`; state_dict: `normalise_state_dict`'s names.  Storage is f16 by default, like the detectors; abi.BF16 is
-        selectable.  rows: rows of the step graph (default: num_beams).  route: overrides `linear_route` (benchmarks)."""
+        selectable.  rows: rows of the step graph (default: num_beams).  route: overrides `linear_route` (benchmarks).  slots: crops that
+        `generate_many` decodes together, each with num_beams rows of ONE step graph whose search runs on the device (1: nothing new is built)."""
         if dtype not in (abi.BF16, abi.F16, abi.F32):
             raise ModelError("manga-ocr: storage dtype must be bf16, f16 or f32")
         self.lib = lib if lib is not None else get_library()
@@ -375,6 +381,13 @@ class MangaOcrHip:
         self.rows = int(rows) if rows is not None else self.gen.num_beams
         if not 1 <= self.rows <= MAX_BEAMS:
             raise ModelError(f"manga-ocr: {self.rows} rows per step are not built (1 .. {MAX_BEAMS})")
+        self.slots = int(slots)
+        if not 1 <= self.slots <= abi.SLOTS_MAX or self.slots * self.gen.num_beams > MAX_BATCH_ROWS:
+            raise ModelError(f"manga-ocr: {self.slots} slots of {self.gen.num_beams} beams are not built (1 .. {abi.SLOTS_MAX} slots, "
+                             f"slots * num_beams <= {MAX_BATCH_ROWS})")
+        if self.slots > 1 and not 1 <= len(self.gen.eos_token_id) <= 4:
+            raise ModelError("manga-ocr: the device search takes 1 .. 4 eos_token_id")
+        self._batch = None
         self.route = route or linear_route
         self._graph = graph and not self.lib.is_simulator
         self._lock = threading.Lock()
@@ -386,6 +399,8 @@ class MangaOcrHip:
     @classmethod
     def from_directory(cls, root, **kw):
         ck = read_checkpoint(root)
+        if kw.get("slots") is None:                               # the default, lowered to what the checkpoint's beams allow
+            kw["slots"] = max(1, min(DEFAULT_SLOTS, MAX_BATCH_ROWS // ck["hp"]["gen"].num_beams))
         return cls(ck["state_dict"], ck["hp"], ck["vocab"], mean=ck["mean"], std=ck["std"], **kw)
 
     # ------------------------------------------------------------------------------------------
@@ -583,9 +598,156 @@ class MangaOcrHip:
             ids = self.generate()
         return post_process(tokens_to_text(ids, self.vocab))
 
+    # ---- a page's crops together ------------------------------------------------------------------
+    def _stepper_batch(self):
+        """ONE plan at rows = slots * num_beams: the gathers read the index vectors the search wrote, every linear runs on MTX_OP_ROWLIN_WIDE,
+        self attention on MTX_OP_DECODE_ATTN_BATCH (each group at its own position), cross attention on MTX_OP_ATTN with batch = slots over
+        per-slot K | V, and MTX_OP_BEAM_STEP ends the step: no host upload or download inside it"""
+        if self._batch is not None:
+            return self._batch
+        hp, W, gen = self.hp, self.W, self.gen
+        enc = self._encoder()
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        S, B, C, heads, d, L_max, T = self.slots, gen.num_beams, hp["d_dim"], hp["d_heads"], HEAD_DIM, self.max_len, enc.tokens
+        R, eps = S * B, hp["d_eps"]
+        words = abi.beam_state_words(B, L_max)
+        state = pb.buf((S, words), torch.int32, zero=True)
+        state[:, abi.BEAM_DONE] = 1                              # every slot starts empty
+        idx = pb.buf((2, R), torch.int32, zero=True)
+        tok_idx, pos_idx = idx[0], idx[1]
+        lp = float(gen.length_penalty)
+        len_pow = pb.hold(torch.tensor([float(j) ** lp for j in range(1, L_max + 1)], dtype=torch.float64).to(torch.float32).to(self.device))
+
+        def lin(a, wb, n, k, label, act=abi.ACT_NONE, res=None, out_f32=False):
+            return pb.row_linear_wide(a, wb[0], R, n, k, bias=wb[2], act=act, res=res, out_f32=out_f32, label=label)
+
+        def norm(t, wb, label):
+            return pb.norm(t, pb.buf((R, C), self.tdt), R, C, gamma=wb[0], beta=wb[1], eps=eps, dtype=abi.F32, out_dtype=self.dtype, label=label)
+
+        f32 = torch.float32
+        e_tok = pb.row_gather(W["tok32"], pb.buf((R, C), f32), tok_idx, R, C, label="embed.token", dtype=abi.F32)
+        e_pos = pb.row_gather(W["d_pos"], pb.buf((R, C), f32), pos_idx, R, C, label="embed.position", dtype=abi.F32)
+        e_sum = pb.ew(abi.EW_ADD, Act(e_tok.view(1, 1, R, C), 1, 1, R, C), Act(e_pos.view(1, 1, R, C), 1, 1, R, C),
+                      out=Act(pb.buf((1, 1, R, C), f32), 1, 1, R, C), label="embed.add", dtype=abi.F32).t.view(R, C)
+        x = norm(e_sum, W["d_ln"], "embed.ln")
+        caches, cross = [], []
+        for i, L in enumerate(self.d_layers):
+            tag = f"dec{i}"
+            kc, vc = pb.buf((S, L_max, B, C), self.tdt, zero=True), pb.buf((S, L_max, B, C), self.tdt, zero=True)
+            caches.append((kc, vc))
+            kv = pb.buf((S, T, 2 * C), self.tdt, zero=True)
+            cross.append(kv)
+            qkv = lin(x, L["qkv"], 3 * C, C, tag + ".qkv")
+            o = pb.decode_attention_batch(qkv, kc, vc, state, pb.buf((R, C), self.tdt), S, B, heads, d, L_max, 1.0 / math.sqrt(d),
+                                          label=tag + ".self_attn")
+            x1 = norm(lin(o, L["so"], C, C, tag + ".self_out", res=x, out_f32=True), L["sln"], tag + ".self_ln")
+            cq = lin(x1, L["cq"], C, C, tag + ".cross_q")
+            o2 = pb.buf((R, C), self.tdt)
+            pb.attention(cq, kv, kv, o2, S, heads, B, T, d, (B * C, C, d), (T * 2 * C, 2 * C, d), (T * 2 * C, 2 * C, d), (B * C, C, d), 1.0 / math.sqrt(d),
+                         v_off=C, label=tag + ".cross_attn")
+            x2 = norm(lin(o2, L["co"], C, C, tag + ".cross_out", res=x1, out_f32=True), L["cln"], tag + ".cross_ln")
+            h = lin(x2, L["fc1"], hp["d_mlp"], C, tag + ".fc1", act=abi.ACT_GELU)
+            x = norm(lin(h, L["fc2"], C, hp["d_mlp"], tag + ".fc2", res=x2, out_f32=True), L["oln"], tag + ".out_ln")
+        t = norm(lin(x, W["h_t"], C, C, "head.transform", act=abi.ACT_GELU, out_f32=True), W["h_ln"], "head.ln")
+        logits = lin(t, W["h_out"], hp["vocab"], C, "head.logits", out_f32=True)
+        early = gen.early_stopping if B > 1 else True           # one beam: greedy, as `beam_search`
+        pb.beam_step(logits, state, tok_idx, pos_idx, len_pow, S, B, hp["vocab"], L_max, max(int(gen.max_length), 2), gen.eos_token_id,
+                     ngram=int(gen.no_repeat_ngram_size), early=early, lp_positive=lp > 0.0, label="beam_step")
+        plan = pb.build()
+        plan.state, plan.idx, plan.logits, plan.caches, plan.cross, plan.words = state, idx, logits, caches, cross, words
+        plan.beam_op = len(pb.ops) - 1
+        self._batch = plan
+        return plan
+
+    def _reset_group(self, plan, s: int) -> None:
+        """slot s takes the image last encoded: its cross K | V move device to device into the slot's region (same stream as the encoder), and
+        its state becomes `beam_search`'s start: B identical rows of which only the first may seed candidates"""
+        B, L_max, gen = self.gen.num_beams, self.max_len, self.gen
+        for kv, mine in zip(plan.cross, self._encoder().cross):
+            kv[s].copy_(mine)
+        st = torch.zeros(plan.words, dtype=torch.int32)
+        stf = st.view(torch.float32)
+        start = int(gen.decoder_start_token_id)
+        st[abi.BEAM_UNSAT] = 1
+        stf[abi.BEAM_RSCORE:abi.BEAM_RSCORE + abi.BEAM_MAX] = -1e9
+        stf[abi.BEAM_RSCORE] = 0.0
+        stf[abi.BEAM_FSCORE:abi.BEAM_FSCORE + abi.BEAM_MAX] = -1e9
+        st[abi.BEAM_FLEN:abi.BEAM_FLEN + abi.BEAM_MAX] = 1
+        run, fin = abi.beam_running(B, L_max), abi.beam_fin(B, L_max)
+        st[run:run + B * L_max:L_max] = start
+        st[fin:fin + B * L_max:L_max] = start
+        plan.state[s].copy_(st)
+        plan.idx[0, s * B:(s + 1) * B] = start
+        plan.idx[1, s * B:(s + 1) * B] = 0
+
+    def generate_many(self, images, check_every: int = 4) -> list:
+        """uint8 RGB arrays [H, W, 3] -> one token list per image (start token included, as `generate`), in input order.  The slots are kept
+        full from the list: a crop is encoded into a free slot, the step graph is replayed `check_every` times, the head of the state block
+        comes down, finished groups hand over their hypothesis and the slots refill.  An image that cannot be prepared, or whose search
+        failed on the device (a logits row without a finite value), leaves a ModelError in its place and does not disturb the others.  With
+        slots == 1 the images go one by one through `encode` + `generate`."""
+        with self._lock:
+            return self._generate_many(list(images), max(1, int(check_every)))
+
+    def _generate_many(self, images, check_every):
+        n = len(images)
+        results: list = [None] * n
+        if self.slots == 1 or self.gen.max_length <= 1:
+            for i, img in enumerate(images):
+                try:
+                    self.encode(img)
+                    results[i] = self.generate()
+                except Exception as e:
+                    results[i] = e if isinstance(e, ModelError) else ModelError(f"manga-ocr: image {i}: {e}")
+            return results
+        plan, S, L_max = self._stepper_batch(), self.slots, self.max_len
+        head = abi.BEAM_OUT + L_max
+        owner: List[Optional[int]] = [None] * S
+        plan.state[:, abi.BEAM_DONE] = 1
+        nxt = 0
+        while True:
+            for s in range(S):
+                while owner[s] is None and nxt < n:
+                    i, nxt = nxt, nxt + 1
+                    try:
+                        if isinstance(images[i], Exception):
+                            raise images[i]
+                        self.encode(images[i])
+                        self._reset_group(plan, s)
+                        owner[s] = i
+                    except Exception as e:
+                        results[i] = e if isinstance(e, ModelError) else ModelError(f"manga-ocr: image {i} could not be prepared: {e}")
+            if all(o is None for o in owner):
+                return results
+            for _ in range(check_every):
+                plan.run(graph=self._graph)
+            st = plan.state[:, :head].cpu()
+            for s in range(S):
+                i = owner[s]
+                if i is None or int(st[s, abi.BEAM_DONE]) == 0:
+                    continue
+                owner[s] = None
+                n_out = int(st[s, abi.BEAM_OUT_LEN])
+                if int(st[s, abi.BEAM_DONE]) == 1 and 1 <= n_out <= L_max:
+                    results[i] = [int(t) for t in st[s, abi.BEAM_OUT:abi.BEAM_OUT + n_out]]
+                else:
+                    results[i] = ModelError(f"manga-ocr: the search of image {i} failed on the device (no finite logit, or a damaged state)")
+
+    def recognise_many(self, pil_images) -> list:
+        """PIL images -> texts, as `__call__` on each, read together through `generate_many`; an image that could not be read holds its
+        ModelError instead of a string"""
+        rgbs = []
+        for img in pil_images:
+            try:
+                rgbs.append(np.asarray(img.convert("L").convert("RGB")))
+            except Exception as e:
+                rgbs.append(ModelError(f"manga-ocr: unreadable image: {e}"))
+        ids = self.generate_many(rgbs)
+        return [r if isinstance(r, Exception) else post_process(tokens_to_text(r, self.vocab)) for r in ids]
+
     def close(self):
-        for p in [self._enc, self._step, *self._pre.values()]:
+        for p in [self._enc, self._step, self._batch, *self._pre.values()]:
             if p is not None:
                 p.close()
-        self._enc = self._step = None
+        self._enc = self._step = self._batch = None
         self._pre.clear()

@@ -661,7 +661,10 @@ class ModelManager:
         `MangaOcrHip` (core/ml/manga_ocr.py: ViT encoder + BERT decoder as libmtx_hip graphs, beam search on the host) is built from the
         directory staged under models/manga-ocr-base and cached in the slot; nothing staged -> ModelError, which
         `extract_text_with_manga_ocr` turns into the reference's "[OCR FAILED]" markers.  `manga_ocr_storage` ("f16" | "bf16" | "f32") picks the
-        storage type before the first call ("f32": the fp32 kernels throughout)."""
+        storage type before the first call ("f32": the fp32 kernels throughout), `manga_ocr_slots` (1 .. 8) how many crops
+        `extract_text_with_manga_ocr` reads together (`MangaOcrHip(slots=)`: per slot a set of self-attention caches and cross K | V, about
+        7.4 MB + 1.2 MB at the published sizes; 1 = one crop at a time, nothing allocated; slots * num_beams <= 32).  The default is
+        core/ml/manga_ocr.py DEFAULT_SLOTS, decided by the page measurement in docs/experiments.md; the texts do not depend on it."""
         with self._lock:
             if self.is_loaded(ModelType.MANGA_OCR):
                 return self.models[ModelType.MANGA_OCR]
@@ -675,7 +678,11 @@ class ModelManager:
                 storage = getattr(self, "manga_ocr_storage", "f16")
                 if storage not in ("f16", "bf16", "f32"):
                     raise ModelError(f"manga_ocr_storage must be 'f16', 'bf16' or 'f32', not {storage!r}")
-                model = MangaOcrHip.from_directory(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16, "f32": abi.F32}[storage])
+                slots = getattr(self, "manga_ocr_slots", None)      # None: DEFAULT_SLOTS, lowered to what the checkpoint's beams allow
+                if slots is not None and (not isinstance(slots, int) or isinstance(slots, bool) or not 1 <= slots <= abi.SLOTS_MAX):
+                    raise ModelError(f"manga_ocr_slots must be an integer 1 .. {abi.SLOTS_MAX}, not {slots!r}")
+                model = MangaOcrHip.from_directory(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16, "f32": abi.F32}[storage],
+                                                   slots=slots)
             except ModelError:
                 raise
             except Exception as e:

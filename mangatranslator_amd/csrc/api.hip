@@ -37,6 +37,9 @@ int causal_attn_launch(const mtx_causal_attn_args*, void*, const char**);
 int greedy_launch(const mtx_greedy_args*, void*, const char**);
 int causal_step_batch_launch(const mtx_causal_step_batch_args*, void*, const char**);
 int greedy_batch_launch(const mtx_greedy_batch_args*, void*, const char**);
+int rowlin_wide_launch(const mtx_rowlin_args*, void*, const char**);
+int decode_attn_batch_launch(const mtx_decode_attn_batch_args*, void*, const char**);
+int beam_step_launch(const mtx_beam_step_args*, void*, const char**);
 
 static thread_local std::string g_err;
 
@@ -90,6 +93,9 @@ static int run_op(const mtx_op& op, void* stream) {
     case MTX_OP_GREEDY: rc = greedy_launch(&op.u.greedy, stream, &err); break;
     case MTX_OP_CAUSAL_STEP_BATCH: rc = causal_step_batch_launch(&op.u.cstepb, stream, &err); break;
     case MTX_OP_GREEDY_BATCH: rc = greedy_batch_launch(&op.u.greedyb, stream, &err); break;
+    case MTX_OP_ROWLIN_WIDE: rc = rowlin_wide_launch(&op.u.rowlin, stream, &err); break;
+    case MTX_OP_DECODE_ATTN_BATCH: rc = decode_attn_batch_launch(&op.u.dattnb, stream, &err); break;
+    case MTX_OP_BEAM_STEP: rc = beam_step_launch(&op.u.beam, stream, &err); break;
     case MTX_OP_MEMSET:
       if (op.u.ms.bytes < 0 || (!op.u.ms.ptr && op.u.ms.bytes > 0)) { rc = MTX_ERR_INVALID; err = "memset: null pointer or negative size"; break; }
       fill_bytes_async(op.u.ms.ptr, op.u.ms.value, (size_t)op.u.ms.bytes, stream);        // a kernel: a captured hipMemsetAsync (memset node) did not always clear (mtx_device.h)
@@ -193,6 +199,9 @@ size_t mtx_abi_sizeof(int kind) {
     case MTX_OP_GREEDY: return sizeof(mtx_greedy_args);
     case MTX_OP_CAUSAL_STEP_BATCH: return sizeof(mtx_causal_step_batch_args);
     case MTX_OP_GREEDY_BATCH: return sizeof(mtx_greedy_batch_args);
+    case MTX_OP_ROWLIN_WIDE: return sizeof(mtx_rowlin_args);
+    case MTX_OP_DECODE_ATTN_BATCH: return sizeof(mtx_decode_attn_batch_args);
+    case MTX_OP_BEAM_STEP: return sizeof(mtx_beam_step_args);
     case 100: return sizeof(mtx_clean_args);       /* op-level only (not a plan op) */
     default: return 0;
   }
@@ -263,6 +272,9 @@ MTX_OP_ENTRY(mtx_causal_attention, mtx_causal_attn_args, causal_attn_launch)
 MTX_OP_ENTRY(mtx_greedy_pick, mtx_greedy_args, greedy_launch)
 MTX_OP_ENTRY(mtx_causal_step_batch, mtx_causal_step_batch_args, causal_step_batch_launch)
 MTX_OP_ENTRY(mtx_greedy_pick_batch, mtx_greedy_batch_args, greedy_batch_launch)
+MTX_OP_ENTRY(mtx_row_linear_wide, mtx_rowlin_args, rowlin_wide_launch)
+MTX_OP_ENTRY(mtx_decode_attention_batch, mtx_decode_attn_batch_args, decode_attn_batch_launch)
+MTX_OP_ENTRY(mtx_beam_step, mtx_beam_step_args, beam_step_launch)
 
 
 int mtx_gemm_last_split(int* whole_tiles, int* k_slices, int* tail_pieces) {

@@ -47,86 +47,7 @@ __device__ __forceinline__ void dec_merge(float& m, float& l, float (&acc)[8], f
 
 template <typename T>
 __global__ __launch_bounds__(256) void decode_attn_kernel(mtx_decode_attn_args p) {
-  __shared__ float part[4][2 + DEC_D];
-  const int h = blockIdx.x, r = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int sub = tid & 7;                 // which 8 of the head's 64 elements
-  const int grp = tid >> 3;                // 0..31: the keys j = grp, grp + 32, ...
-  const int pos = *p.pos;
-  if (pos < 0 || pos >= p.max_len) return;            // nothing is read or written for a position outside the cache
-  const long hd = (long)p.heads * DEC_D;
-  const T* row = reinterpret_cast<const T*>(p.qkv) + (long)r * p.ld_qkv + (long)h * DEC_D + sub * 8;
-  T* KC = reinterpret_cast<T*>(p.k_cache);
-  T* VC = reinterpret_cast<T*>(p.v_cache);
-  float q[8], k_own[8], v_own[8];
-  load8<T>(row, q);
-  load8<T>(row + hd, k_own);
-  load8<T>(row + 2 * hd, v_own);
-  if (grp == 0) {                           // this row's k and v go to its own slot at `pos` (nobody reads that position in this launch)
-    const long at = ((long)pos * p.slots + r) * hd + (long)h * DEC_D + sub * 8;
-    store8<T>(KC + at, k_own);              // (values of the storage type: the round trip through float is exact)
-    store8<T>(VC + at, v_own);
-  }
-  float m = DEC_NEG, l = 0.f, acc[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-  for (int j0 = 0; j0 <= pos; j0 += 32) {             // wave-uniform trip count: every lane reaches the shuffles
-    const int j = j0 + grp;
-    float kf[8], vf[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { kf[e] = k_own[e]; vf[e] = v_own[e]; }
-    if (j < pos) {
-      int slot = p.src[(long)j * p.slots + r];
-      slot = slot < 0 ? 0 : (slot >= p.slots ? p.slots - 1 : slot);          // a damaged table must not leave the cache
-      const long at = ((long)j * p.slots + slot) * hd + (long)h * DEC_D + sub * 8;
-      load8<T>(KC + at, kf);
-      load8<T>(VC + at, vf);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += q[e] * kf[e];
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    if (j <= pos) {
-      s *= p.scale;
-      const float mn = s > m ? s : m;
-      const float f = __expf(m - mn), w = __expf(s - mn);
-      l = l * f + w;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] = acc[e] * f + w * vf[e];
-      m = mn;
-    }
-  }
-  // the 8 lane groups of a wave, then the 4 waves
-#pragma unroll
-  for (int off = 8; off <= 32; off <<= 1) {
-    const float m2 = __shfl_xor(m, off, 64), l2 = __shfl_xor(l, off, 64);
-    float a2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a2[e] = __shfl_xor(acc[e], off, 64);
-    dec_merge(m, l, acc, m2, l2, a2);
-  }
-  if (lane < 8) {
-    if (sub == 0) { part[wave][0] = m; part[wave][1] = l; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) part[wave][2 + sub * 8 + e] = acc[e];
-  }
-  __syncthreads();
-  if (tid < 8) {
-    m = part[0][0]; l = part[0][1];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = part[0][2 + sub * 8 + e];
-    for (int w = 1; w < 4; ++w) {
-      float a2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a2[e] = part[w][2 + sub * 8 + e];
-      dec_merge(m, l, acc, part[w][0], part[w][1], a2);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = acc[e] / l;          // l >= 1: the key at the running maximum weighs exp(0)
-    store8<T>(reinterpret_cast<T*>(p.o) + (long)r * p.ld_o + (long)h * DEC_D + sub * 8, acc);
-  }
+#include "decode_attn_body.inc"
 }
 
 int decode_attn_launch(const mtx_decode_attn_args* a, void* stream, const char** err) {
@@ -223,6 +144,151 @@ int rowlin_launch(const mtx_rowlin_args* a0, void* stream, const char** err) {
 #undef MTX_ROWLIN_R
 #undef MTX_ROWLIN
       })) { *err = "rowlin: dtype must be bf16, f16 or f32"; return MTX_ERR_INVALID; }
+  return MTX_OK;
+}
+
+// ---- the same two for S groups of B beams (MTX_OP_DECODE_ATTN_BATCH, MTX_OP_ROWLIN_WIDE) ------------------------------------------------------
+// grid (heads, beams, groups): group blockIdx.z owns its caches, its ancestry table and its rows of qkv and o, so the groups never meet
+template <typename T>
+__global__ __launch_bounds__(256) void decode_attn_batch_kernel(mtx_decode_attn_batch_args b) {
+  const int g = blockIdx.z;
+  const int32_t* st = b.state + (long)g * b.state_stride;
+  if (st[MTX_BEAM_DONE] != 0) return;                    // (workgroup-uniform, before the barrier) a finished or empty group sits out
+  mtx_decode_attn_args p;
+  p.qkv = reinterpret_cast<const T*>(b.qkv) + (long)g * b.beams * b.ld_qkv;
+  p.k_cache = reinterpret_cast<T*>(b.k_cache) + (long)g * b.cache_stride;
+  p.v_cache = reinterpret_cast<T*>(b.v_cache) + (long)g * b.cache_stride;
+  p.pos = st + MTX_BEAM_POS;                             // the body reads it and leaves (as uniformly) unless 0 <= pos < max_len
+  p.src = b.src + (long)g * b.src_stride;
+  p.o = reinterpret_cast<T*>(b.o) + (long)g * b.beams * b.ld_o;
+  p.rows = b.beams; p.slots = b.beams; p.heads = b.heads; p.d = b.d; p.max_len = b.max_len;
+  p.ld_qkv = b.ld_qkv; p.ld_o = b.ld_o;
+  p.scale = b.scale; p.dtype = b.dtype;
+#include "decode_attn_body.inc"
+}
+
+int decode_attn_batch_launch(const mtx_decode_attn_batch_args* a, void* stream, const char** err) {
+  if (!a->qkv || !a->k_cache || !a->v_cache || !a->state || !a->src || !a->o) { *err = "decode_attn_batch: null operand"; return MTX_ERR_INVALID; }
+  if (a->d != DEC_D) { *err = "decode_attn_batch: only head width 64 is built"; return MTX_ERR_UNSUPPORTED; }
+  if (a->groups < 1 || a->groups > MTX_SLOTS_MAX || a->beams < 1 || a->beams > MTX_BEAM_MAX) { *err = "decode_attn_batch: needs 1 <= groups <= MTX_SLOTS_MAX, 1 <= beams <= 8"; return MTX_ERR_INVALID; }
+  if (a->heads < 1 || a->heads > 65535 || a->max_len < 1) { *err = "decode_attn_batch: bad heads / max_len"; return MTX_ERR_INVALID; }
+  if (a->ld_qkv % 8 || a->ld_o % 8 || a->ld_qkv < 3L * a->heads * DEC_D || a->ld_o < (long)a->heads * DEC_D) { *err = "decode_attn_batch: row strides must be multiples of 8 and cover the row"; return MTX_ERR_INVALID; }
+  if (a->cache_stride % 8 || a->cache_stride < (long)a->max_len * a->beams * a->heads * DEC_D) { *err = "decode_attn_batch: cache_stride must be a multiple of 8 and cover one cache"; return MTX_ERR_INVALID; }
+  if (a->src_stride < (long)a->max_len * a->beams || a->state_stride < 2) { *err = "decode_attn_batch: src_stride / state_stride too short"; return MTX_ERR_INVALID; }
+  if ((((size_t)a->qkv | (size_t)a->k_cache | (size_t)a->v_cache | (size_t)a->o) & 15) != 0) { *err = "decode_attn_batch: operands must be 16-byte aligned"; return MTX_ERR_INVALID; }
+  const dim3 grid((unsigned)a->heads, (unsigned)a->beams, (unsigned)a->groups);
+  if (!with_decode_type(a->dtype, [&](auto t) { MTX_LAUNCH((decode_attn_batch_kernel<typename decltype(t)::type>), grid, dim3(256), 0, stream, *a); })) {
+    *err = "decode_attn_batch: dtype must be bf16, f16 or f32"; return MTX_ERR_INVALID;
+  }
+  return MTX_OK;
+}
+
+// The skinny-row linear for up to 32 rows: a wave owns NW columns for ALL RT rows, so the weights are read once whatever `rows` is.  Every
+// output runs rowlin_kernel's arithmetic — the same chunks in the same order, the same eight multiply-adds, the same wave sum — which does
+// not depend on RT or NW: row r is bit for bit the single op's.  RT * NW may exceed the 64 lanes of the finishing step: it is looped.
+// One multiply-add of the wide kernel.  With 16-bit storage the product of two operands is exact in fp32, so a fused and an unfused
+// multiply-add give the same bits and the plain expression serves.  With fp32 storage they do not, and the compiler's choice in
+// rowlin_kernel<float, 1, NW> — the kernel a single row runs on, whose code is pinned — is: the product rounded before the sum everywhere,
+// except in columns 0 and 1 of a wave's four at NW == 4, which are fused.  The wide kernel spells that choice out so that an fp32 row is the
+// single op's bit for bit (the GPU tier holds it to that for all three column tilings); the simulator never fuses.
+template <typename T, int NW>
+__device__ __forceinline__ float rowlin_wide_mac(float acc, float a, float w, int c) { return acc + a * w; }
+#ifndef MTX_EMU
+__device__ __forceinline__ float rowlin_unfused(float acc, float a, float w) {
+#pragma clang fp contract(off)
+  const float prod = a * w;
+  return acc + prod;
+}
+template <> __device__ __forceinline__ float rowlin_wide_mac<float, 1>(float acc, float a, float w, int) { return rowlin_unfused(acc, a, w); }
+template <> __device__ __forceinline__ float rowlin_wide_mac<float, 2>(float acc, float a, float w, int) { return rowlin_unfused(acc, a, w); }
+template <> __device__ __forceinline__ float rowlin_wide_mac<float, 4>(float acc, float a, float w, int c) {
+  return c < 2 ? __builtin_fmaf(a, w, acc) : rowlin_unfused(acc, a, w);
+}
+#endif
+
+template <typename T, int RT, int NW>
+__global__ __launch_bounds__(256) void rowlin_wide_kernel(mtx_rowlin_args p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long n0 = ((long)blockIdx.x * 4 + wave) * NW;
+  if (n0 >= p.n) return;                                 // wave-uniform
+  const T* A = reinterpret_cast<const T*>(p.a);
+  const T* W = reinterpret_cast<const T*>(p.w);
+  const long nch = p.k / 8;
+  float acc[RT][NW];
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int c = 0; c < NW; ++c) acc[r][c] = 0.f;
+  for (long ch = lane; ch < nch; ch += 64) {
+    float wf[NW][8];
+#pragma unroll
+    for (int c = 0; c < NW; ++c) {
+      const long n = n0 + c < p.n ? n0 + c : p.n - 1;      // a wave's columns past N repeat the last one and are not stored
+      load8<T>(W + n * p.ldw + ch * 8, wf[c]);
+    }
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+      if (r < p.rows) {
+        float af[8];
+        load8<T>(A + (long)r * p.lda + ch * 8, af);
+#pragma unroll
+        for (int c = 0; c < NW; ++c)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[r][c] = rowlin_wide_mac<T, NW>(acc[r][c], af[e], wf[c][e], c);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int c = 0; c < NW; ++c) acc[r][c] = wave_sum(acc[r][c]);
+  // pass q: lane finishes output (r, n0 + c) with r * NW + c == q * 64 + lane
+#pragma unroll
+  for (int q = 0; q < (RT * NW + 63) / 64; ++q) {
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+      for (int c = 0; c < NW; ++c)
+        if ((r * NW + c) / 64 == q) v = lane == (r * NW + c) % 64 ? acc[r][c] : v;
+    const int idx = q * 64 + lane;
+    const int r = idx / NW;
+    const long n = n0 + idx % NW;
+    if (idx >= RT * NW || r >= p.rows || n >= p.n) continue;
+    v = apply_act(v * p.alpha + (p.bias ? p.bias[n] : 0.f), p.act, p.act_param);
+    if (p.out_dtype == MTX_F32) {
+      if (p.res) v += to_f32(reinterpret_cast<const T*>(p.res)[(long)r * p.ldres + n]);
+      reinterpret_cast<float*>(p.c)[(long)r * p.ldc + n] = v;
+      continue;
+    }
+    T t = from_f32<T>(v);                                   // round_T(act(alpha * acc + bias))
+    if (p.res) t = from_f32<T>(to_f32(t) + to_f32(reinterpret_cast<const T*>(p.res)[(long)r * p.ldres + n]));      // the second rounding
+    reinterpret_cast<T*>(p.c)[(long)r * p.ldc + n] = t;
+  }
+}
+
+int rowlin_wide_launch(const mtx_rowlin_args* a0, void* stream, const char** err) {
+  if (!a0->a || !a0->w || !a0->c) { *err = "rowlin_wide: null operand"; return MTX_ERR_INVALID; }
+  if (a0->rows < 1 || a0->rows > MTX_WIDE_ROWS_MAX) { *err = "rowlin_wide: needs 1 <= rows <= 32"; return MTX_ERR_INVALID; }
+  if (a0->n < 1 || a0->k < 8 || a0->k % 8 || a0->lda % 8 || a0->ldw % 8 || a0->lda < a0->k || a0->ldw < a0->k) { *err = "rowlin_wide: K, lda and ldw must be multiples of 8 that cover K"; return MTX_ERR_INVALID; }
+  if ((((size_t)a0->a | (size_t)a0->w) & 15) != 0) { *err = "rowlin_wide: a and w must be 16-byte aligned"; return MTX_ERR_INVALID; }
+  if (a0->ldc < a0->n || (a0->res && a0->ldres < a0->n)) { *err = "rowlin_wide: ldc / ldres must cover N"; return MTX_ERR_INVALID; }
+  if (a0->out_dtype != MTX_F32 && a0->out_dtype != a0->dtype) { *err = "rowlin_wide: out_dtype must be the storage type or fp32"; return MTX_ERR_INVALID; }
+  mtx_rowlin_args a = *a0;
+  if (a.alpha == 0.f) a.alpha = 1.f;                      // as mtx_gemm: an unset alpha means 1
+  const int nw = a.n >= 4096 ? 4 : (a.n >= 2048 ? 2 : 1); // the single op's column tiling
+  const unsigned blocks = (unsigned)((a.n + 4L * nw - 1) / (4L * nw));
+  const int rt = a.rows <= 8 ? 8 : (a.rows <= 16 ? 16 : 32);
+  if (!with_decode_type(a.dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+#define MTX_ROWLIN(RT, NW) MTX_LAUNCH((rowlin_wide_kernel<T, RT, NW>), dim3(blocks), dim3(256), 0, stream, a)
+#define MTX_ROWLIN_R(RT) do { if (nw == 4) MTX_ROWLIN(RT, 4); else if (nw == 2) MTX_ROWLIN(RT, 2); else MTX_ROWLIN(RT, 1); } while (0)
+        if (rt == 8) MTX_ROWLIN_R(8);
+        else if (rt == 16) MTX_ROWLIN_R(16);
+        else MTX_ROWLIN_R(32);
+#undef MTX_ROWLIN_R
+#undef MTX_ROWLIN
+      })) { *err = "rowlin_wide: dtype must be bf16, f16 or f32"; return MTX_ERR_INVALID; }
   return MTX_OK;
 }
 

@@ -20,6 +20,7 @@ IMG_NCHW_F32_TO_NHWC, IMG_NHWC_TO_NCHW_F32, IMG_NHWC_TO_HWC_U8, IMG_HWC_U8_TO_NH
  OP_MEMSET, OP_MASK_SELECT, OP_PREPROC, OP_YOLO_DECODE, OP_DETR, OP_QUANT, OP_TAIL, OP_TEXTCOLOR) = range(1, 18)
 OP_DECODE_ATTN, OP_ROWLIN = 18, 19                             # the decode step's two ops (csrc/decode.hip)
 OP_CAUSAL_STEP_BATCH, OP_GREEDY_BATCH = 22, 23                 # the same two for up to SLOTS_MAX sequences in one launch (additive to ABI 12)
+OP_ROWLIN_WIDE, OP_DECODE_ATTN_BATCH, OP_BEAM_STEP = 24, 25, 26  # manga-ocr's step for S groups of B beams, the search on the device (additive to ABI 12)
 OP_CAUSAL_ATTN, OP_GREEDY = 20, 21                             # causal GQA attention over a cache, the greedy pick (csrc/causal.hip)
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -238,6 +239,56 @@ class GreedyBatchArgs(C.Structure):
                 ("slots", i32), ("vocab", i32), ("max_new", i32), ("n_eos", i32), ("advance", i32), ("eos", i32 * 4)]
 
 
+WIDE_ROWS_MAX, BEAM_MAX, BEAM_CHUNK = 32, 8, 512
+# the group state block of the batched manga-ocr step: int32 words per group (include/mtx_hip.h, MTX_BEAM_*)
+BEAM_POS, BEAM_DONE, BEAM_UNSAT, BEAM_OUT_LEN = 0, 1, 2, 3
+BEAM_RSCORE, BEAM_FSCORE, BEAM_FDONE, BEAM_FLEN, BEAM_PARENT, BEAM_OUT = 8, 16, 24, 32, 40, 48
+
+
+def beam_running(beams: int, max_len: int) -> int:
+    return BEAM_OUT + max_len
+
+
+def beam_fin(beams: int, max_len: int) -> int:
+    return beam_running(beams, max_len) + beams * max_len
+
+
+def beam_stage(beams: int, max_len: int) -> int:
+    return beam_fin(beams, max_len) + beams * max_len
+
+
+def beam_src(beams: int, max_len: int) -> int:
+    return beam_stage(beams, max_len) + beams * max_len
+
+
+def beam_state_words(beams: int, max_len: int) -> int:
+    """MTX_BEAM_STATE_WORDS of include/mtx_hip.h"""
+    return beam_src(beams, max_len) + beams * max_len
+
+
+def beam_keep(beams: int, n_eos: int) -> int:
+    return max(2, 1 + n_eos) * beams
+
+
+def beam_scratch_bytes(rows: int, vocab: int, keep: int) -> int:
+    """MTX_BEAM_SCRATCH_BYTES of include/mtx_hip.h"""
+    return rows * 8 + rows * ((vocab + BEAM_CHUNK - 1) // BEAM_CHUNK) * keep * 8
+
+
+class DecodeAttnBatchArgs(C.Structure):
+    _fields_ = [("qkv", vp), ("k_cache", vp), ("v_cache", vp), ("state", vp), ("src", vp), ("o", vp),
+                ("groups", i32), ("beams", i32), ("heads", i32), ("d", i32), ("max_len", i32),
+                ("ld_qkv", i64), ("ld_o", i64), ("cache_stride", i64), ("src_stride", i64), ("state_stride", i64),
+                ("scale", f32), ("dtype", i32)]
+
+
+class BeamStepArgs(C.Structure):
+    _fields_ = [("logits", vp), ("state", vp), ("tok_idx", vp), ("pos_idx", vp), ("len_pow", vp), ("scratch", vp),
+                ("ld_logits", i64), ("state_stride", i64),
+                ("groups", i32), ("beams", i32), ("vocab", i32), ("max_len", i32), ("max_length", i32), ("n_eos", i32), ("ngram", i32),
+                ("early", i32), ("lp_positive", i32), ("eos", i32 * 4)]
+
+
 def greedy_scratch_bytes(vocab: int) -> int:
     """MTX_GREEDY_SCRATCH_BYTES of include/mtx_hip.h"""
     return (vocab + GREEDY_CHUNK - 1) // GREEDY_CHUNK * 8
@@ -261,7 +312,7 @@ class _OpUnion(C.Union):
                 ("gn", GroupNormArgs), ("ew", EwArgs), ("ca", CaArgs), ("img", ImgArgs),
                 ("rt", ResizeThreshArgs), ("ms", MemsetArgs), ("sel", MaskSelectArgs), ("pre", PreprocArgs), ("yd", YoloDecodeArgs), ("detr", DetrArgs), ("quant", QuantArgs), ("tail", TailArgs), ("tc", TextColorArgs),
                 ("dattn", DecodeAttnArgs), ("rowlin", RowLinArgs), ("cattn", CausalAttnArgs), ("greedy", GreedyArgs),
-                ("cstepb", CausalStepBatchArgs), ("greedyb", GreedyBatchArgs)]
+                ("cstepb", CausalStepBatchArgs), ("greedyb", GreedyBatchArgs), ("dattnb", DecodeAttnBatchArgs), ("beam", BeamStepArgs)]
 
 
 LANE_SIDE, LANE_JOIN = 1, 2
@@ -276,19 +327,21 @@ ARG_TYPES = {OP_CONV2D: ConvArgs, OP_GEMM: GemmArgs, OP_ATTN: AttnArgs, OP_NORM:
              OP_RESIZE_THRESH: ResizeThreshArgs, OP_MEMSET: MemsetArgs,
              OP_MASK_SELECT: MaskSelectArgs, OP_PREPROC: PreprocArgs, OP_YOLO_DECODE: YoloDecodeArgs, OP_DETR: DetrArgs, OP_QUANT: QuantArgs, OP_TAIL: TailArgs, OP_TEXTCOLOR: TextColorArgs,
              OP_DECODE_ATTN: DecodeAttnArgs, OP_ROWLIN: RowLinArgs, OP_CAUSAL_ATTN: CausalAttnArgs, OP_GREEDY: GreedyArgs,
-             OP_CAUSAL_STEP_BATCH: CausalStepBatchArgs, OP_GREEDY_BATCH: GreedyBatchArgs}
+             OP_CAUSAL_STEP_BATCH: CausalStepBatchArgs, OP_GREEDY_BATCH: GreedyBatchArgs,
+             OP_ROWLIN_WIDE: RowLinArgs, OP_DECODE_ATTN_BATCH: DecodeAttnBatchArgs, OP_BEAM_STEP: BeamStepArgs}
 UNION_FIELD = {OP_CONV2D: "conv", OP_GEMM: "gemm", OP_ATTN: "attn", OP_NORM: "norm",
                OP_GROUPNORM: "gn", OP_EW: "ew", OP_CA: "ca", OP_IMG: "img",
                OP_RESIZE_THRESH: "rt", OP_MEMSET: "ms", OP_MASK_SELECT: "sel", OP_PREPROC: "pre", OP_YOLO_DECODE: "yd", OP_DETR: "detr", OP_QUANT: "quant", OP_TAIL: "tail", OP_TEXTCOLOR: "tc",
                OP_DECODE_ATTN: "dattn", OP_ROWLIN: "rowlin", OP_CAUSAL_ATTN: "cattn", OP_GREEDY: "greedy",
-               OP_CAUSAL_STEP_BATCH: "cstepb", OP_GREEDY_BATCH: "greedyb"}
+               OP_CAUSAL_STEP_BATCH: "cstepb", OP_GREEDY_BATCH: "greedyb",
+               OP_ROWLIN_WIDE: "rowlin", OP_DECODE_ATTN_BATCH: "dattnb", OP_BEAM_STEP: "beam"}
 
 # every symbol include/mtx_hip.h declares (tests check the built library exports all of them)
 EXPORTS = [
     "mtx_abi_version", "mtx_abi_sizeof", "mtx_last_error", "mtx_init", "mtx_device_info",
     "mtx_conv2d", "mtx_conv2d_tiles", "mtx_gemm", "mtx_gemm_last_split", "mtx_attention", "mtx_norm", "mtx_groupnorm",
     "mtx_elementwise", "mtx_channel_attention", "mtx_image_convert", "mtx_resize_threshold",
-    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
+    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_row_linear_wide", "mtx_decode_attention_batch", "mtx_beam_step", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
     "mtx_plan_create", "mtx_plan_run", "mtx_plan_run_graph", "mtx_plan_num_ops",
     "mtx_plan_run_range", "mtx_plan_destroy", "mtx_plan_time", "mtx_plan_time_range", "mtx_plan_time_ops",
 ]

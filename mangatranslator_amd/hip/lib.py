@@ -51,7 +51,9 @@ class MtxLibrary:
                         ("mtx_text_color", abi.TextColorArgs),
                         ("mtx_decode_attention", abi.DecodeAttnArgs), ("mtx_row_linear", abi.RowLinArgs),
                         ("mtx_causal_attention", abi.CausalAttnArgs), ("mtx_greedy_pick", abi.GreedyArgs),
-                        ("mtx_causal_step_batch", abi.CausalStepBatchArgs), ("mtx_greedy_pick_batch", abi.GreedyBatchArgs)):
+                        ("mtx_causal_step_batch", abi.CausalStepBatchArgs), ("mtx_greedy_pick_batch", abi.GreedyBatchArgs),
+                        ("mtx_row_linear_wide", abi.RowLinArgs), ("mtx_decode_attention_batch", abi.DecodeAttnBatchArgs),
+                        ("mtx_beam_step", abi.BeamStepArgs)):
             getattr(d, name).argtypes = [C.POINTER(t), C.c_void_p]
         d.mtx_host_text_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.c_void_p, C.POINTER(C.c_int)]

@@ -491,6 +491,67 @@ class PlanBuilder:
         self._add(abi.OP_ROWLIN, g, label)
         return out
 
+    def row_linear_wide(self, a_t, w_t, rows, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE, res=None, ldres=None,
+                        alpha=1.0, out_f32=False, label="rowlin_wide"):
+        """MTX_OP_ROWLIN_WIDE: `row_linear` for up to 32 rows; the weights are read once per launch and every row is bit for bit the single
+        op's"""
+        if out is None:
+            out = self.buf((rows, n), torch.float32 if out_f32 else self.tdtype)
+        g = abi.RowLinArgs()
+        g.a, g.w, g.bias, g.res, g.c = _ptr(a_t), _ptr(w_t), _ptr(bias), _ptr(res), _ptr(out)
+        g.rows, g.n, g.k = rows, n, k
+        g.lda, g.ldw, g.ldc, g.ldres = (lda or k), (ldw or k), (ldc or n), (ldres or n)
+        g.act, g.act_param, g.alpha = act, 0.0, alpha
+        g.dtype, g.out_dtype = self.dtype, (abi.F32 if out_f32 else self.dtype)
+        self._add(abi.OP_ROWLIN_WIDE, g, label)
+        return out
+
+    def decode_attention_batch(self, qkv, k_cache, v_cache, state, o, groups, beams, heads, d, max_len, scale, cache_stride=None, src=None,
+                               src_stride=None, state_stride=None, ld_qkv=None, ld_o=None, label="decode_attn_batch"):
+        """MTX_OP_DECODE_ATTN_BATCH: `decode_attention` for `groups` groups of `beams` rows, each group at the position its state block
+        holds.  qkv [groups * beams, ld_qkv], o [groups * beams, ld_o], caches [groups, max_len, beams, heads * d]; `state` is the int32
+        [groups, state_stride] block of `beam_step` (a group with done != 0 or pos outside [0, max_len) sits out); the ancestry tables are
+        the block's own unless `src` [groups, max_len, beams] is given"""
+        assert state.dtype == torch.int32 and state.is_contiguous()
+        words = abi.beam_state_words(beams, max_len)
+        a = abi.DecodeAttnBatchArgs()
+        a.qkv, a.k_cache, a.v_cache, a.state, a.o = _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(state), _ptr(o)
+        a.state_stride = state_stride if state_stride is not None else words
+        if src is None:
+            a.src, a.src_stride = state.data_ptr() + 4 * abi.beam_src(beams, max_len), a.state_stride
+        else:
+            assert src.dtype == torch.int32
+            a.src, a.src_stride = _ptr(src), (src_stride if src_stride is not None else max_len * beams)
+        a.groups, a.beams, a.heads, a.d, a.max_len = groups, beams, heads, d, max_len
+        a.ld_qkv, a.ld_o = (ld_qkv or 3 * heads * d), (ld_o or heads * d)
+        a.cache_stride = cache_stride if cache_stride is not None else max_len * beams * heads * d
+        a.scale, a.dtype = scale, self.dtype
+        self._add(abi.OP_DECODE_ATTN_BATCH, a, label)
+        return o
+
+    def beam_step(self, logits, state, tok_idx, pos_idx, len_pow, groups, beams, vocab, max_len, max_length, eos, ngram=0, early=False,
+                  lp_positive=True, ld_logits=None, state_stride=None, label="beam_step"):
+        """MTX_OP_BEAM_STEP: one iteration of `beam_search` (core/ml/manga_ocr.py) per group with done == 0, on fp32 `logits`
+        [groups * beams, ld_logits] and the int32 [groups, state_stride] state block; writes the next token and position of every row to
+        `tok_idx` / `pos_idx`.  `len_pow`: fp32 [max_len], float32(float(j) ** length_penalty) for j = 1 ..; early: False, True or "never"."""
+        eos = [int(e) for e in eos]
+        assert len(eos) <= 4 and logits.dtype == torch.float32 and state.dtype == torch.int32 and state.is_contiguous()
+        assert tok_idx.dtype == torch.int32 and pos_idx.dtype == torch.int32 and len_pow.dtype == torch.float32
+        a = abi.BeamStepArgs()
+        keep = abi.beam_keep(beams, len(eos))
+        scratch = self.buf((max(abi.beam_scratch_bytes(max(groups * beams, 1), max(vocab, 1), keep), 16),), torch.uint8)
+        a.logits, a.state, a.tok_idx, a.pos_idx, a.len_pow, a.scratch = (_ptr(logits), _ptr(state), _ptr(tok_idx), _ptr(pos_idx), _ptr(len_pow),
+                                                                           scratch.data_ptr())
+        a.ld_logits = ld_logits if ld_logits is not None else vocab
+        a.state_stride = state_stride if state_stride is not None else abi.beam_state_words(beams, max_len)
+        a.groups, a.beams, a.vocab, a.max_len, a.max_length, a.n_eos, a.ngram = groups, beams, vocab, max_len, max_length, len(eos), ngram
+        a.early = 2 if early == "never" else (1 if early is True or early == 1 else 0)
+        a.lp_positive = 1 if lp_positive else 0
+        for i, e in enumerate(eos):
+            a.eos[i] = e
+        self._add(abi.OP_BEAM_STEP, a, label)
+        return state
+
     def v_f8t(self, v, rows, heads, ldv, v_off=0, out=None, label="v_f8t"):
         """MTX_EW_V_F8T: the value rows [rows, heads * 128] (16-bit, row stride ldv) as e4m3 V^T [heads * 128, ld] with ld = rows padded to 64, keys in
         accumulator order inside every 64-key tile — the operand of `attention(pv_f8=...)`.  -> (tensor, ld)"""

@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [paddleocr] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [mangaocr_batch] [paddleocr] ..."""
 import os
 import sys
 
@@ -513,9 +513,113 @@ def paddleocr_batch(reps=3, windows=4, iters=60):
                   f"{n * base / best:.2f} x the single step ({plan.n_ops} launches)", flush=True)
 
 
+def mangaocr_batch(reps=3, iters=40, crops=16):
+    """manga-ocr's batched step graph (`MangaOcrHip(slots=S)._stepper_batch()`: wide row linears, group-batched attention, the beam search on the
+    device) at S = 1, 2, 4, 8 beside today's 4-row step graph: published widths, f16, 4 beams, a 300-position cache.  Whole-graph replays; the
+    batched graph advances its own positions, so every window is `iters` LIVE steps from position 150 with the state reset before it (no group
+    at done = 1; the count of groups still searching after the window is printed), every window is warmed, the graphs alternate inside a
+    repetition, the figure is the best repetition with the spread beside it.  Then `crops` synthetic crops by the wall, `recognise_many` at
+    S = 8 against a loop of `__call__`, alternating, each ending in a synchronise, at max_length 32 and 300 (seeded weights never end a
+    hypothesis early, so a crop costs max_length - 1 steps)."""
+    import ctypes as C
+    import time
+    import numpy as np
+    from PIL import Image
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import manga_ocr_checks as mc
+    model, pixels = mc.oracle(0, real=True)
+    B, START = 4, 150
+    gen = dict(mc.GEN, max_length=300, num_beams=B)
+    single = mc.hip_model(lib, model, abi.F16, rows=B, gen=gen)
+    batched = {S: mc.hip_model(lib, model, abi.F16, rows=B, gen=gen, slots=S) for S in (1, 2, 4, 8)}
+    single.encode_pixels(pixels[0])
+    single.step(mc.mo.BeamStep(0, [2] * B, list(range(B))))
+    single._stepper().ctl[0] = START
+    plans = {0: single._stepper()}
+    for S, m in batched.items():
+        plan = m._stepper_batch()
+        m.encode_pixels(pixels[0])
+        for s in range(S):
+            m._reset_group(plan, s)
+        st = plan.state[0].clone()
+        L = m.max_len
+        run = abi.beam_running(B, L)
+        st[run:run + B * L] = 5
+        st[abi.BEAM_POS] = START
+        st.view(torch.float32)[abi.BEAM_RSCORE:abi.BEAM_RSCORE + B] = torch.tensor([-10.0, -11.0, -12.0, -13.0], device=st.device)
+        plan.start_state = st[None].expand(S, -1).contiguous()
+        plan.idx[1] = START
+        plans[S] = plan
+
+    def reset(S):
+        if S:
+            plans[S].state.copy_(plans[S].start_state)
+        torch.cuda.synchronize()
+
+    for S, plan in plans.items():
+        reset(S)
+        plan.time(3, graph=True)
+    runs, alive = {S: [] for S in plans}, {}
+    for _ in range(reps):
+        for S, plan in plans.items():
+            reset(S)
+            plan.time(3, graph=True)                               # warm this window
+            reset(S)
+            runs[S].append(plan.time(iters, graph=True))
+            if S:
+                alive[S] = int((plan.state[:, abi.BEAM_DONE] == 0).sum())
+    base = min(runs[0])
+    for S, plan in plans.items():
+        best, spread, n = min(runs[S]), max(runs[S]) - min(runs[S]), max(S, 1)
+        name = "single 4-row step graph (no search)" if S == 0 else f"batched step graph S = {S} ({alive[S]} of {S} groups still searching)"
+        print(f"  {name}: {best:.4f} ms per step (spread {spread:.4f} over {reps} repetitions) = {n * 1e3 / best:.0f} groups x tokens/s, "
+              f"{n * base / best:.2f} x the single step ({plan.n_ops} launches)", flush=True)
+    p8 = plans[8]
+    idx = [p8.beam_op]
+    ms = C.c_float(0.0)
+    reset(8)
+    lib.check(lib.mtx_plan_time_ops(p8._h, None, (C.c_int * 1)(*idx), 1, 20, C.byref(ms)), "mtx_plan_time_ops")
+    print(f"  beam step inside the S = 8 graph (graph with minus graph without): {ms.value / 20:.4f} ms", flush=True)
+    enc = single._encoder()
+    enc.time(3, graph=True)
+    enc_ms = min(enc.time(10, graph=True) for _ in range(reps))
+    print(f"  encoder: {enc_ms:.3f} ms per crop", flush=True)
+    for m in [single, *batched.values()]:
+        m.close()
+    imgs = []
+    for i in range(crops):
+        h, w = 40 + 13 * (i % 5), 48 + 17 * (i % 7)
+        yy, xx = np.mgrid[0:h, 0:w]
+        imgs.append(Image.fromarray(((xx * (3 + i) + yy * (5 + 2 * i)) % 97 + 80).astype(np.uint8)).convert("RGB"))
+    for max_length in (32, 300):
+        g = dict(mc.GEN, max_length=max_length, num_beams=B)
+        one, many = mc.hip_model(lib, model, abi.F16, rows=B, gen=g), mc.hip_model(lib, model, abi.F16, rows=B, gen=g, slots=8)
+        want = [one(im) for im in imgs[:2]]
+        got = many.recognise_many(imgs)                            # warms both paths (plans, graphs, pre-processing plans)
+        for im in imgs[2:]:
+            one(im)
+        walls = {"loop": [], "many": []}
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            a = [one(im) for im in imgs]
+            torch.cuda.synchronize(); walls["loop"].append((time.perf_counter() - t0) * 1e3)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            b = many.recognise_many(imgs)
+            torch.cuda.synchronize(); walls["many"].append((time.perf_counter() - t0) * 1e3)
+        same = sum(x == y for x, y in zip(a, b))
+        lo, mo_ = walls["loop"], walls["many"]
+        print(f"  {crops} crops, max_length {max_length}: loop of __call__ {min(lo):.1f} ms (spread {max(lo) - min(lo):.1f}), recognise_many S = 8 "
+              f"{min(mo_):.1f} ms (spread {max(mo_) - min(mo_):.1f}) = {min(lo) / min(mo_):.2f} x; encoder share of the batched page "
+              f"{crops * enc_ms / min(mo_) * 100:.0f} %; {same} of {crops} texts equal", flush=True)
+        one.close(); many.close()
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
+        if args[0] == "mangaocr_batch":
+            mangaocr_batch(); args = args[1:]
+            continue
         if args[0] == "paddleocr":
             paddleocr(); paddleocr_batch(); args = args[1:]
             continue

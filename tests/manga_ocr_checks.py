@@ -6,7 +6,9 @@ integers and the denominator a power of two, so the output is ONE rounding of an
 Decode attention, random: against fp32 torch on the same 16-bit inputs.  The bound is half a spacing of T at the reference (the one rounding) plus
 the fp32 softmax's own error over at most 300 keys, 300 * 2^-23 of the largest value.
 Skinny linear, exact: integer operands make every partial sum exact in any order, so the kernel must give the bytes of mtx_gemm (whose rounding
-points tests/exact_checks.py pins); on random data both are held to float64 with the bound of their common contract."""
+points tests/exact_checks.py pins); on random data both are held to float64 with the bound of their common contract.
+Skinny linears, contract: `check_rowlin_contract_exact` holds MTX_OP_ROWLIN and MTX_OP_ROWLIN_WIDE to float64 with those rounding points directly,
+for every (RT, NW) instantiation (`rowlin_tiling` restates the launchers' rule), so that neither mtx_gemm nor the other linear is the witness."""
 import ctypes as C
 
 import pytest
@@ -43,8 +45,9 @@ def _src_table(max_len, slots, rows):
     return src
 
 
-def _attn_ref(qkv, kc, vc, src, pos, rows, scale):
-    """fp32 torch on the same 16-bit inputs: [rows, HD]"""
+def _attn_ref(qkv, kc, vc, src, pos, rows, scale, heads=HEADS):
+    """fp32 torch on the same 16-bit inputs: [rows, heads * D]"""
+    HEADS, HD = heads, heads * D
     out = torch.zeros(rows, HD, dtype=torch.float64)
     qkv = qkv.double().cpu()
     kc, vc, src = kc.double().cpu(), vc.double().cpu(), src.cpu().long()
@@ -59,19 +62,21 @@ def _attn_ref(qkv, kc, vc, src, pos, rows, scale):
 
 
 class _AttnRig:
-    def __init__(self, lib, dtype, rows, slots, max_len, d=D):
+    def __init__(self, lib, dtype, rows, slots, max_len, d=D, heads=HEADS, pad_qkv=0, pad_o=0):
         self.lib, self.dev, self.td = lib, _dev(lib), TD[dtype]
         self.rows, self.slots, self.max_len = rows, slots, max_len
+        HD = self.hd = heads * D
+        self.ld_qkv, self.ld_o = 3 * HD + pad_qkv, HD + pad_o          # row strides; the padding columns belong to the test
         pb = PlanBuilder(lib, self.dev, dtype)
-        self.qkv = pb.buf((rows, 3 * HD), self.td, zero=True)
+        self.qkv = pb.buf((rows, self.ld_qkv), self.td, zero=True)
         self.kc = pb.buf((max_len, slots, HD), self.td)
         self.vc = pb.buf((max_len, slots, HD), self.td)
         self.pos = pb.buf((1,), torch.int32, zero=True)
         self.src = pb.buf((max_len, slots), torch.int32, zero=True)
-        self.o = pb.buf((rows, HD), self.td, zero=True)
+        self.o = pb.buf((rows, self.ld_o), self.td, zero=True)
         self.scale = 0.125
         pb.decode_attention(self.qkv, self.kc, self.vc, self.pos, self.src, self.o, rows, slots, HD // d, d, max_len, self.scale,
-                            ld_qkv=3 * HD, ld_o=HD)
+                            ld_qkv=self.ld_qkv, ld_o=self.ld_o)
         self.pb = pb
         self.plan = None
 
@@ -82,12 +87,13 @@ class _AttnRig:
         _sync(self.lib)
 
 
-def check_decode_attn_exact(lib, dtype, n_keys, seed=0):
-    """R = 3, all keys equal, integer values: the mean over n_keys (a power of two) is exact; the kernel's bytes must equal its one rounding"""
-    assert n_keys & (n_keys - 1) == 0
-    rows, slots, pos = 3, 4, n_keys - 1
+def check_decode_attn_exact(lib, dtype, n_keys, seed=0, rows=3, slots=4, heads=HEADS):
+    """all keys equal, integer values: the mean over n_keys (a power of two) is exact; the kernel's bytes must equal its one rounding"""
+    assert n_keys & (n_keys - 1) == 0 and 1 <= rows <= slots <= 8
+    pos = n_keys - 1
+    HD = heads * D
     g = torch.Generator().manual_seed(seed)
-    rig = _AttnRig(lib, dtype, rows, slots, max_len=n_keys)
+    rig = _AttnRig(lib, dtype, rows, slots, max_len=n_keys, heads=heads)
     td = rig.td
     k0 = torch.randint(-3, 4, (HD,), generator=g).double()
     q = torch.randint(-3, 4, (rows, HD), generator=g).double()
@@ -107,14 +113,15 @@ def check_decode_attn_exact(lib, dtype, n_keys, seed=0):
     ref = ref.float().to(td).double()
     got = rig.o.double().cpu()
     bad = int((got != ref).sum())
-    assert bad == 0, f"decode attention, {n_keys} equal keys: {bad} of {ref.numel()} elements differ from the rounded exact mean"
+    assert bad == 0, f"decode attention, {n_keys} equal keys, rows={rows} heads={heads}: {bad} of {ref.numel()} elements differ from the rounded exact mean"
 
 
-def check_decode_attn_random(lib, dtype, rows, pos, seed=0):
+def check_decode_attn_random(lib, dtype, rows, pos, seed=0, slots=4, heads=HEADS):
     """returns the largest error relative to its bound"""
-    slots, max_len = 4, 304
+    max_len = 304
+    HD = heads * D
     g = torch.Generator().manual_seed(seed * 1000 + rows * 31 + pos)
-    rig = _AttnRig(lib, dtype, rows, slots, max_len)
+    rig = _AttnRig(lib, dtype, rows, slots, max_len, heads=heads)
     td = rig.td
     kc = torch.randn(max_len, slots, HD, generator=g).to(td)
     vc = torch.randn(max_len, slots, HD, generator=g).to(td)
@@ -123,6 +130,8 @@ def check_decode_attn_random(lib, dtype, rows, pos, seed=0):
         cb[pos:] = NAN_BITS                   # nothing at or beyond pos may be read ...
         cb[:, rows:] = NAN_BITS               # ... and no slot that holds no row
     src = _src_table(max_len, slots, rows)
+    if rows >= 3:
+        assert len(set(src[:rows, rows - 1].tolist())) == rows, "the last row must walk through every slot that holds a row"
     qkv = (torch.randn(rows, 3 * HD, generator=g) * 1.5).to(td)
     rig.qkv.copy_(qkv); rig.kc.copy_(kc); rig.vc.copy_(vc); rig.src.copy_(src); rig.pos.fill_(pos)
     rig.run()
@@ -130,11 +139,11 @@ def check_decode_attn_random(lib, dtype, rows, pos, seed=0):
     def compare(qkv_now, kc_ref, vc_ref, src_now, pos_now):
         got = rig.o.double().cpu()
         assert bool(torch.isfinite(got).all()), f"decode attention R={rows} pos={pos_now}: non-finite output (a cache entry beyond pos or a free slot was read)"
-        ref = _attn_ref(qkv_now, kc_ref, vc_ref, src_now, pos_now, rows, rig.scale)
+        ref = _attn_ref(qkv_now, kc_ref, vc_ref, src_now, pos_now, rows, rig.scale, heads)
         vmax = float(qkv_now[:, 2 * HD:].double().abs().max().clamp_min(vc_ref[:pos_now, :rows].double().abs().max() if pos_now else 0.0))
         bound = ref.abs() * 2.0 ** -(MANT[dtype] + 1) * (1 + 2.0 ** -6) + 300 * 2.0 ** -23 * vmax
         ratio = float(((got - ref).abs() / bound).max())
-        assert ratio <= 1.0, f"decode attention R={rows} pos={pos_now}: error {ratio:.2f} x the bound (one rounding + fp32 softmax)"
+        assert ratio <= 1.0, f"decode attention R={rows} heads={heads} pos={pos_now}: error {ratio:.2f} x the bound (one rounding + fp32 softmax)"
         return ratio
 
     worst = compare(qkv, kc, vc, src, pos)
@@ -152,6 +161,34 @@ def check_decode_attn_random(lib, dtype, rows, pos, seed=0):
     rig.run()
     worst = max(worst, compare(qkv2, want_k, want_v, src2, pos + 1))
     return worst
+
+
+def check_decode_attn_padded_strides(lib, dtype, rows=5, slots=8, heads=3, pos=33, seed=0):
+    """ld_qkv = 3 HD + 16 and ld_o = HD + 8: the bytes of the unpadded case; NaN in the padding of qkv is not read, the padding of o keeps
+    its sentinel"""
+    max_len = pos + 3
+    HD = heads * D
+    g = torch.Generator().manual_seed(seed + rows)
+    plain = _AttnRig(lib, dtype, rows, slots, max_len, heads=heads)
+    wide = _AttnRig(lib, dtype, rows, slots, max_len, heads=heads, pad_qkv=16, pad_o=8)
+    assert (wide.ld_qkv, wide.ld_o) == (3 * HD + 16, HD + 8)
+    td = plain.td
+    kc = torch.randn(max_len, slots, HD, generator=g).to(td)
+    vc = torch.randn(max_len, slots, HD, generator=g).to(td)
+    src = _src_table(max_len, slots, rows)
+    qkv = (torch.randn(rows, 3 * HD, generator=g) * 1.5).to(td)
+    padded = torch.full((rows, wide.ld_qkv), float("nan")).to(td)
+    padded[:, :3 * HD] = qkv
+    sentinel = torch.full((rows, wide.ld_o), 7.0).to(td)
+    for rig, q, o0 in ((plain, qkv, torch.zeros(rows, HD).to(td)), (wide, padded, sentinel)):
+        rig.qkv.copy_(q); rig.kc.copy_(kc); rig.vc.copy_(vc); rig.src.copy_(src); rig.pos.fill_(pos); rig.o.copy_(o0)
+        rig.run()
+    want, got = plain.o.cpu(), wide.o.cpu()
+    assert bool(torch.isfinite(want.float()).all()) and float(want.float().abs().max()) > 0
+    what = f"decode attention with padded strides R={rows} heads={heads}"
+    assert torch.equal(got[:, :HD].contiguous().view(torch.uint8), want.view(torch.uint8)), f"{what}: differs from the unpadded case"
+    assert torch.equal(got[:, HD:].contiguous().view(torch.uint8), sentinel[:, HD:].contiguous().view(torch.uint8)), f"{what}: the padding of o was written"
+    assert torch.equal(wide.kc.cpu().view(torch.uint8), plain.kc.cpu().view(torch.uint8)) and torch.equal(wide.vc.cpu().view(torch.uint8), plain.vc.cpu().view(torch.uint8))
 
 
 def check_decode_attn_refuses_d32(lib):
@@ -225,6 +262,74 @@ def check_rowlin_random(lib, dtype, rows, n, k, out_f32, seed=0):
         assert ratio <= 1.0, f"{name} {rows}x{n}x{k}: error {ratio:.2f} x the contract's bound against float64"
         worst = max(worst, ratio)
     return worst
+
+
+def rowlin_tiling(rows, n, wide):
+    """rowlin_launch's / rowlin_wide_launch's rule restated: (RT, NW) of rowlin_kernel<T, RT, NW> / rowlin_wide_kernel<T, RT, NW>"""
+    nw = 4 if n >= 4096 else (2 if n >= 2048 else 1)
+    if wide:
+        assert 1 <= rows <= 32
+        return (8 if rows <= 8 else (16 if rows <= 16 else 32)), nw
+    assert 1 <= rows <= 8
+    return (1 if rows == 1 else (4 if rows <= 4 else 8)), nw
+
+
+C_SENTINEL, RES_PAD = -77.0, 999.0
+_CONTRACT_OPERANDS = {}
+
+
+def _contract_operands(dtype, n, k):
+    """integer operands for 17 rows and their float64 product, built once per (dtype, n, k) and shared, never modified: a case reads its
+    leading rows"""
+    import exact_checks as ec
+    key = (dtype, n, k)
+    if key not in _CONTRACT_OPERANDS:
+        g = torch.Generator().manual_seed(n * 7 + k)
+        rng = abi.F16 if dtype == abi.F32 else dtype               # fp32 storage rounds nowhere: the f16 operand range serves
+        r, alpha = ec.operand_range(rng, k, spread=1.5)             # (RELU zeroes half of the outputs: the spread keeps precondition (c))
+        a, w = ec._ints(g, (17, k), r), ec._ints(g, (n, k), r)
+        bias, res = ec._ints(g, (n,), ec.INT_CAP[rng]), ec._ints(g, (17, n), ec.INT_CAP[rng])
+        assert k * r * r * alpha + ec.INT_CAP[rng] < ec.EXACT, "precondition (a): partial sums are not exact in fp32"
+        _CONTRACT_OPERANDS[key] = (a, w, bias, res, alpha, a @ w.t())
+    return _CONTRACT_OPERANDS[key]
+
+
+def check_rowlin_contract_exact(lib, dtype, rows, n, k, wide, out_f32, expect):
+    """the skinny linears against float64 with the contract's rounding points, not against mtx_gemm or each other: integer operands, a
+    power-of-two alpha, an integer bias and residual, RELU;  t = round_T(act(alpha acc + bias)), c = round_T(t + res);  an fp32 output and
+    fp32 storage round nowhere.  Zero differing elements; the output lies in a sentinel-filled buffer (ldc = n + 5, a spare row) and the
+    residual has ldres = n + 3.  `expect` = the (RT, NW) instantiation the case is meant for.  Returns the rounding share (None: no rounding)"""
+    import exact_checks as ec
+    assert rowlin_tiling(rows, n, wide) == expect, f"rows={rows} n={n} runs {rowlin_tiling(rows, n, wide)}, the case is meant for {expect}"
+    assert k % 8 == 0
+    dev, td = _dev(lib), TD[dtype]
+    out_f32 = out_f32 or dtype == abi.F32
+    a, w, bias, res, alpha, acc = _contract_operands(dtype, n, k)
+    a, res, acc = a[:rows], res[:rows], acc[:rows]
+    t = (acc * alpha + bias).clamp_min(0.0)
+    what = f"{'wide ' if wide else ''}row linear {rows}x{n}x{k} (RT, NW) = {expect}, {'fp32' if out_f32 else '16-bit'} out"
+    share = None
+    if out_f32:
+        ref = t + res
+        assert float(ref.abs().max()) < ec.EXACT
+    else:
+        ref = ec._round(ec._round(t, td) + res, td)
+        share = ec._assert_rounding_share(ref, dtype, what)
+    assert float((t > 0).double().mean()) > 0.3 and float((t == 0).double().mean()) > 0.3, "RELU must see both signs"
+    pb = PlanBuilder(lib, dev, dtype)
+    otd = torch.float32 if out_f32 else td
+    out = pb.const(torch.full((rows + 1, n + 5), C_SENTINEL).to(otd))
+    res_t = torch.full((rows, n + 3), RES_PAD, dtype=torch.float64)
+    res_t[:, :n] = res
+    op = pb.row_linear_wide if wide else pb.row_linear
+    op(pb.const(a.to(td)), pb.const(w.to(td)), rows, n, k, out=out, ldc=n + 5, bias=pb.const(bias.float()), act=abi.ACT_RELU, res=pb.const(res_t.to(td)),
+       ldres=n + 3, alpha=alpha, out_f32=out_f32)
+    _run(pb)
+    got = out.cpu().double()
+    ec._assert_equal(got[:rows, :n], ref, what)
+    got[:rows, :n] = C_SENTINEL
+    assert bool((got == C_SENTINEL).all()), f"{what}: the buffer changed outside the result"
+    return share
 
 
 # ---- the model against the transformers oracle -----------------------------------------------------------------------------------------------------

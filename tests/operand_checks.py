@@ -23,7 +23,7 @@ import math
 
 import torch
 
-from exact_checks import EXACT, INT_CAP, MANT, _assert_equal, _ints, _round, _spacing
+from exact_checks import EXACT, INT_CAP, MANT, ROUNDS_FROM, _assert_equal, _ints, _round, _spacing
 from mangatranslator_amd.hip import abi
 from mangatranslator_amd.hip.plan import Act, PlanBuilder, glu_interleave, residual_distance
 from op_checks import TD, _dev, _run
@@ -740,6 +740,127 @@ def check_gemm_glu_exact(lib, dtype, m, col0, hid, k, r=2, alpha=1.0 / 16, row_o
     assert bool((sc[keep] == S_SENTINEL).all()), f"{what}: scale words outside the target window were written"
     if col0:
         _assert_equal(cbuf[:, :col0].cpu(), PT[:, :col0], what + ": the ungated columns")
+
+
+# ---- the activation + MX-fp8 epilogue of the fp8 GEMM ---------------------------------------------------------------------------------------
+def gemm256_act_instantiation(act):
+    """with_gemm256_act (csrc/gemm.hip) restated: the ACT template argument of the 256-tile kernels; -1 = the runtime switch"""
+    return act if act in (abi.ACT_NONE, abi.ACT_SILU, abi.ACT_GELU_TANH) else -1
+
+
+def _act_formula(v, act, dt, slope):
+    v = v.to(dt)
+    if act == abi.ACT_SILU:
+        return v / (1.0 + torch.exp(-v))
+    if act == abi.ACT_GELU_TANH:
+        return 0.5 * v * (1.0 + torch.tanh(0.7978845608028654 * (v + 0.044715 * v * v * v)))
+    if act == abi.ACT_RELU:
+        return v.clamp_min(0.0)
+    if act == abi.ACT_LEAKY:
+        return torch.where(v > 0, v, v * slope)
+    assert act == abi.ACT_NONE
+    return v
+
+
+ACTQ_EXACT_ACTS = (abi.ACT_NONE, abi.ACT_RELU, abi.ACT_LEAKY)
+ACTQ_SLOPE = 2.0 ** -2
+
+
+def check_gemm_actq_exact(lib, dtype, m, n, k, act, instantiation, row_off=0, q_col_off=0, seed=0):
+    """mtx_gemm_args.actq_* (gemm256_f8_actq_kernel<T, ACT>) against Q_ref(round_T(act(alpha acc + bias))) — a reference that shares no
+    arithmetic with the kernel, where kontext_fp8_checks.check_gemm_f8_actq compares with mtx_quantize_mx.  Integer operands in [-r, r],
+    r <= 7, times a power of two per row of A (exact in MX e4m3: the block scale is a power of two; the factors spread the scale bytes), an
+    integer bias.  NONE, RELU and LEAKY with slope 2^-2 give h exactly: every byte and every scale byte is compared.  SILU and GELU_TANH
+    take the slack protocol of check_gemm_glu_exact unchanged (cap: 2 % left out, never an element of a zero block) on a narrower operand
+    range, so that act() sees |t| of a few units.  A zero block: 32 zero rows of W with a zero bias.  `instantiation` = the ACT the case
+    is meant for.  Returns (left-out share, rounding share)."""
+    dev, td = _dev(lib), TD[dtype]
+    assert gemm256_act_instantiation(act) == instantiation, f"act {act} runs gemm256_f8_actq_kernel<T, {gemm256_act_instantiation(act)}>, the case is meant for {instantiation}"
+    assert n % 256 == 0 and k % 128 == 0
+    exact = act in ACTQ_EXACT_ACTS
+    what = f"activation + MX-fp8 epilogue {m}x{n}x{k} act {act}"
+    g = torch.Generator().manual_seed(seed)
+    if exact:
+        from exact_checks import operand_range
+        r, alpha = operand_range(dtype, k, cap=7)
+        bias_cap = INT_CAP[dtype]
+    elif act == abi.ACT_SILU:
+        r, alpha, bias_cap = 2, 2.0 ** -4, 2
+    else:                                                     # the tanh form cancels in fp32 for t below -4: a narrower range keeps the slack sharp
+        r, alpha, bias_cap = 1, 2.0 ** -(4 + (k > 128)), 1
+    factor = torch.exp2(-torch.randint(0, 4, (m, 1), generator=g).double())          # 1, 1/2, 1/4, 1/8 per row
+    A, W = _ints(g, (m, k), r) * factor, _ints(g, (n, k), r)
+    bias = _ints(g, (n,), bias_cap)
+    zero_spans = torch.arange(1, n // 32, 3)
+    for s in zero_spans.tolist():
+        W[32 * s:32 * s + 32] = 0.0
+        bias[32 * s:32 * s + 32] = 0.0
+    assert r <= 7 and _exact_in(A, td) and (k * r * r * max(alpha, 1.0) + bias_cap) * 8 < EXACT, f"{what}: precondition — partial sums are not exact in fp32"
+    t = (A @ W.t()) * alpha + bias
+    ref = _act_formula(t, act, torch.float64, ACTQ_SLOPE)
+    near = _round(ref, td)
+    assert bool(torch.isfinite(near).all()) and float(near.abs().max()) < 60000.0, f"{what}: precondition — h leaves the finite range of T"
+    nb = n // 32
+    if exact:
+        compare = torch.ones(m, n, dtype=torch.bool)
+        settled = torch.ones(m, nb, dtype=torch.bool)
+        grid = factor * torch.where(ref < 0, ACTQ_SLOPE if act == abi.ACT_LEAKY else 1.0, 1.0)      # every h of a row is a multiple of it
+        assert bool((ref / grid == torch.round(ref / grid)).all())
+        share = float((ref.abs() / grid >= ROUNDS_FROM[dtype]).double().mean())
+        assert share >= 0.20, f"{what}: precondition — only {share:.1%} of the outputs lie where the storage type rounds multiples of the row's grid"
+    else:
+        gap, slack, denom = _slack(_act_formula(t, act, torch.float32, ACTQ_SLOPE), ref, dtype, what)
+        sp = _spacing(ref, dtype)
+        ambiguous = (0.5 * sp - (ref - near).abs() <= slack * denom) & (ref != 0)
+        other = torch.where(ambiguous, near + torch.sign(ref - near) * sp, near)
+        assert _exact_in(other, td)
+        lo, hi = torch.minimum(near.abs(), other.abs()), torch.maximum(near.abs(), other.abs())
+        settled = mx_scale(lo.view(m, nb, 32).amax(-1)) == mx_scale(hi.view(m, nb, 32).amax(-1))
+        compare = settled.repeat_interleave(32, 1) & ~ambiguous
+        share = None
+    left_out = 1.0 - float(compare.double().mean())
+    zero_block = torch.zeros(nb, dtype=torch.bool)
+    zero_block[zero_spans] = True
+    assert bool((near.view(m, nb, 32)[:, zero_block] == 0).all()) and bool(compare.view(m, nb, 32)[:, zero_block].all()), f"{what}: precondition — a zero block is left out"
+    assert left_out <= 0.02, f"{what}: precondition — {left_out:.2%} of the elements are left out"
+    ties = {}
+    q_want, eb_want, _ = q_ref(near, ties)
+    assert bool((eb_want[:, zero_block] == 127).all()) and set(q_want.view(m, nb, 32)[:, zero_block].unique().tolist()) <= {0x00, 0x80}
+    assert ties["down"] > 0 and ties["up"] > 0, f"{what}: precondition — ties in both directions, got {ties}"
+    assert len(eb_want[eb_want != 127].unique()) >= 3, f"{what}: precondition — the scale bytes span fewer than 3 values"
+    print(f"{what} [{NAME[dtype]}]: left out {left_out:.3%}, blocks unsettled {int((~settled).sum())}, rounding share {share if share is None else round(share, 3)}, ties {ties}, "
+          f"scale bytes {int(eb_want[eb_want != 127].min())}..{int(eb_want.max())}")
+
+    R, QW = row_off + m + 3, q_col_off + n + 128          # three spare rows below, one spare 128-byte group to the right
+    lds = (R + 63) // 64 * 64
+    pb = PlanBuilder(lib, dev, dtype)
+    aq, asc, lds_a = pb.quantize(pb.const(A.to(td)), m, k)
+    wq, wsc, lds_w = pb.quantize(pb.const(W.to(td)), n, k)
+    q8 = pb.buf((R, QW), torch.uint8)
+    q8.fill_(Q_SENTINEL)
+    sc = pb.buf((QW // 128, lds), torch.int32)
+    sc.fill_(S_SENTINEL)
+    c = pb.gemm(aq, wq, m, n, k, bias=pb.const(bias.float()), act=act, alpha=alpha, f8=(asc, lds_a, wsc, lds_w, 0, 0), actq=(q8, sc, QW, lds, row_off, q_col_off))
+    assert c is None
+    getattr(pb.ops[-1].u, abi.UNION_FIELD[abi.OP_GEMM]).act_param = ACTQ_SLOPE
+    _run(pb)
+    got_q = q8[row_off:row_off + m, q_col_off:q_col_off + n].cpu()
+    got_eb = _scale_bytes(sc[q_col_off // 128:(q_col_off + n) // 128, row_off:], m)
+    bad = (got_eb != eb_want) & settled
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} scale bytes differ from the reference; first at {tuple(bad.nonzero()[0].tolist())}"
+    bad = (got_q != q_want) & compare
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {int(compare.sum())} compared e4m3 bytes differ from the reference; first at {tuple(bad.nonzero()[0].tolist())}"
+    keep = torch.ones_like(q8, dtype=torch.bool)
+    keep[row_off:row_off + m, q_col_off:q_col_off + n] = False
+    assert bool((q8[keep] == Q_SENTINEL).all()), f"{what}: bytes outside the target window were written"
+    keep = torch.ones_like(sc, dtype=torch.bool)
+    keep[q_col_off // 128:(q_col_off + n) // 128, row_off:row_off + m] = False
+    assert bool((sc[keep] == S_SENTINEL).all()), f"{what}: scale words outside the target window were written"
+    return left_out, share
+
+
+ACTQ_CASES = [dict(m=300, n=256, k=384, row_off=5, q_col_off=128), dict(m=260, n=512, k=128)]
+ACTQ_ACTS = [(abi.ACT_NONE, abi.ACT_NONE), (abi.ACT_RELU, -1), (abi.ACT_LEAKY, -1), (abi.ACT_SILU, abi.ACT_SILU), (abi.ACT_GELU_TANH, abi.ACT_GELU_TANH)]
 
 
 # ---- attention with MX fp8 output ---------------------------------------------------------------------------------------------------------

@@ -226,6 +226,81 @@ def check_batch_selection(lib, dtype, heads, kv, seed=0):
         assert torch.equal(_bits(rig.kc[s].cpu()), _bits(want_k)) and torch.equal(_bits(rig.vc[s].cpu()), _bits(want_v)), f"slot {s}: the cache changed elsewhere than at pos"
 
 
+def _selection_case_per_head(td, pos, heads, kv, g):
+    """paddle_ocr_vl_checks.per_head_selection for ONE row at `pos` (scale 1): query head h plays VARIANTS[h % 3] -> (qkv row, k cache, v cache,
+    per query head the chosen row of ITS kv head's values)"""
+    n = MAX_LEN + GUARD
+    phi, psi, win = pc.per_head_selection(td, n, pos, 1, heads)
+    keys = phi.to(td)[:, None, :].expand(n, kv, D).reshape(n, kv * D)
+    vals = torch.randn(n, kv * D, generator=g).to(td)
+    qkv = torch.cat([psi.to(td).reshape(1, heads * D), keys[pos:pos + 1], vals[pos:pos + 1]], 1)[0]
+    kc, vc = keys.clone(), vals.clone()
+    for c in (kc, vc):
+        cb = c.view(torch.int16)
+        cb[pos:pos + 1] = NAN_BITS                   # the launch's own position is read from its row, not from the cache
+        cb[pos + 2:] = NAN_BITS                      # cache[pos + 1] keeps the key of the future that would outscore the winner
+    want = vals.view(n, kv, D)[win[0], torch.arange(heads) // (heads // kv)].reshape(heads * D)
+    return qkv, kc, vc, want
+
+
+def check_batch_selection_per_head(lib, dtype, heads, kv, seed=0):
+    """check_batch_selection with a winner per query head: every slot's head h returns its own chosen V row bit for bit (slot = blockIdx.z / nz,
+    zc = blockIdx.z - slot * nz and h0 = kvh * gfull + zc * G all have to be right for that), and the ticket words are zero afterwards"""
+    positions = [S + 1, 2 * S + 5, S - 1, S, 0, 1]
+    slots = len(positions)
+    g = torch.Generator().manual_seed(seed + heads)
+    rig = BatchRig(lib, dtype, slots, heads, kv)
+    rig.scale = 1.0
+    rig.pb.ops[-1].u.cstepb.scale = 1.0
+    built = [_selection_case_per_head(rig.td, pos, heads, kv, g) for pos in positions]
+    qkv, kc, vc = (torch.stack([b[i] for b in built]) for i in range(3))
+    rig.load(qkv, kc, vc, make_state(positions), o=_nan_rows(rig.td, slots, heads * D))
+    got = rig.run()
+    assert int(rig.counters().abs().sum()) == 0, f"batched step heads={heads}/{kv}: ticket counters are not zero after the launch"
+    for s, pos in enumerate(positions):
+        wrong = (_bits(got[s]) != _bits(built[s][3])).view(heads, D).any(-1).nonzero().flatten().tolist()
+        assert not wrong, f"batched step heads={heads}/{kv} (G, nz) = {pc.step_layout(heads, kv)} slot {s} pos={pos}: query heads {wrong} differ from their own chosen V row"
+        want_k, want_v = kc[s].clone(), vc[s].clone()
+        want_k[pos] = qkv[s, heads * D:(heads + kv) * D]
+        want_v[pos] = qkv[s, (heads + kv) * D:]
+        assert torch.equal(_bits(rig.kc[s].cpu()), _bits(want_k)) and torch.equal(_bits(rig.vc[s].cpu()), _bits(want_v)), f"slot {s}: the cache changed elsewhere than at pos"
+
+
+def check_batch_padded_strides(lib, dtype, heads=24, kv=2, seed=0):
+    """ld_qkv = w + 24, ld_o = heads * D + 8 in the batched step: every slot's row equals the single step's, the padding of o keeps its sentinel and
+    NaN patterns in the padding of qkv are not read"""
+    pc.assert_layout(heads, kv)
+    positions = SLOT_POSITIONS[3]
+    slots = len(positions)
+    g = torch.Generator().manual_seed(seed + heads)
+    w = (heads + 2 * kv) * D
+    td = TD[dtype]
+    pb = PlanBuilder(lib, _dev(lib), dtype)
+    qkv_b = pb.buf((slots, w + 24), td, zero=True)
+    kc_b = pb.buf((slots, MAX_LEN + GUARD, kv * D), td, zero=True)
+    vc_b = pb.buf((slots, MAX_LEN + GUARD, kv * D), td, zero=True)
+    st_b = pb.buf((abi.SLOT_FIELDS, LANES), torch.int32, zero=True)
+    o_b = pb.buf((slots, heads * D + 8), td, zero=True)
+    pb.causal_step_batch(qkv_b, kc_b, vc_b, st_b, o_b, slots, heads, kv, D, MAX_LEN, D ** -0.5, cache_stride=(MAX_LEN + GUARD) * kv * D,
+                         ld_qkv=w + 24, ld_o=heads * D + 8)
+    single = CausalRig(lib, dtype, 1, heads, kv, MAX_LEN)
+    caches = [_poisoned(td, kv, p, g) for p in positions]
+    kc, vc = torch.stack([c[0] for c in caches]), torch.stack([c[1] for c in caches])
+    qkv = (torch.randn(slots, w, generator=g) * 1.5).to(td)
+    padded = _nan_rows(td, slots, w + 24)
+    padded[:, :w] = qkv
+    sentinel = torch.full((slots, heads * D + 8), 7.0).to(td)
+    qkv_b.copy_(padded); kc_b.copy_(kc); vc_b.copy_(vc); st_b.copy_(make_state(positions)); o_b.copy_(sentinel)
+    pb.build().run()
+    _sync(lib)
+    got = o_b.cpu()
+    assert torch.equal(_bits(got[:, heads * D:]), _bits(sentinel[:, heads * D:])), "the padding of o was written"
+    for s, p in enumerate(positions):
+        o1, k1, v1 = _single(single, qkv[s], kc[s], vc[s], p)
+        assert torch.equal(_bits(got[s, :heads * D]), _bits(o1)), f"padded strides, slot {s}: o differs from the single step"
+        assert torch.equal(_bits(kc_b[s].cpu()), _bits(k1)) and torch.equal(_bits(vc_b[s].cpu()), _bits(v1)), f"padded strides, slot {s}: the cache differs"
+
+
 # ---- greedy batch --------------------------------------------------------------------------------------------------------------------------
 BATCH_VOCABS = [1, 255, 4097, 103424]
 OUT_GUARD = 4
@@ -310,6 +385,27 @@ def check_greedy_batch_damaged_state(lib):
     assert guard.tolist() == [-99] * (2 * OUT_GUARD)
     assert st[:, 0].tolist() == [5, -1, 1, 0, 1] and st[:, 1].tolist() == [6, max_new, 1, 0, 2] and st[:, 2].tolist() == [8, 2, 0, 7, 4]
     assert rows.tolist() == [[-7] * 4, [-7] * 4, [-7, 7, -7, -7]]
+
+
+def check_greedy_batch_65_chunks(lib):
+    """paddle_ocr_vl_checks.greedy_65_cases in slot 1 of 2 (record run 2 * 1 * 65 on) with ld_logits = vocab + 3; slot 0 holds the next case.
+    Three launches; the expected tokens come from the cases, not from the single op"""
+    cases = pc.greedy_65_cases()
+    vocab, max_new = pc.VOCAB_65, 4
+    assert pc.greedy_chunks(vocab) == 65
+    for k in range(len(cases)):
+        pair = [cases[(k + 1) % len(cases)], cases[k]]
+        logits = torch.full((2, vocab + 3), 50.0)              # the padding behind each row would win if it were read
+        for s, (_, lg, _) in enumerate(pair):
+            logits[s, :vocab] = lg
+        state = make_state([10, 20], n_out=[1, 2], token=[-1, -1], rope=[40, 43])
+        out = torch.full((2, max_new), -7, dtype=torch.int32)
+        st, rows, guard = _greedy_batch(lib, logits, state, out, vocab, max_new, [], 1)
+        assert guard.tolist() == [-99] * (2 * OUT_GUARD) and torch.equal(st[:, 2:], state[:, 2:])
+        for s, (name, _, want) in enumerate(pair):
+            n = 1 + s
+            assert st[:, s].tolist() == [10 + 10 * s + 1, n + 1, 0, want, 40 + 3 * s + 1], f"65 chunks, slot {s}, {name}: state {st[:, s].tolist()}, expected token {want}"
+            assert rows[s].tolist() == [-7] * n + [want] + [-7] * (max_new - n - 1)
 
 
 def check_greedy_batch_run(lib):

@@ -10,7 +10,10 @@ a sum of rank-one terms, each a (function of i) x (function of j) held in a few 
 entry is exact in bf16 and f16.
 Causal attention, random: against fp32 torch (explicit causal mask, repeat_interleave of the kv heads) on the same 16-bit inputs, with the
 bound of manga_ocr_checks.check_decode_attn_random: half a spacing of T at the reference (the one rounding) plus the fp32 softmax's own error
-over at most 300 keys, 300 * 2^-23 of the largest value (the largest case here has 133 + 131 = 264 keys)."""
+over at most 300 keys, 300 * 2^-23 of the largest value (the largest case here has 133 + 131 = 264 keys).
+Head layouts: HEADS gives one chunk of G = 1, 2 or 8 query heads per kv head; STEP_LAYOUTS adds G = 4 and several chunks per kv head for every
+G (`step_layout` restates the launcher's rule), and `check_causal_selection_per_head` gives every query head a winner of its own, so that a
+result which lands at another head of its group is a wrong V row."""
 import ctypes as C
 
 import pytest
@@ -27,6 +30,8 @@ TQ, TK, S = abi.CAUSAL_TQ, abi.CAUSAL_TK, abi.CAUSAL_S
 ROWS = [1, 2, TQ - 1, TQ, TQ + 1, 2 * TQ + 3]
 POSITIONS = [0, 1, TK - 1, TK, TK + 1, 2 * S + 5]
 HEADS = [(2, 2), (4, 2), (16, 2)]
+# head layouts of the step kernels that HEADS (G = 1, 2, 8 with one chunk of query heads per kv head) does not reach; see `step_layout`
+STEP_LAYOUTS = [(8, 2), (24, 2), (32, 2), (6, 2), (12, 2), (12, 3)]
 GUARD = 4                             # cache rows behind max_len that nobody may touch
 NAN_BITS = 0x7FC1                     # a NaN bit pattern of both 16-bit types
 MTX_ERR_UNSUPPORTED = -3                 # include/mtx_hip.h
@@ -39,19 +44,20 @@ def _bits(t):
 class CausalRig:
     """one recorded MTX_OP_CAUSAL_ATTN over caches with a guard band; `run` launches it"""
 
-    def __init__(self, lib, dtype, rows, heads, kv_heads, max_len, d=D, scale=None):
+    def __init__(self, lib, dtype, rows, heads, kv_heads, max_len, d=D, scale=None, pad_qkv=0, pad_o=0):
         self.lib, self.dev, self.td = lib, _dev(lib), TD[dtype]
         self.rows, self.heads, self.kv, self.max_len = rows, heads, kv_heads, max_len
         self.w = (heads + 2 * kv_heads) * D
+        self.ld_qkv, self.ld_o = self.w + pad_qkv, heads * D + pad_o          # row strides; the padding columns belong to the test
         pb = PlanBuilder(lib, self.dev, dtype)
-        self.qkv = pb.buf((rows, self.w), self.td, zero=True)
+        self.qkv = pb.buf((rows, self.ld_qkv), self.td, zero=True)
         self.kc = pb.buf((max_len + GUARD, kv_heads * D), self.td, zero=True)
         self.vc = pb.buf((max_len + GUARD, kv_heads * D), self.td, zero=True)
         self.pos = pb.buf((1,), torch.int32, zero=True)
-        self.o = pb.buf((rows, heads * D), self.td, zero=True)
+        self.o = pb.buf((rows, self.ld_o), self.td, zero=True)
         self.scale = D ** -0.5 if scale is None else scale
         pb.causal_attention(self.qkv, self.kc, self.vc, self.pos, self.o, rows, heads, kv_heads, d, max_len, self.scale,
-                            ld_qkv=self.w, ld_o=heads * D)
+                            ld_qkv=self.ld_qkv, ld_o=self.ld_o)
         self.pb, self.plan = pb, None
 
     def run(self, qkv=None, kc=None, vc=None, pos=None):
@@ -239,18 +245,143 @@ def check_step_is_deterministic(lib, dtype, pos, heads, kv, repeats=5):
         assert torch.equal(_bits(rig.run()), first)
 
 
-def check_gqa_mapping(lib, dtype, rows):
-    """(4, 2) heads, value heads hold distinct constants: query heads 0, 1 read kv head 0 and heads 2, 3 read kv head 1"""
-    heads, kv, pos = 4, 2, 5
+def check_gqa_mapping(lib, dtype, rows, heads=4, kv=2):
+    """value head v holds the constant v + 1: query head h returns (h // (heads / kv)) + 1 — at (4, 2) query heads 0, 1 read kv head 0 and
+    heads 2, 3 read kv head 1"""
+    pos = 5
     g = torch.Generator().manual_seed(rows)
     rig = CausalRig(lib, dtype, rows, heads, kv, pos + rows)
     kc = torch.randn(pos + rows + GUARD, kv * D, generator=g).to(rig.td)
-    vc = torch.cat([torch.full((pos + rows + GUARD, D), 1.0), torch.full((pos + rows + GUARD, D), 2.0)], 1).to(rig.td)
+    vc = torch.cat([torch.full((pos + rows + GUARD, D), v + 1.0) for v in range(kv)], 1).to(rig.td)
     qkv = torch.randn(rows, rig.w, generator=g).to(rig.td)
     qkv[:, (heads + kv) * D:] = vc[:rows]
     got = rig.run(qkv, kc, vc, pos).float().view(rows, heads, D)
-    want = torch.tensor([1.0, 1.0, 2.0, 2.0])[None, :, None].expand(rows, heads, D)
-    assert torch.equal(got, want), f"GQA mapping: head means {got.mean((0, 2)).tolist()}"
+    want = (torch.arange(heads) // (heads // kv) + 1.0)[None, :, None].expand(rows, heads, D)
+    if (heads, kv) == (4, 2):
+        assert torch.equal(want[0, :, 0], torch.tensor([1.0, 1.0, 2.0, 2.0]))
+    assert torch.equal(got, want), f"GQA mapping heads={heads}/{kv}: head means {got.mean((0, 2)).tolist()}"
+
+
+# ---- head layouts of the step kernels ----------------------------------------------------------------------------------------------------------
+def step_layout(heads, kv):
+    """causal_attn_launch's rule restated: (G, nz) = (query heads that share one pass over the keys, chunks of G heads per kv head).  The
+    step runs causal_step_kernel<T, G> on a grid (splits, kv, nz); the batched step causal_step_batch_kernel<T, G> on (splits, kv, slots * nz)"""
+    assert heads % kv == 0
+    gfull = heads // kv
+    G = 8 if gfull % 8 == 0 else (4 if gfull % 4 == 0 else (2 if gfull % 2 == 0 else 1))
+    return G, gfull // G
+
+
+# the instantiation every layout-parametrised case is meant for: causal_step_kernel<T, G> / causal_step_batch_kernel<T, G> with nz chunks per kv head
+LAYOUT_OF = {(8, 2): (4, 1), (24, 2): (4, 3), (32, 2): (8, 2), (6, 2): (1, 3), (12, 2): (2, 3), (12, 3): (4, 1), (16, 2): (8, 1)}
+assert [LAYOUT_OF[hk] for hk in STEP_LAYOUTS] == [(4, 1), (4, 3), (8, 2), (1, 3), (2, 3), (4, 1)]
+
+
+def assert_layout(heads, kv):
+    """the case runs the (G, nz) it is meant for; -> (G, nz)"""
+    assert step_layout(heads, kv) == LAYOUT_OF[(heads, kv)], f"heads {heads}/{kv} runs (G, nz) = {step_layout(heads, kv)}, the case is meant for {LAYOUT_OF[(heads, kv)]}"
+    return LAYOUT_OF[(heads, kv)]
+
+
+assert all(step_layout(h, k)[1] == 1 and step_layout(h, k)[0] != 4 for h, k in HEADS), "what HEADS leaves open"
+assert all(any(step_layout(h, k) == (G, nz) and nz > 1 for h, k in STEP_LAYOUTS for nz in (2, 3)) for G in (1, 2, 4, 8)), \
+    "every G needs a layout with more than one chunk of query heads per kv head"
+assert any(k > 2 for _, k in STEP_LAYOUTS)
+STEP_POSITIONS = [0, TK + 1, 2 * S + 5]
+VARIANTS = ("own", "pos", "zero")
+
+
+def per_head_selection(td, n, pos, rows, heads):
+    """check_causal_selection's construction with a winner PER QUERY HEAD: head h plays VARIANTS[h % 3].  The key features of the two fixed
+    winners lie side by side (columns 4-6 for w = pos, 7-9 for w = 0) and a head holds zeros in the columns of the variant it does not play, so
+    the keys are the same for every kv head while the heads of one group expect different rows.
+    -> (phi [n, D], psi [rows, heads, D], win [rows, heads]), float64 / int64; asserts the premise per head from its own score matrix"""
+    j = torch.arange(n)
+    i_abs = pos + torch.arange(rows)
+    phi = torch.zeros(n, D, dtype=torch.float64)
+    phi[:, 0], phi[:, 1] = (j // 16).double(), (j % 16).double()
+    phi[:, 2] = 1.0
+    phi[:, 3] = 1.0
+    for c, w in ((4, pos), (7, 0)):
+        phi[:, c] = (j != w).double()
+        phi[:, c + 1] = (j == w).double()
+        phi[:, c + 2] = (j == w).double()
+    psi = torch.zeros(rows, heads, D, dtype=torch.float64)
+    hi, lo = _b16(i_abs)
+    psi[:, :, 0], psi[:, :, 1] = 128.0 * 16, 128.0
+    psi[:, :, 2], psi[:, :, 3] = (-128.0 * hi)[:, None], (-128.0 * lo)[:, None]
+    win = torch.zeros(rows, heads, dtype=torch.long)
+    for h in range(heads):
+        variant = VARIANTS[h % 3]
+        if variant == "own":
+            win[:, h] = i_abs
+            continue
+        c, w = (4, pos) if variant == "pos" else (7, 0)
+        hi, lo = _b16(i_abs - w)
+        psi[:, h, c], psi[:, h, c + 1], psi[:, h, c + 2] = -120.0, 128.0 * hi, 128.0 * lo
+        win[:, h] = w
+    for t in (phi, psi):
+        assert torch.equal(t, t.to(td).double()), "the test's own premise: every feature is exact in the storage type"
+    for h in range(heads):
+        M = psi[:, h] @ phi.t()
+        for i in range(rows):
+            vis = M[i, :pos + i + 1]
+            assert vis[win[i, h]] == 0 and int((vis > -120).sum()) == 1 and M[i, pos + i + 1] == (128.0 if h % 3 == 0 else 8.0)
+    if pos > 0 and heads >= 3:                       # (in the first row "own" and "pos" name the same key; "zero" never does)
+        assert win[0, 1] != win[0, 2] and win[-1, 0] != win[-1, 2], "neighbouring heads must expect different rows"
+    return phi, psi, win
+
+
+def check_causal_selection_per_head(lib, dtype, rows, pos, heads, kv, seed=0):
+    """query head h must return, bit for bit, row win_h(i) of the values of kv head h // (heads / kv): with a different winner per head, a
+    result that lands at another head of its group (m[g], l[g], acc[g], part[wave][g], the record of head h0 + g) is a wrong V row"""
+    max_len = pos + rows + 2
+    n = max_len + GUARD
+    g = torch.Generator().manual_seed(seed + rows * 31 + pos * 7 + heads)
+    rig = CausalRig(lib, dtype, rows, heads, kv, max_len, scale=1.0)
+    td = rig.td
+    phi, psi, win = per_head_selection(td, n, pos, rows, heads)
+    keys = phi.to(td)[:, None, :].expand(n, kv, D).reshape(n, kv * D)
+    vals = torch.randn(n, kv * D, generator=g).to(td)
+    qkv = torch.cat([psi.to(td).reshape(rows, heads * D), keys[pos:pos + rows], vals[pos:pos + rows]], 1)
+    kc, vc = keys.clone(), vals.clone()
+    for c in (kc, vc):
+        cb = c.view(torch.int16)
+        cb[pos:pos + rows] = NAN_BITS                # the launch's own positions are read from its rows, not from the cache
+        cb[pos + rows + 1:] = NAN_BITS               # cache[pos + rows] keeps the key of the future that would outscore the winner
+    got = rig.run(qkv, kc, vc, pos)
+    kvh = torch.arange(heads) // (heads // kv)
+    want = vals.view(n, kv, D)[win, kvh[None, :].expand(rows, heads)].reshape(rows, heads * D)
+    if pos > 0 and heads // kv >= 3:
+        assert not torch.equal(_bits(want.view(rows, heads, D)[:, 1]), _bits(want.view(rows, heads, D)[:, 2])), "heads 1 and 2 share a kv head and must expect different rows"
+    wrong = (_bits(got) != _bits(want)).view(rows, heads, D).any(-1).any(0).nonzero().flatten().tolist()
+    assert not wrong, (f"causal attention rows={rows} pos={pos} heads={heads}/{kv} (G, nz) = {step_layout(heads, kv)}: query heads {wrong} differ "
+                       f"from their own chosen V row")
+    _check_caches(rig, kc, vc, qkv, pos, f"causal attention (selection per head) rows={rows} pos={pos}")
+
+
+def check_causal_padded_strides(lib, dtype, rows, heads=24, kv=2, pos=TK + 1, seed=0):
+    """ld_qkv = w + 24 and ld_o = heads * D + 8 (both multiples of 8, as the launcher asks): the bytes of the unpadded case, NaN patterns in
+    the padding of qkv are not read, the padding of o keeps its sentinel"""
+    assert_layout(heads, kv)                       # (24, 2): G = 4 in three chunks per kv head for the step, h / G in the prefill
+    max_len = pos + rows + 3
+    g = torch.Generator().manual_seed(seed + rows)
+    plain = CausalRig(lib, dtype, rows, heads, kv, max_len)
+    wide = CausalRig(lib, dtype, rows, heads, kv, max_len, pad_qkv=24, pad_o=8)
+    assert (wide.ld_qkv, wide.ld_o) == (plain.w + 24, heads * D + 8) and wide.ld_qkv % 8 == 0 and wide.ld_o % 8 == 0
+    kc, vc = _poisoned_caches(plain, pos, g)
+    qkv = (torch.randn(rows, plain.w, generator=g) * 1.5).to(plain.td)
+    want = plain.run(qkv, kc, vc, pos)
+    assert bool(torch.isfinite(want.float()).all())
+    padded = torch.full((rows, wide.ld_qkv), NAN_BITS, dtype=torch.int16).view(plain.td)
+    padded[:, :plain.w] = qkv
+    sentinel = torch.full((rows, wide.ld_o), 7.0).to(plain.td)
+    wide.o.copy_(sentinel)
+    got = wide.run(padded, kc, vc, pos)
+    what = f"causal attention with padded strides rows={rows} heads={heads}/{kv}"
+    assert torch.equal(_bits(got[:, :heads * D]), _bits(want)), f"{what}: differs from the unpadded case"
+    assert torch.equal(_bits(got[:, heads * D:]), _bits(sentinel[:, heads * D:])), f"{what}: the padding of o was written"
+    assert torch.equal(_bits(wide.kc.cpu()), _bits(plain.kc.cpu())) and torch.equal(_bits(wide.vc.cpu()), _bits(plain.vc.cpu())), f"{what}: the caches differ"
 
 
 def check_causal_refusals(lib):
@@ -345,6 +476,57 @@ def check_greedy_run_of_steps(lib):
     pb.build().run()
     _sync(lib)
     assert st.cpu().tolist() == [34, 4, 1, 2] and ot.cpu().tolist() == [5, 6, 7, 2] + [-7] * 12
+
+
+def greedy_chunks(vocab):
+    """greedy_launch's rule restated: chunk records per row; the folding wave reads record c in lane c % 64 on trip c // 64"""
+    return (vocab + abi.GREEDY_CHUNK - 1) // abi.GREEDY_CHUNK
+
+
+VOCAB_65 = 64 * abi.GREEDY_CHUNK + 1
+assert greedy_chunks(VOCAB_65) == 65 and max(greedy_chunks(v) for v in VOCABS) <= 64, "VOCABS stays within one trip of the folding wave"
+
+
+def greedy_65_cases(seed=0):
+    """[(name, logits [VOCAB_65], expected token)]: record 64 is the one a lane reads on its second trip.  The expected token comes from the
+    stated rule alone (largest value, lowest index among equals, a NaN never wins) and is asserted against torch here"""
+    C_ = abi.GREEDY_CHUNK
+    base = torch.randn(VOCAB_65, generator=torch.Generator().manual_seed(seed)).clamp_(-4.0, 4.0)
+    alone = base.clone(); alone[64 * C_] = 9.0
+    tie = base.clone(); tie[5] = 9.0; tie[64 * C_] = 9.0
+    nan = base.clone(); nan[63 * C_ + 7] = 9.0; nan[64 * C_] = float("nan")
+    cases = [("the maximum alone in chunk 64", alone, 64 * C_), ("equal maxima in chunks 0 and 64", tie, 5), ("a maximum in chunk 63, a NaN in chunk 64", nan, 63 * C_ + 7)]
+    for name, lg, want in cases:
+        clean = torch.nan_to_num(lg, nan=float("-inf"))
+        assert float(clean.max()) == 9.0 and int((clean == 9.0).nonzero()[0]) == want, name
+    assert alone[:64 * C_].max() < 9.0 and 64 * C_ // C_ == 64 and (63 * C_ + 7) // C_ == 63 and 5 // C_ == 0
+    return cases
+
+
+def check_greedy_65_chunks(lib):
+    """three launches of the single op at 65 chunk records (greedy_final_kernel's loop takes a second trip in lane 0)"""
+    for name, lg, want in greedy_65_cases():
+        st, out = _greedy(lib, lg, [10, 1, 0, -1], 4, [], 1)
+        assert st == [11, 2, 0, want] and out == [-7, want, -7, -7], f"65 chunks, {name}: state {st}, expected token {want}"
+
+
+def check_greedy_damaged_state(lib):
+    """n_out = -1 and n_out = max_new with done = 0: done = 1, every other state word and all of `out` unchanged"""
+    vocab, max_new = 300, 6
+    lg = torch.zeros(vocab); lg[41] = 1.0
+    before = torch.tensor([11, 12, 13, -7, -7, -7])
+    for n_out in (-1, max_new, max_new + 3):
+        st, out = _greedy(lib, lg, [17, n_out, 0, 5], max_new, [3], 1, out=before)
+        assert st == [17, n_out, 1, 5] and out == before.tolist(), f"damaged state n_out={n_out}: state {st} out {out}"
+
+
+def check_greedy_all_nan(lib, vocab):
+    """all-NaN logits: no record ever replaces the start value, the token is 0 and the state advances as for any other token"""
+    lg = torch.full((vocab,), float("nan"))
+    st, out = _greedy(lib, lg, [17, 2, 0, 5], 6, [3], 1, out=torch.tensor([11, 12, -7, -7, -7, -7]))
+    assert st == [18, 3, 0, 0] and out == [11, 12, 0, -7, -7, -7], f"all NaN, vocab {vocab}: state {st} out {out}"
+    st, out = _greedy(lib, lg, [17, 2, 0, 5], 6, [0], 1)          # and token 0 is an end-of-sequence token like any other
+    assert st == [18, 3, 1, 0]
 
 
 # ---- MTX_EW_QK_ROPE at head width 72 ---------------------------------------------------------------------------------------------------------

@@ -96,3 +96,18 @@ def test_published_widths_logits_equal_the_single_step(hip_lib):
 
 def test_published_widths_generate_many_equals_generate(hip_lib):
     print(f"generated lengths {bc.check_published_generate_many(hip_lib)}")
+
+
+# ---- the wide linear against float64 with the contract's rounding points, for every (RT, NW) it is built for ------------------------------------
+CONTRACT_K = (lambda n: 520)
+CONTRACT_TYPES = [(abi.BF16, False), (abi.F16, False), (abi.F16, True), (abi.F32, True)]
+
+
+@pytest.mark.parametrize("dtype,out_f32", CONTRACT_TYPES)
+@pytest.mark.parametrize("n,nw", [(257, 1), (2050, 2), (4100, 4)])
+@pytest.mark.parametrize("rows,rt", [(7, 8), (9, 16), (17, 32)])
+def test_wide_row_linear_contract_exact(hip_lib, dtype, out_f32, n, nw, rows, rt):
+    """rowlin_wide_kernel<T, RT, NW> held to float64, not to rowlin_kernel"""
+    import manga_ocr_checks as mc
+    share = mc.check_rowlin_contract_exact(hip_lib, dtype, rows, n, CONTRACT_K(n), True, out_f32, (rt, nw))
+    print(f"wide row linear contract {rows}x{n} dtype {dtype}: rounding share {share}")

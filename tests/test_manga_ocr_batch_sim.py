@@ -93,3 +93,18 @@ def test_generate_many_refused_items(emu_lib):
 
 def test_driver_reads_a_page_together(emu_lib, tmp_path, monkeypatch):
     bc.check_driver(emu_lib, tmp_path, monkeypatch)
+
+
+# ---- the wide linear against float64 with the contract's rounding points, for every (RT, NW) it is built for ------------------------------------
+CONTRACT_K = (lambda n: 136 if n == 4100 else 520)          # the simulator tier shortens K at the widest N
+CONTRACT_TYPES = [(abi.BF16, False), (abi.F16, False), (abi.F16, True), (abi.F32, True)]
+
+
+@pytest.mark.parametrize("dtype,out_f32", CONTRACT_TYPES)
+@pytest.mark.parametrize("n,nw", [(257, 1), (2050, 2), (4100, 4)])
+@pytest.mark.parametrize("rows,rt", [(7, 8), (9, 16), (17, 32)])
+def test_wide_row_linear_contract_exact(emu_lib, dtype, out_f32, n, nw, rows, rt):
+    """rowlin_wide_kernel<T, RT, NW> held to float64, not to rowlin_kernel"""
+    import manga_ocr_checks as mc
+    share = mc.check_rowlin_contract_exact(emu_lib, dtype, rows, n, CONTRACT_K(n), True, out_f32, (rt, nw))
+    print(f"wide row linear contract {rows}x{n} dtype {dtype}: rounding share {share}")

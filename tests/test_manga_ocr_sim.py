@@ -8,7 +8,7 @@ from mangatranslator_amd.hip import abi
 
 DTYPES = [abi.BF16, abi.F16]
 KERNEL_DTYPES = DTYPES + [abi.F32]          # the two decode kernels also come in fp32 (the recogniser's storage "f32")
-ROWLIN_SHAPES = [(768, 768), (6144, 768), (136, 72)]
+ROWLIN_SHAPES = [(768, 768), (6144, 768), (136, 72), (2050, 520)]          # NW = 1, 4, 1, 2 (manga_ocr_checks.rowlin_tiling)
 
 
 @pytest.mark.parametrize("dtype", KERNEL_DTYPES)
@@ -130,3 +130,39 @@ def test_nothing_staged_is_a_model_error(tmp_path, monkeypatch):
         mgr.get_manga_ocr()
     from PIL import Image
     assert od.extract_text_with_manga_ocr([Image.new("RGB", (8, 8))]) == ["[OCR FAILED]"]
+
+
+# ---- routes the cases above leave open: rows 5..8 and other head counts in the attention, padded strides, the skinny linear against float64 ----
+@pytest.mark.parametrize("dtype", KERNEL_DTYPES)
+@pytest.mark.parametrize("heads", [1, 3])
+@pytest.mark.parametrize("rows", [5, 8])
+def test_decode_attention_exact_eight_slots(emu_lib, dtype, heads, rows):
+    """decode_attn_kernel<T> on a grid (heads, rows) with blockIdx.y up to 7 and heads != 2"""
+    for n_keys in (2, 64):
+        mc.check_decode_attn_exact(emu_lib, dtype, n_keys, rows=rows, slots=8, heads=heads)
+
+
+@pytest.mark.parametrize("dtype", KERNEL_DTYPES)
+@pytest.mark.parametrize("heads", [1, 3])
+@pytest.mark.parametrize("rows", [5, 8])
+def test_decode_attention_random_eight_slots(emu_lib, dtype, heads, rows):
+    worst = max(mc.check_decode_attn_random(emu_lib, dtype, rows, pos, slots=8, heads=heads) for pos in (0, 32, 33, 299))
+    print(f"decode attention rows {rows} heads {heads} dtype {dtype}: worst error {worst:.3f} x bound")
+
+
+@pytest.mark.parametrize("dtype", KERNEL_DTYPES)
+def test_decode_attention_padded_strides(emu_lib, dtype):
+    mc.check_decode_attn_padded_strides(emu_lib, dtype)
+
+
+CONTRACT_K = (lambda n: 136 if n == 4100 else 520)          # the simulator tier shortens K at the widest N
+CONTRACT_TYPES = [(abi.BF16, False), (abi.F16, False), (abi.F16, True), (abi.F32, True)]
+
+
+@pytest.mark.parametrize("dtype,out_f32", CONTRACT_TYPES)
+@pytest.mark.parametrize("n,nw", [(257, 1), (2050, 2), (4100, 4)])
+@pytest.mark.parametrize("rows,rt", [(1, 1), (3, 4), (5, 8)])
+def test_row_linear_contract_exact(emu_lib, dtype, out_f32, n, nw, rows, rt):
+    """rowlin_kernel<T, RT, NW> for every (RT, NW), against float64 with the contract's rounding points"""
+    share = mc.check_rowlin_contract_exact(emu_lib, dtype, rows, n, CONTRACT_K(n), False, out_f32, (rt, nw))
+    print(f"row linear contract {rows}x{n} dtype {dtype}: rounding share {share}")

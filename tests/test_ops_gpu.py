@@ -572,3 +572,11 @@ def test_channel_attention_exact(hip_lib, dtype, cfg):
 @pytest.mark.parametrize("cfg", fc.CA_POOLED_CASES, ids=_id)
 def test_channel_attention_pooled_exact(hip_lib, cfg):
     fc.check_ca_pooled_exact(hip_lib, **cfg)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
+@pytest.mark.parametrize("act,instantiation", pc.ACTQ_ACTS)
+def test_gemm_fp8_activation_epilogue_against_the_reference(hip_lib, dtype, act, instantiation):
+    """gemm256_f8_actq_kernel<T, ACT> against Q_ref(round_T(act(alpha acc + bias))); RELU and LEAKY reach ACT = -1"""
+    for case in pc.ACTQ_CASES:
+        pc.check_gemm_actq_exact(hip_lib, dtype, act=act, instantiation=instantiation, **case)

@@ -3,6 +3,7 @@ library (checks in paddle_batch_checks.py)."""
 import pytest
 
 import paddle_batch_checks as bc
+import paddle_ocr_vl_checks as pc
 from mangatranslator_amd.hip import abi
 
 pytestmark = pytest.mark.gpu
@@ -73,3 +74,44 @@ def test_driver_reads_a_page_together(hip_lib, tmp_path, monkeypatch):
 
 def test_generate_many_at_the_published_widths(hip_lib):
     bc.check_published_widths(hip_lib)
+
+
+# ---- head layouts that HEADS does not reach: G = 4, and nz > 1 where slot = blockIdx.z / nz differs from blockIdx.z ------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+def test_step_layouts_batched_equals_single(hip_lib, dtype, heads, kv):
+    """causal_step_batch_kernel<T, G> at (G, nz) = step_layout(heads, kv), three slots; the counter check covers the ticket words kvh * nz + z"""
+    pc.assert_layout(heads, kv)
+    _, nz = pc.step_layout(heads, kv)
+    assert kv * nz <= heads, "every ticket word lies among the words `counters()` reads"
+    bc.check_batch_equals_single(hip_lib, dtype, heads, kv, 3)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+def test_step_layouts_slots_that_sit_out(hip_lib, dtype, heads, kv):
+    pc.assert_layout(heads, kv)
+    bc.check_sitting_out(hip_lib, dtype, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+def test_step_layouts_batched_selection(hip_lib, dtype, heads, kv):
+    pc.assert_layout(heads, kv)
+    bc.check_batch_selection(hip_lib, dtype, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS + [(16, 2)])
+def test_batched_step_selects_exactly_per_head(hip_lib, dtype, heads, kv):
+    pc.assert_layout(heads, kv)
+    bc.check_batch_selection_per_head(hip_lib, dtype, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_batched_step_padded_strides(hip_lib, dtype):
+    bc.check_batch_padded_strides(hip_lib, dtype)
+
+
+def test_greedy_batch_65_chunks(hip_lib):
+    bc.check_greedy_batch_65_chunks(hip_lib)

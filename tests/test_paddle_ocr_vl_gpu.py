@@ -165,3 +165,63 @@ def test_published_widths(hip_lib):
     record("paddle_ocr_vl_published_f16", max=mx, rms=rms)
     print(f"published widths f16: max {mx:.5f} rms {rms:.5f}")
     assert mx <= 2 * GPU_REAL[abi.F16][0] and rms <= 2 * GPU_REAL[abi.F16][1]
+
+
+# ---- head layouts of the step kernels that HEADS does not reach (G = 4; more than one chunk of query heads per kv head), strides, greedy edges ----
+LAYOUTS_AND_16 = pc.STEP_LAYOUTS + [(16, 2)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+def test_step_layouts_random(hip_lib, dtype, heads, kv):
+    """causal_step_kernel<T, G> at (G, nz) = step_layout(heads, kv) and the prefill's h / G, against the fp32 reference under the bound of
+    test_causal_attention_random (derived for up to 300 keys; the largest case here has 2 S + 6 = 134)"""
+    pc.assert_layout(heads, kv)
+    assert max(pc.STEP_POSITIONS) + 1 <= 300 and pc.TK + 1 + pc.TQ + 3 <= 300
+    worst = max(pc.check_causal_random(hip_lib, dtype, 1, pos, heads, kv) for pos in pc.STEP_POSITIONS)
+    worst = max(worst, pc.check_causal_random(hip_lib, dtype, pc.TQ + 3, pc.TK + 1, heads, kv))
+    print(f"step layouts heads {heads}/{kv} (G, nz) {pc.step_layout(heads, kv)} dtype {dtype}: worst error {worst:.3f} x bound")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", LAYOUTS_AND_16)
+@pytest.mark.parametrize("rows", [1, pc.TQ + 1])
+def test_causal_attention_selects_exactly_per_head(hip_lib, dtype, heads, kv, rows):
+    pc.assert_layout(heads, kv)
+    for pos in pc.STEP_POSITIONS:
+        pc.check_causal_selection_per_head(hip_lib, dtype, rows, pos, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", [(32, 2), (24, 2)])
+def test_step_layouts_deterministic(hip_lib, dtype, heads, kv):
+    pc.assert_layout(heads, kv)
+    assert pc.LAYOUT_OF[(heads, kv)][1] > 1
+    pc.check_step_is_deterministic(hip_lib, dtype, 4 * pc.S + 9, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+@pytest.mark.parametrize("rows", [1, 3])
+def test_gqa_mapping_step_layouts(hip_lib, dtype, heads, kv, rows):
+    pc.assert_layout(heads, kv)
+    pc.check_gqa_mapping(hip_lib, dtype, rows, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rows", [1, pc.TQ + 1])
+def test_causal_attention_padded_strides(hip_lib, dtype, rows):
+    pc.check_causal_padded_strides(hip_lib, dtype, rows)
+
+
+def test_greedy_pick_65_chunks(hip_lib):
+    pc.check_greedy_65_chunks(hip_lib)
+
+
+def test_greedy_pick_damaged_state(hip_lib):
+    pc.check_greedy_damaged_state(hip_lib)
+
+
+@pytest.mark.parametrize("vocab", [1, 300, 4097])
+def test_greedy_pick_all_nan(hip_lib, vocab):
+    pc.check_greedy_all_nan(hip_lib, vocab)

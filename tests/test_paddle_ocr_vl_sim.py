@@ -148,3 +148,63 @@ def test_model_refusals(emu_lib):
 
 def test_end_to_end_from_a_staged_directory(emu_lib, tmp_path, monkeypatch):
     pc.check_end_to_end(emu_lib, tmp_path, monkeypatch)
+
+
+# ---- head layouts of the step kernels that HEADS does not reach (G = 4; more than one chunk of query heads per kv head), strides, greedy edges ----
+LAYOUTS_AND_16 = pc.STEP_LAYOUTS + [(16, 2)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+def test_step_layouts_random(emu_lib, dtype, heads, kv):
+    """causal_step_kernel<T, G> at (G, nz) = step_layout(heads, kv) and the prefill's h / G, against the fp32 reference under the bound of
+    test_causal_attention_random (derived for up to 300 keys; the largest case here has 2 S + 6 = 134)"""
+    pc.assert_layout(heads, kv)
+    assert max(pc.STEP_POSITIONS) + 1 <= 300 and pc.TK + 1 + pc.TQ + 3 <= 300
+    worst = max(pc.check_causal_random(emu_lib, dtype, 1, pos, heads, kv) for pos in pc.STEP_POSITIONS)
+    worst = max(worst, pc.check_causal_random(emu_lib, dtype, pc.TQ + 3, pc.TK + 1, heads, kv))
+    print(f"step layouts heads {heads}/{kv} (G, nz) {pc.step_layout(heads, kv)} dtype {dtype}: worst error {worst:.3f} x bound")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", LAYOUTS_AND_16)
+@pytest.mark.parametrize("rows", [1, pc.TQ + 1])
+def test_causal_attention_selects_exactly_per_head(emu_lib, dtype, heads, kv, rows):
+    pc.assert_layout(heads, kv)
+    for pos in pc.STEP_POSITIONS:
+        pc.check_causal_selection_per_head(emu_lib, dtype, rows, pos, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", [(32, 2), (24, 2)])
+def test_step_layouts_deterministic(emu_lib, dtype, heads, kv):
+    pc.assert_layout(heads, kv)
+    assert pc.LAYOUT_OF[(heads, kv)][1] > 1
+    pc.check_step_is_deterministic(emu_lib, dtype, 4 * pc.S + 9, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("heads,kv", pc.STEP_LAYOUTS)
+@pytest.mark.parametrize("rows", [1, 3])
+def test_gqa_mapping_step_layouts(emu_lib, dtype, heads, kv, rows):
+    pc.assert_layout(heads, kv)
+    pc.check_gqa_mapping(emu_lib, dtype, rows, heads, kv)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rows", [1, pc.TQ + 1])
+def test_causal_attention_padded_strides(emu_lib, dtype, rows):
+    pc.check_causal_padded_strides(emu_lib, dtype, rows)
+
+
+def test_greedy_pick_65_chunks(emu_lib):
+    pc.check_greedy_65_chunks(emu_lib)
+
+
+def test_greedy_pick_damaged_state(emu_lib):
+    pc.check_greedy_damaged_state(emu_lib)
+
+
+@pytest.mark.parametrize("vocab", [1, 300, 4097])
+def test_greedy_pick_all_nan(emu_lib, vocab):
+    pc.check_greedy_all_nan(emu_lib, vocab)

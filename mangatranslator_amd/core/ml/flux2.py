@@ -78,9 +78,12 @@ FP8_ALL = ("qkv", "out", "ff_in", "ff_out", "single_in", "single_out")
 
 
 class Flux2DiTHip:
-    def __init__(self, provider, cfg: dict, device, lib=None, fp8=False, fused_quant=True, glu_epilogue=True, attn_q8=True, attn_qk_f8=True, attn_pv_f8=True):
+    def __init__(self, provider, cfg: dict, device, lib=None, fp8=False, fused_quant=True, glu_epilogue=True, attn_q8=True, attn_qk_f8=True, attn_pv_f8=True,
+                 text_stream_on_side_lane: bool = True):
         """provider(name) -> tensor with diffusers' Flux2Transformer2DModel parameter of that name.
-        fp8: False, True (= every block linear) or a tuple of names out of FP8_ALL."""
+        fp8: False, True (= every block linear) or a tuple of names out of FP8_ALL.
+        text_stream_on_side_lane: run the double-stream blocks' text linears beside the image stream's (plan lanes); False keeps one lane."""
+        self.side_lane = bool(text_stream_on_side_lane)
         self.lib = lib if lib is not None else get_library()
         self.device = torch.device(device)
         self.dtype, self.tdt = abi.BF16, torch.bfloat16
@@ -190,7 +193,7 @@ class Flux2DiTHip:
         t_img = t_noise + t_ref
         T = t_txt + t_img
         FW = 3 * D + 2 * hid                                     # width of the single blocks' fused projection
-        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        pb = PlanBuilder(self.lib, self.device, self.dtype, lanes=self.side_lane)
         lat = pb.buf((t_img, cfg["in_channels"]), self.tdt)       # [noise tokens ; reference tokens]
         ctx_in = pb.buf((t_txt, cfg["joint_dim"]), self.tdt)      # prompt embeddings
         tab = torch.from_numpy(rope_table(token_ids(t_txt, h2, w2, rh2, rw2), cfg["axes_dim"], theta=cfg.get("rope_theta", 2000.0)))
@@ -315,7 +318,12 @@ class Flux2VAEHip(FluxVAEHip):
 class Flux2KleinHip:
     """diffusers-pipeline-shaped callable (Flux2KleinPipeline) built from the two graphs above."""
 
-    def __init__(self, dit: Flux2DiTHip, vae: Flux2VAEHip, graph: bool = True):
+    def __init__(self, dit: Flux2DiTHip, vae: Flux2VAEHip, graph: bool = True, text_stream_on_side_lane=None):
+        """text_stream_on_side_lane: None keeps what the DiT was built with (lanes on by default); True / False set it for the step plans this
+        pipeline builds (plans built before are dropped)"""
+        if text_stream_on_side_lane is not None and bool(text_stream_on_side_lane) != dit.side_lane:
+            dit.side_lane = bool(text_stream_on_side_lane)
+            dit._plans.clear()
         self.transformer, self.vae = dit, vae
         self.device = dit.device
         self._execution_device = dit.device

@@ -765,6 +765,17 @@ MTX_API int mtx_gemm(const mtx_gemm_args* a, void* stream);
  * tiles (1 = none) and the number of (slice, tile) pieces of the K-slice tail */
 MTX_API int mtx_gemm_last_split(int* whole_tiles, int* k_slices, int* tail_pieces);
 MTX_API int mtx_attention(const mtx_attn_args* a, void* stream);
+/* which kernel THIS THREAD's last 16-bit mtx_attention launch took (test / tooling introspection, host only): `kernel` is MTX_ATTN_ROUTE_LONG
+ * for the long-sequence kernel (d = 128, sq >= 1024, sk >= 256), else the padded head width of the short kernel (32 / 64 / 96 / 128; 0 = no
+ * launch yet); `flags` are MTX_ATTN_ROUTE_* bits (of the long-sequence kernel, PRESCALED of either); workgroups [0, n_full) cover whole key
+ * ranges and every query block beyond them is cut into `split` key ranges that the merge kernel adds up (split = 1: none) */
+#define MTX_ATTN_ROUTE_LONG 1
+#define MTX_ATTN_ROUTE_PRESCALED 1    /* the pre-scaled tile step (MTX_ATTN_Q_PRESCALED; always with fp8 scores) */
+#define MTX_ATTN_ROUTE_WIDE_STORE 2   /* 16-bit rows leave as 16-byte stores (o_ss, o_hs, o_bs multiples of 8 and o 16-byte aligned), else 8-byte ones */
+#define MTX_ATTN_ROUTE_F8_SCORES 4    /* q_f8 / k_f8 */
+#define MTX_ATTN_ROUTE_F8_PV 8        /* v_f8t */
+#define MTX_ATTN_ROUTE_Q8 16          /* the rows leave as the MX fp8 operand (q8) */
+MTX_API int mtx_attention_last_route(int* kernel, int* flags, int* n_full, int* split);
 MTX_API int mtx_norm(const mtx_norm_args* a, void* stream);
 MTX_API int mtx_groupnorm(const mtx_groupnorm_args* a, void* stream);
 MTX_API int mtx_elementwise(const mtx_ew_args* a, void* stream);

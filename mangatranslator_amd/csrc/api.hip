@@ -16,6 +16,7 @@ int conv2d_launch(const mtx_conv2d_args*, void*, const char**);
 int conv2d_tiles(const mtx_conv2d_args*);
 int gemm_launch(const mtx_gemm_args*, void*, const char**);
 void gemm_last_split(int*);
+void attn_last_route(int*);
 int attn_launch(const mtx_attn_args*, void*, const char**);
 int norm_launch(const mtx_norm_args*, void*, const char**);
 int groupnorm_launch(const mtx_groupnorm_args*, void*, const char**);
@@ -283,6 +284,16 @@ int mtx_gemm_last_split(int* whole_tiles, int* k_slices, int* tail_pieces) {
   if (whole_tiles) *whole_tiles = v[0];
   if (k_slices) *k_slices = v[1];
   if (tail_pieces) *tail_pieces = v[2];
+  return MTX_OK;
+}
+
+int mtx_attention_last_route(int* kernel, int* flags, int* n_full, int* split) {
+  int v[4];
+  attn_last_route(v);
+  if (kernel) *kernel = v[0];
+  if (flags) *flags = v[1];
+  if (n_full) *n_full = v[2];
+  if (split) *split = v[3];
   return MTX_OK;
 }
 

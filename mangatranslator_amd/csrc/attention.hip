@@ -705,7 +705,11 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(AttnParams p) {
     const float inv = L > 0.f ? 1.0f / L : 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] *= inv;
-    *reinterpret_cast<u32x4*>(O + qr * p.o_ss + ch * 8) = pack8<T>(acc);
+    const u32x4 out = pack8<T>(acc);
+    T* dst = O + qr * p.o_ss + ch * 8;
+    // an output the ABI admits with 8-byte alignment only (o itself, or o_ss / o_hs / o_bs = 4 mod 8: the main kernel's 8-byte store form) leaves in two halves
+    if (((size_t)dst & 15) == 0) *reinterpret_cast<u32x4*>(dst) = out;
+    else { *reinterpret_cast<u32x2*>(dst) = u32x2{out[0], out[1]}; *reinterpret_cast<u32x2*>(dst + 4) = u32x2{out[2], out[3]}; }
   }
 }
 
@@ -746,6 +750,10 @@ __global__ __launch_bounds__(256) void attn_merge_q8_kernel(AttnParams p) {
   }
 }
 
+// kernel family (MTX_ATTN_ROUTE_LONG, or the short kernel's padded head width), MTX_ATTN_ROUTE_* flags, n_full, split of this thread's last launch
+static thread_local int g_last_route[4] = {0, 0, 0, 1};
+void attn_last_route(int* out) { for (int i = 0; i < 4; ++i) out[i] = g_last_route[i]; }
+
 template <typename T>
 static int launch_attn_t(const AttnParams& p0, void* stream) {
   AttnParams p = p0;
@@ -773,12 +781,19 @@ static int launch_attn_t(const AttnParams& p0, void* stream) {
     else if (p.q8 != nullptr) kernel = p.prescaled ? attn_mma32_q8d_kernel<T, 128, true> : attn_mma32_q8_kernel<T, 128, false>;
     else if (p.prescaled) kernel = wide_ok ? attn_mma32_d_kernel<T, 128, true> : attn_mma32_kernel<T, 128, true>;      // wide_ok: the FLUX graphs' form
     else kernel = attn_mma32_kernel<T, 128, false>;
+    g_last_route[0] = MTX_ATTN_ROUTE_LONG;
+    g_last_route[1] = (p.kf8 != nullptr || p.prescaled ? MTX_ATTN_ROUTE_PRESCALED : 0) | (p.kf8 != nullptr ? MTX_ATTN_ROUTE_F8_SCORES : 0) |
+                      (p.vf8 != nullptr && p.kf8 != nullptr ? MTX_ATTN_ROUTE_F8_PV : 0) | (p.q8 != nullptr ? MTX_ATTN_ROUTE_Q8 : 0) |
+                      (p.q8 == nullptr && (p.kf8 != nullptr || (p.prescaled && wide_ok)) ? MTX_ATTN_ROUTE_WIDE_STORE : 0);
+    g_last_route[2] = (int)p.n_full; g_last_route[3] = (int)p.split;
     MTX_LAUNCH(kernel, dim3(g), dim3(512), 0, stream, p);
     if (p.split > 1) MTX_LAUNCH((p.q8 != nullptr ? attn_merge_q8_kernel<T, 128> : attn_merge_kernel<T, 128>), dim3((total - p.n_full) * 8), dim3(256), 0, stream, p);
     return MTX_OK;
   }
   if (p.q8 != nullptr || p.kf8 != nullptr) return MTX_ERR_UNSUPPORTED;
   const unsigned grid = (unsigned)(p.batch * p.heads) * p.qblocks;
+  g_last_route[0] = p.d <= 32 ? 32 : p.d <= 64 ? 64 : p.d <= 96 ? 96 : 128;
+  g_last_route[1] = p.prescaled ? MTX_ATTN_ROUTE_PRESCALED : 0; g_last_route[2] = (int)grid; g_last_route[3] = 1;
   if (p.d <= 32) MTX_LAUNCH((attn_kernel<T, 32>), dim3(grid), dim3(256), 0, stream, p);
   else if (p.d <= 64) MTX_LAUNCH((attn_kernel<T, 64>), dim3(grid), dim3(256), 0, stream, p);
   else if (p.d <= 96) MTX_LAUNCH((attn_kernel<T, 96>), dim3(grid), dim3(256), 0, stream, p);

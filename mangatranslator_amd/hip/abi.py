@@ -74,6 +74,8 @@ class AttnArgs(C.Structure):
 
 
 ATTN_Q_PRESCALED = 1
+ATTN_ROUTE_LONG = 1                                           # mtx_attention_last_route: `kernel` of the long-sequence kernel, else the short kernel's padded head width
+ATTN_ROUTE_PRESCALED, ATTN_ROUTE_WIDE_STORE, ATTN_ROUTE_F8_SCORES, ATTN_ROUTE_F8_PV, ATTN_ROUTE_Q8 = 1, 2, 4, 8, 16      # its `flags`
 ATTN_WORKSPACE_BYTES = 256 * (256 * 128 * 4 + 256 * 2 * 4)
 
 
@@ -339,7 +341,7 @@ UNION_FIELD = {OP_CONV2D: "conv", OP_GEMM: "gemm", OP_ATTN: "attn", OP_NORM: "no
 # every symbol include/mtx_hip.h declares (tests check the built library exports all of them)
 EXPORTS = [
     "mtx_abi_version", "mtx_abi_sizeof", "mtx_last_error", "mtx_init", "mtx_device_info",
-    "mtx_conv2d", "mtx_conv2d_tiles", "mtx_gemm", "mtx_gemm_last_split", "mtx_attention", "mtx_norm", "mtx_groupnorm",
+    "mtx_conv2d", "mtx_conv2d_tiles", "mtx_gemm", "mtx_gemm_last_split", "mtx_attention", "mtx_attention_last_route", "mtx_norm", "mtx_groupnorm",
     "mtx_elementwise", "mtx_channel_attention", "mtx_image_convert", "mtx_resize_threshold",
     "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_row_linear_wide", "mtx_decode_attention_batch", "mtx_beam_step", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
     "mtx_plan_create", "mtx_plan_run", "mtx_plan_run_graph", "mtx_plan_num_ops",

@@ -64,6 +64,7 @@ class MtxLibrary:
         d.mtx_host_png_encode.restype = C.c_int64
         d.mtx_conv2d_tiles.argtypes = [C.POINTER(abi.ConvArgs)]
         d.mtx_gemm_last_split.argtypes = [C.POINTER(C.c_int)] * 3
+        d.mtx_attention_last_route.argtypes = [C.POINTER(C.c_int)] * 4
         d.mtx_plan_create.argtypes = [C.POINTER(abi.Op), C.c_int, C.POINTER(C.c_void_p)]
         d.mtx_plan_run.argtypes = [C.c_void_p, C.c_void_p]
         d.mtx_plan_run_graph.argtypes = [C.c_void_p, C.c_void_p]
@@ -99,6 +100,13 @@ class MtxLibrary:
         """(whole tiles, K slices, tail pieces) of this thread's last 256-tile GEMM launch (mtx_gemm_last_split)"""
         v = [C.c_int(0) for _ in range(3)]
         self._dll.mtx_gemm_last_split(*[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def attention_last_route(self):
+        """(kernel, flags, n_full, split) of this thread's last 16-bit attention launch (mtx_attention_last_route): kernel = abi.ATTN_ROUTE_LONG or the
+        short kernel's padded head width, flags = abi.ATTN_ROUTE_* bits"""
+        v = [C.c_int(0) for _ in range(4)]
+        self._dll.mtx_attention_last_route(*[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
     def init(self, device_ordinal: int = 0) -> None:

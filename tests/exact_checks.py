@@ -405,12 +405,138 @@ def _assert_one_rounding(got, ref, dtype, what):
     return worst
 
 
-def _launch_attention(lib, dtype, q, k, v, f8_scores, prescaled):
-    """q [b, sq, heads, d], k / v [b, sk, heads, d] (float64 on the device, values exact in T and, with f8_scores, in e4m3) -> the kernel's output"""
+ATTN_LAYOUTS = ("dense", "fused_qkv", "windows", "fused_kv", "fused_qk_sep_v", "o_slice", "head_major", "narrow_o_ss", "narrow_o_off")
+ATTN_TAIL_ROWS = 64                     # poisoned / sentinel rows behind every buffer: one key tile, so a load that lost its guard meets NaN inside the allocation
+UNIT_SCALE = 0.6931471824645996         # the fp32 value whose fp32 product with the launcher's log2(e) constant is exactly 1: integer logits stay integers without MTX_ATTN_Q_PRESCALED
+assert float(torch.tensor(UNIT_SCALE, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)) == 1.0
+
+
+def attention_layout(layout, batch, heads, sq, sk, d):
+    """Where the four operands of a call live (C = heads * d, ld = row stride in elements):
+         fused_qkv       q | k | v in the rows of one [batch * max(sq, sk), 3C + 8] buffer, o in [rows, C]     (SAM 3, FLUX, the manga-ocr encoder)
+         windows         fused_qkv with sq == sk == the window's tokens: window b + 1 starts right behind window b  (SAM 2.1, YOLO11 area attention)
+         fused_kv        q apart, k | v in [sk, 2C]                                                               (manga-ocr cross attention)
+         fused_qk_sep_v  q | k in [rows, 2C], v in [rows, C + 8]: k_ss != v_ss                                    (RT-DETR, the SAM decoder)
+         o_slice         fused_qkv, o at column 2C of a [rows, 5C] buffer                                         (the FLUX single block)
+         head_major      [batch, heads, s, d], every operand with its own row, sequence and batch padding: twelve different strides
+         narrow_o_ss     fused_qkv with o_ss = C + 4; narrow_o_off: o four elements into rows of C + 8: 8-byte stores only
+    -> {operand: (buffer, offset, (bs, ss, hs))} in elements"""
+    C, smax = heads * d, max(sq, sk)
+    if layout == "dense":
+        return {"q": ("q", 0, (sq * C, C, d)), "k": ("k", 0, (sk * C, C, d)), "v": ("v", 0, (sk * C, C, d)), "o": ("o", 0, (sq * C, C, d))}
+    if layout == "head_major":
+        spec = {}
+        for i, (x, s) in enumerate((("q", sq), ("k", sk), ("v", sk), ("o", sq))):
+            ss = d + 8 * i
+            hs = (s + 1 + i) * ss
+            spec[x] = (x, 0, (heads * hs + 8 * (i + 1), ss, hs))
+        strides = [st for _, _, three in spec.values() for st in three]
+        assert len(set(strides)) == 12, f"head_major: two of the twelve strides are equal: {strides}"
+        return spec
+    if layout == "fused_kv":
+        return {"q": ("q", 0, (sq * C, C, d)), "k": ("kv", 0, (sk * 2 * C, 2 * C, d)), "v": ("kv", C, (sk * 2 * C, 2 * C, d)), "o": ("o", 0, (sq * C, C, d))}
+    if layout == "fused_qk_sep_v":
+        return {"q": ("qk", 0, (smax * 2 * C, 2 * C, d)), "k": ("qk", C, (smax * 2 * C, 2 * C, d)), "v": ("v", 0, (sk * (C + 8), C + 8, d)),
+                "o": ("o", 0, (sq * C, C, d))}
+    if layout == "windows":
+        assert sq == sk and sq % 64, "windows: one window of tokens on both sides, not a multiple of the key tile"
+    ld = 3 * C + 8
+    spec = {"q": ("qkv", 0, (smax * ld, ld, d)), "k": ("qkv", C, (smax * ld, ld, d)), "v": ("qkv", 2 * C, (smax * ld, ld, d)), "o": ("o", 0, (sq * C, C, d))}
+    if layout == "o_slice":
+        spec["o"] = ("o", 2 * C, (sq * 5 * C, 5 * C, d))
+    elif layout == "narrow_o_ss":
+        spec["o"] = ("o", 0, (sq * (C + 4), C + 4, d))
+    elif layout == "narrow_o_off":
+        spec["o"] = ("o", 4, (sq * (C + 8), C + 8, d))
+    else:
+        assert layout in ("fused_qkv", "windows"), layout
+    return spec
+
+
+def attention_route(cus, batch, heads, sq, sk, d, layout="dense", prescaled=False):
+    """launch_attn_t (csrc/attention.hip) restated: what mtx_attention_last_route must report for a 16-bit call without fp8 operands on `cus` compute
+    units, from buffers that start on a 16-byte boundary -> (kernel, flags, n_full, split)"""
+    pre = abi.ATTN_ROUTE_PRESCALED if prescaled else 0
+    if not (d == 128 and sq >= 1024 and sk >= 256):
+        grid = batch * heads * ((sq + 127) // 128)
+        return (32 if d <= 32 else 64 if d <= 64 else 96 if d <= 96 else 128), pre, grid, 1
+    _, off, (bs, ss, hs) = attention_layout(layout, batch, heads, sq, sk, d)["o"]
+    wide = prescaled and ss % 8 == 0 and hs % 8 == 0 and bs % 8 == 0 and off % 8 == 0
+    total, ntiles = batch * heads * ((sq + 255) // 256), (sk + 63) // 64
+    rem = total % cus
+    split = min(cus // rem if rem > 0 and total > cus else 1, 8, ntiles // 2)
+    n_full, split = (total, 1) if split < 2 else (total - rem, split)
+    return abi.ATTN_ROUTE_LONG, pre | (abi.ATTN_ROUTE_WIDE_STORE if wide else 0), n_full, split
+
+
+def compute_units(lib):
+    """the CU count the launchers see: mtx_device_info's, or the simulator's 3 (csrc/mtx_device.h)"""
+    if lib.is_simulator:
+        return 3
+    import ctypes as C
+    cus = C.c_int(0)
+    lib.check(lib.mtx_device_info(C.byref(cus), None, None, 0), "mtx_device_info")
+    return cus.value
+
+
+def _assert_route(lib, route, what):
+    """route: None, or (kernel, flags, n_full, split) where None = any value and a split of ">=2" = any key split"""
+    if route is None:
+        return
+    got = lib.attention_last_route()
+    ok = all(e is None or (e == ">=2" and g >= 2) or e == g for e, g in zip(route, got))
+    assert ok, f"{what}: the launch took (kernel, flags, n_full, split) = {got}, the case is written for {tuple(route)}"
+
+
+def _launch_attention_layout(lib, dtype, q, k, v, prescaled, layout, route, scale):
+    """the operands placed as attention_layout says, every element around them NaN (inputs) or _SENTINEL (output), ATTN_TAIL_ROWS such rows behind each buffer"""
+    dev, td = _dev(lib), TD[dtype]
+    batch, sq, heads, d = q.shape
+    sk = k.shape[1]
+    what = f"attention {layout} {batch}x{heads}x{sq}x{sk} d{d}"
+    spec = attention_layout(layout, batch, heads, sq, sk, d)
+    shape = {"q": (batch, sq, heads, d), "k": (batch, sk, heads, d), "v": (batch, sk, heads, d), "o": (batch, sq, heads, d)}
+    size = {}
+    for x, (name, off, (bs, ss, hs)) in spec.items():
+        b_, s_, h_, _ = shape[x]
+        assert off + d <= ss and min(bs, ss, hs) >= d, f"{what}: operand {x} overlaps itself"
+        extent = off + (b_ - 1) * bs + (s_ - 1) * ss + (h_ - 1) * hs + d
+        size[name] = max(size.get(name, 0), extent + ATTN_TAIL_ROWS * ss + 8)
+    pb = PlanBuilder(lib, dev, dtype)
+    bufs = {name: pb.buf((n,), td) for name, n in size.items()}
+    view = lambda t, x: t.as_strided(shape[x], spec[x][2] + (1,), spec[x][1])
+    for name, t in bufs.items():
+        t.fill_(_SENTINEL if name == "o" else float("nan"))
+    for x, val in (("q", q), ("k", k), ("v", v)):
+        view(bufs[spec[x][0]], x).copy_(val.to(td))
+    for name, t in bufs.items():                                 # what the call must not read is NaN, all of it: the operands do not overlap
+        if name != "o":
+            inside = sum(math.prod(shape[x]) for x in "qkv" if spec[x][0] == name)
+            assert int(t.isnan().sum()) == t.numel() - inside, f"{what}: operands overlap in buffer {name}"
+    ptr_off = {x: spec[x][1] for x in spec}
+    assert all(t.data_ptr() % 16 == 0 for t in bufs.values())
+    pb.attention(bufs[spec["q"][0]], bufs[spec["k"][0]], bufs[spec["v"][0]], bufs["o"], batch, heads, sq, sk, d,
+                 spec["q"][2], spec["k"][2], spec["v"][2], spec["o"][2], scale, q_off=ptr_off["q"], k_off=ptr_off["k"], v_off=ptr_off["v"],
+                 o_off=ptr_off["o"], q_prescaled=prescaled)
+    _run(pb)
+    _assert_route(lib, route, what)
+    written = torch.zeros(bufs["o"].numel(), dtype=torch.bool, device=dev)
+    view(written, "o").fill_(True)
+    assert int(written.sum()) == math.prod(shape["o"])
+    assert bool((bufs["o"][~written] == _SENTINEL).all()), f"{what}: written outside the output ({int((bufs['o'][~written] != _SENTINEL).sum())} elements)"
+    return view(bufs["o"], "o")
+
+
+def _launch_attention(lib, dtype, q, k, v, f8_scores, prescaled, layout="dense", route=None, scale=None):
+    """q [b, sq, heads, d], k / v [b, sk, heads, d] (float64 on the device, values exact in T and, with f8_scores, in e4m3) -> the kernel's output.
+    layout: where the operands live (attention_layout); "dense" = four private buffers, as the cases of the first round of exact tests had them"""
     dev, td = _dev(lib), TD[dtype]
     batch, sq, heads, d = q.shape
     sk = k.shape[1]
     D = heads * d
+    if layout != "dense":
+        assert not f8_scores
+        return _launch_attention_layout(lib, dtype, q, k, v, prescaled, layout, route, 1.0 / math.sqrt(d) if scale is None else scale)
     pb = PlanBuilder(lib, dev, dtype)
     o = pb.buf((batch, sq, heads, d), td, zero=True)
     if f8_scores:
@@ -424,15 +550,17 @@ def _launch_attention(lib, dtype, q, k, v, f8_scores, prescaled):
                      1.0, q_prescaled=True, qk_f8=(pb.const(packed), 0, D, 2 * D, 0))
     else:
         pb.attention(pb.const(q.to(td)), pb.const(k.to(td)), pb.const(v.to(td)), o, batch, heads, sq, sk, d,
-                     (sq * D, D, d), (sk * D, D, d), (sk * D, D, d), (sq * D, D, d), 1.0 / math.sqrt(d), q_prescaled=prescaled)
+                     (sq * D, D, d), (sk * D, D, d), (sk * D, D, d), (sq * D, D, d), 1.0 / math.sqrt(d) if scale is None else scale, q_prescaled=prescaled)
     _run(pb)
+    _assert_route(lib, route, f"attention {batch}x{heads}x{sq}x{sk} d{d}")
     return o
 
 
-def check_attention_census(lib, dtype, batch, heads, sq, sk, d, prescaled=False, f8_scores=False, seed=0):
+def check_attention_census(lib, dtype, batch, heads, sq, sk, d, prescaled=False, f8_scores=False, seed=0, layout="dense", route=None):
     """Key census: q = 0, so every score is 0 and every probability 1; v[j, :, c] = 64 where c = hash(j) and 0 elsewhere.  Every output row is
     then 64 * count_c / sk: a key dropped or counted twice moves one channel by 64 / sk — about 128 / sk of its value, far above the rounding.
-    Two hashes, j % d and (j // d) % d, so that every key is told apart from its neighbours and from the keys d away."""
+    Two hashes, j % d and (j // d) % d, so that every key is told apart from its neighbours and from the keys d away.
+    layout: where the operands live (attention_layout); route: what mtx_attention_last_route must report (_assert_route)."""
     g = torch.Generator().manual_seed(seed)
     dev = _dev(lib)
     worst = 0.0
@@ -444,16 +572,17 @@ def check_attention_census(lib, dtype, batch, heads, sq, sk, d, prescaled=False,
         v[:, j, :, hashed(j)] = 64.0
         count = torch.bincount(hashed(j), minlength=d).double()
         ref = (64.0 * count / sk).to(dev).expand(batch, sq, heads, d)
-        o = _launch_attention(lib, dtype, q, k, v.to(dev), f8_scores, prescaled)
-        worst = max(worst, _assert_one_rounding(o, ref, dtype, f"attention census {batch}x{heads}x{sq}x{sk} d{d}"))
+        o = _launch_attention(lib, dtype, q, k, v.to(dev), f8_scores, prescaled, layout, route)
+        worst = max(worst, _assert_one_rounding(o, ref, dtype, f"attention census {layout} {batch}x{heads}x{sq}x{sk} d{d}"))
     return worst
 
 
-def check_attention_dyadic(lib, dtype, batch, heads, sq, sk, d, f8_scores=False, late_max=False, seed=0):
+def check_attention_dyadic(lib, dtype, batch, heads, sq, sk, d, f8_scores=False, late_max=False, seed=0, layout="dense", route=None, prescaled=True):
     """Dyadic softmax (MTX_ATTN_Q_PRESCALED; with f8_scores the e4m3 score path at qk_f8_exp = 0): q rows are +-one-hot, k holds integers in
     [-3, 3], v integers in [-4, 4].  The base-2 logits are then integers, every probability is a power of two whatever maximum the kernel
     subtracts, and numerator and denominator are exact in fp32 (sk * 4 * 2^6 < 2^24).  late_max: the first three quarters of the keys are clamped
-    to [-1, 1], so the running maximum has to move late."""
+    to [-1, 1], so the running maximum has to move late.  prescaled = False: the same logits through the scaling kernels, at UNIT_SCALE.
+    layout, route: as in check_attention_census."""
     g = torch.Generator().manual_seed(seed)
     dev = _dev(lib)
     assert sk * 4 * 64 < EXACT
@@ -466,7 +595,7 @@ def check_attention_dyadic(lib, dtype, batch, heads, sq, sk, d, f8_scores=False,
         k[:, :sk * 3 // 4].clamp_(-1, 1)
     v = _ints(g, (batch, sk, heads, d), 4)
     q, k, v = q.to(dev), k.to(dev), v.to(dev)
-    o = _launch_attention(lib, dtype, q, k, v, f8_scores, True)
+    o = _launch_attention(lib, dtype, q, k, v, f8_scores, prescaled, layout, route, scale=1.0 if prescaled else UNIT_SCALE)
     worst = 0.0
     for bi in range(batch):
         for hd in range(heads):                                                          # head by head: the float64 score matrix of 24 heads would not fit
@@ -475,6 +604,78 @@ def check_attention_dyadic(lib, dtype, batch, heads, sq, sk, d, f8_scores=False,
             ref = (p @ v[bi, :, hd]) / p.sum(dim=1, keepdim=True)
             worst = max(worst, _assert_one_rounding(o[bi, :, hd], ref, dtype, f"dyadic attention {sq}x{sk} d{d}, batch {bi} head {hd}"))
     return worst
+
+
+# ---- attention through the layouts the model graphs use (attention_layout), every case with the route it is written for -------------------
+# kernel: the short kernel's padded head width, or "long"; wide: the long-sequence kernel's 16-byte row stores (pre-scaled q and an aligned output only).
+# at_256 = (n_full, split) on 256 compute units: the key-split tail and attn_merge_kernel; at_3 the same on the simulator's three.  gpu_only: left out of
+# the simulator tier — the 43 to 84 heads that fill 256 compute units cost it many times what its other long-sequence cases do, and on 3 compute units
+# they would be cut differently anyway (there every long-sequence case with total % 3 == 1 goes through split 3 and the merge).
+_L = abi.ATTN_ROUTE_LONG
+ATTN_LAYOUT_CASES = [
+    # the short kernel, its four widths through fused_qkv and one more layout each
+    dict(layout="fused_qkv", batch=1, heads=3, sq=70, sk=150, d=8, kernel=32),
+    dict(layout="fused_kv", batch=2, heads=3, sq=5, sk=100, d=8, kernel=32, prescaled=True),
+    dict(layout="fused_qkv", batch=1, heads=2, sq=9, sk=100, d=40, kernel=64, prescaled=True),
+    dict(layout="windows", batch=3, heads=2, sq=196, sk=196, d=40, kernel=64),
+    dict(layout="head_major", batch=2, heads=2, sq=70, sk=150, d=40, kernel=64),
+    dict(layout="fused_qkv", batch=1, heads=2, sq=70, sk=150, d=88, kernel=96),
+    dict(layout="fused_qk_sep_v", batch=2, heads=2, sq=70, sk=150, d=88, kernel=96, prescaled=True),
+    dict(layout="fused_qkv", batch=1, heads=2, sq=70, sk=150, d=104, kernel=128),
+    dict(layout="fused_qkv", batch=2, heads=2, sq=130, sk=100, d=128, kernel=128, prescaled=True),
+    dict(layout="head_major", batch=1, heads=3, sq=9, sk=100, d=104, kernel=128),
+    dict(layout="o_slice", batch=2, heads=2, sq=70, sk=150, d=128, kernel=128),
+    dict(layout="fused_kv", batch=1, heads=2, sq=1, sk=70, d=128, kernel=128),
+    dict(layout="narrow_o_ss", batch=2, heads=2, sq=70, sk=150, d=104, kernel=128),
+    dict(layout="narrow_o_off", batch=1, heads=2, sq=9, sk=100, d=16, kernel=32),
+    dict(layout="fused_qkv", batch=1, heads=1, sq=1030, sk=200, d=128, kernel=128),                    # long queries, short keys: still the short kernel
+    # the long-sequence kernel (d = 128, sq >= 1024, sk >= 256)
+    dict(layout="fused_qkv", batch=1, heads=2, sq=1030, sk=330, d=128, kernel=_L, prescaled=True, wide=True, at_3=(9, 3)),      # on the simulator's 3 compute units: n_full 9, split 3, the merge
+    dict(layout="fused_qk_sep_v", batch=1, heads=1, sq=1100, sk=449, d=128, kernel=_L, wide=False),
+    dict(layout="narrow_o_ss", batch=1, heads=1, sq=1030, sk=330, d=128, kernel=_L, prescaled=True, wide=False),
+    dict(layout="fused_qkv", batch=1, heads=2, sq=1030, sk=330, d=128, kernel=_L, wide=False),
+    dict(layout="fused_qk_sep_v", batch=1, heads=2, sq=1100, sk=449, d=128, kernel=_L, prescaled=True, wide=True),
+    dict(layout="head_major", batch=1, heads=2, sq=1100, sk=449, d=128, kernel=_L, prescaled=True, wide=True),
+    dict(layout="head_major", batch=2, heads=2, sq=1100, sk=449, d=128, kernel=_L, wide=False),
+    dict(layout="fused_qkv", batch=2, heads=2, sq=1030, sk=330, d=128, kernel=_L, prescaled=True, wide=True),
+    dict(layout="o_slice", batch=2, heads=2, sq=1030, sk=330, d=128, kernel=_L, prescaled=True, wide=True),
+    dict(layout="narrow_o_off", batch=1, heads=2, sq=1030, sk=330, d=128, kernel=_L, prescaled=True, wide=False, at_3=(9, 3)),     # the merge writes 8-byte aligned rows
+    dict(layout="narrow_o_ss", batch=2, heads=2, sq=1030, sk=330, d=128, kernel=_L, wide=False),
+    # the key-split tail
+    dict(layout="fused_qkv", batch=1, heads=65, sq=1024, sk=256, d=128, kernel=_L, prescaled=True, wide=True, at_256=(256, 2), gpu_only=True),      # total 260, rem 4: 64 clamped by ntiles / 2
+    dict(layout="fused_qkv", batch=1, heads=65, sq=1024, sk=1000, d=128, kernel=_L, prescaled=True, wide=True, at_256=(256, 8), gpu_only=True),     # ... clamped by 8; ragged last key tile
+    dict(layout="fused_qkv", batch=1, heads=84, sq=1024, sk=640, d=128, kernel=_L, prescaled=True, wide=True, at_256=(256, 3), gpu_only=True),      # total 336, rem 80
+    dict(layout="fused_qkv", batch=1, heads=43, sq=1300, sk=1000, d=128, kernel=_L, prescaled=True, wide=True, at_256=(256, 8), gpu_only=True),     # 6 query blocks, the last one partial; rem 2
+    dict(layout="narrow_o_off", batch=1, heads=65, sq=1024, sk=256, d=128, kernel=_L, prescaled=True, wide=False, at_256=(256, 2), gpu_only=True),  # the merge writes 8-byte aligned rows
+    dict(layout="fused_qkv", batch=1, heads=65, sq=1024, sk=320, d=128, kernel=_L, wide=False, at_256=(256, 2), gpu_only=True),                      # the scaling kernel's partials
+]
+
+
+def attention_case_id(case):
+    return f"{case['layout']}-{case['batch']}x{case['heads']}x{case['sq']}x{case['sk']}-d{case['d']}{'-prescaled' if case.get('prescaled') else ''}"
+
+
+def check_attention_layout_case(lib, dtype, kind, case, seed=0):
+    """one row of ATTN_LAYOUT_CASES as a key census (kind "census") or a dyadic softmax ("dyadic"); the route comes from launch_attn_t's rule at the
+    device's CU count, must be the one the row is written for, and the launch must report it"""
+    import pytest
+    shape = {key: case[key] for key in ("batch", "heads", "sq", "sk", "d")}
+    prescaled = case.get("prescaled", False)
+    route = attention_route(compute_units(lib), layout=case["layout"], prescaled=prescaled, **shape)
+    assert route[0] == case["kernel"], f"{attention_case_id(case)}: written for kernel {case['kernel']}, the launch rule gives {route[0]}"
+    if case["kernel"] == _L:
+        assert bool(route[1] & abi.ATTN_ROUTE_WIDE_STORE) == case["wide"], f"{attention_case_id(case)}: written for {'16' if case['wide'] else '8'}-byte stores"
+    if "at_3" in case:
+        assert attention_route(3, layout=case["layout"], prescaled=prescaled, **shape)[2:] == case["at_3"]
+    if "at_256" in case:
+        assert attention_route(256, layout=case["layout"], prescaled=prescaled, **shape)[2:] == case["at_256"]
+        if route[3] < 2:
+            pytest.skip(f"{attention_case_id(case)} reaches the key split on 256 compute units as (n_full, split) = {case['at_256']}; "
+                        f"on the {compute_units(lib)} of this device the launch rule gives split {route[3]}: no partials, no merge")
+    if kind == "census":
+        return check_attention_census(lib, dtype, prescaled=prescaled, seed=seed, layout=case["layout"], route=route, **shape)
+    assert kind == "dyadic"
+    return check_attention_dyadic(lib, dtype, prescaled=prescaled, seed=seed, layout=case["layout"], route=route, **shape)
 
 
 # ---- the conv cases of both tiers (the GPU tier adds the page-scale shapes) -------------------------------------------------------------

@@ -410,6 +410,95 @@ def check_ew_im2col(lib, dtype, seed=0):
     e.run()
 
 
+def _im2col_patch_ref(x, k, s):
+    """_im2col_ref without padding (MTX_EW_IM2COL_PATCH): oh = (h - k) // s + 1, the pixels a last partial patch would need are dropped"""
+    n, h, w, c = x.shape
+    u = F.unfold(x.permute(0, 3, 1, 2), k, padding=0, stride=s)
+    oh, ow = (h - k) // s + 1, (w - k) // s + 1
+    assert u.shape == (n, c * k * k, oh * ow)
+    ref = u.view(n, c, k * k, oh * ow).permute(0, 3, 2, 1).reshape(n * oh * ow, k * k * c)
+    r5 = ref.view(n, oh, ow, k * k, c)
+    for tap in range(k * k):
+        ky, kx = tap // k, tap % k
+        want = x[:, ky:ky + (oh - 1) * s + 1:s, kx:kx + (ow - 1) * s + 1:s]
+        assert torch.equal(r5[:, :, :, tap], want), f"the im2col_patch reference is not in the column order tap * C + c (tap {tap})"
+    return ref, oh, ow
+
+
+def check_ew_im2col_patch(lib, dtype, seed=0):
+    """MTX_EW_IM2COL_PATCH, the unpadded im2col behind the patch embeddings: k = s in {2, 4, 14} and k != s (3 / 2), h and w that leave remainder pixels,
+    h == k, C = 8 and 24, ldy > k * k * C, without a row map, with a shuffled one (a subset, some rows twice) and with the window-major order of
+    sam_common.window_order for a 4 x 4 grid of 2 x 2 windows (SAM 3's patch embedding); an image smaller than the patch is refused"""
+    import pytest
+    from mangatranslator_amd.core.ml.sam_common import window_order
+    from mangatranslator_amd.utils.exceptions import ModelError
+    e = _Ew(lib, dtype)
+    g = torch.Generator(device=e.host).manual_seed(seed)
+    for k, s, n, h, w, c, mapped in ((2, 2, 2, 16, 16, 8, "windows"), (2, 2, 1, 5, 7, 24, None), (4, 4, 1, 9, 14, 24, "shuffled"), (4, 4, 2, 4, 19, 8, None),
+                                     (14, 14, 1, 14, 30, 8, "shuffled"), (14, 14, 2, 29, 15, 8, None), (3, 2, 2, 8, 7, 8, None), (3, 2, 1, 3, 10, 24, "shuffled")):
+        x = _nonzero_ints(g, (n, h, w, c), 120)
+        ref, oh, ow = _im2col_patch_ref(x, k, s)
+        assert (oh, ow) == ((h - k) // s + 1, (w - k) // s + 1) and oh >= 1 and ow >= 1
+        rows = n * oh * ow
+        idx = None
+        if mapped == "windows":
+            assert (oh, ow) == (8, 8)
+            order = torch.from_numpy(window_order(oh, ow, 2))
+            assert order[:4].tolist() == [0, 1, 8, 9] and sorted(order.tolist()) == list(range(64))           # the first window: two tokens of row 0, two of row 1
+            idx = torch.cat([order + i * oh * ow for i in range(n)])
+        elif mapped == "shuffled":
+            sub = torch.randperm(rows, generator=g, device=e.host)[:max(rows * 2 // 3, 1)]
+            idx = torch.cat([sub, sub])[:rows]
+            assert rows < 2 or (len(set(idx.tolist())) < rows and bool((idx != torch.arange(rows, device=e.host)).any()))
+        if idx is not None:
+            ref = ref[idx]
+        ldy = k * k * c + 8
+        dst = e.pb.buf((rows + 2, ldy), e.td)
+        dst.fill_(SENTINEL)
+        e.pb.im2col(e.inp(x, c0=8), dst, k, s, ldy, row_map=e.pb.hold(idx.to(torch.int32).to(e.dev)) if idx is not None else None, pad=False)
+        e.expect(dst[:rows, :k * k * c], ref, f"im2col_patch k{k} s{s} {n}x{h}x{w}x{c}{' ' + mapped if mapped else ''}", dst)
+    e.run()
+    for h, w in ((3, 9), (9, 3)):                                                          # csrc/elementwise.hip, ew_launch: nothing is launched
+        r = _Ew(lib, dtype)
+        dst = r.pb.buf((4, 4 * 4 * 8 + 8), r.td)
+        dst.fill_(SENTINEL)
+        r.pb.im2col(r.inp(_nonzero_ints(g, (1, h, w, 8), 120)), dst, 4, 4, dst.shape[-1], pad=False)
+        with pytest.raises(ModelError, match="elementwise: im2col_patch needs an image of at least k x k"):
+            _run(r.pb)
+        assert bool((dst == SENTINEL).all()), "a refused im2col_patch wrote"
+
+
+def check_ew_im2col_patch_embed(lib, dtype, seed=0):
+    """A patch embedding as the ViT graphs build it — packing.patch_embed_rows(w), MTX_EW_IM2COL_PATCH on a 3-channel image padded to 8 channels, one GEMM —
+    equals F.conv2d(x, w, stride=p) rounded once to T: integer pixels and weights under precondition (a) of check_gemm_exact (every partial sum exact in
+    fp32).  The padding channels hold GARBAGE, which the zero columns of the packed filter must cancel; h and w leave remainder pixels."""
+    from mangatranslator_amd.core.ml.packing import patch_embed_rows
+    host, dev, td = torch.device("cpu"), _dev(lib), TD[dtype]
+    g = torch.Generator(device=host).manual_seed(seed)
+    for p, n, h, w, cout in ((4, 2, 18, 11, 24), (14, 1, 30, 43, 40)):
+        what = f"patch embedding p{p} {n}x{h}x{w} -> {cout}"
+        r, alpha = operand_range(dtype, p * p * 3)
+        x, wt = _ints(g, (n, h, w, 3), r), _ints(g, (cout, 3, p, p), r)
+        assert p * p * 3 * float(x.abs().max()) * float(wt.abs().max()) * alpha < EXACT, f"{what}: precondition (a)"
+        ref = _round(F.conv2d(x.permute(0, 3, 1, 2), wt, stride=p).permute(0, 2, 3, 1) * alpha, td)
+        oh, ow = ref.shape[1], ref.shape[2]
+        assert (oh, ow) == (h // p, w // p) and h % p and w % p
+        _assert_rounding_share(ref, dtype, what)
+        pb = PlanBuilder(lib, dev, dtype)
+        xb = pb.act(n, h, w, 8)
+        xb.t.fill_(GARBAGE)
+        xb.t[..., :3] = x.to(td)
+        wk = patch_embed_rows(wt.float())
+        assert wk.shape == (cout, p * p * 8) and bool((wk.view(cout, p * p, 8)[:, :, 3:] == 0).all())
+        rows, kk = n * oh * ow, p * p * 8
+        cols = pb.buf((rows, kk), td)
+        cols.fill_(SENTINEL)
+        pb.im2col(xb, cols, p, p, kk, pad=False)
+        out = pb.gemm(cols, pb.const(wk, td), rows, cout, kk, alpha=alpha)
+        _run(pb)
+        _assert_equal(out.view(n, oh, ow, cout).cpu(), ref, f"{what} [{NAME[dtype]}]")
+
+
 def check_ew_resample(lib, dtype, seed=0):
     """MTX_EW_UPSAMPLE2X with and without b; MTX_EW_MAXPOOL 5/1, 2/2 on odd sizes, 3/2 on odd and even sizes, the SPPF chain inside one buffer, an all-negative
     input; MTX_EW_AVGPOOL2 (ceil mode, divisor = the taps inside) on h odd, w odd, both odd and 1 x 1"""

@@ -44,6 +44,24 @@ def test_library_loads_and_exports_every_declared_symbol(path, sim, request):
     assert lib.mtx_abi_sizeof(12345) == 0
 
 
+@pytest.mark.parametrize("path,sim", [(PRODUCT, False), (SIMULATOR, True)])
+def test_attention_last_route_is_host_only_and_per_thread(path, sim, request):
+    """mtx_attention_last_route needs no device; a thread that has launched nothing reads (0, 0, 0, 1), and NULL pointers are skipped"""
+    import threading
+    if sim:
+        request.getfixturevalue("emu_lib")
+    if not path.exists():
+        pytest.skip(f"{path.name} not built")
+    lib = MtxLibrary(path, is_simulator=sim)
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(lib.attention_last_route()))
+    t.start()
+    t.join()
+    assert seen == [(0, 0, 0, 1)]
+    split = C.c_int(-7)
+    assert lib.mtx_attention_last_route(None, None, None, C.byref(split)) == 0 and split.value >= 1
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from mangatranslator_amd.utils.exceptions import ModelError
     with pytest.raises(ModelError):

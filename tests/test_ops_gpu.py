@@ -319,6 +319,9 @@ def test_conv_exact(hip_lib, dtype, cfg):
     ec.check_conv_exact(hip_lib, dtype, **cfg)
 
 
+KEY_SPLIT = (abi.ATTN_ROUTE_LONG, None, None, ">=2")          # the 24-head page shapes leave a partial last wave of query blocks: key-split tail + merge
+
+
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
 def test_attention_census(hip_lib, dtype):
     """every key counted exactly once, up to the FLUX shape (24 heads, key-split tail) and Klein's with fp8 scores"""
@@ -327,8 +330,8 @@ def test_attention_census(hip_lib, dtype):
     ec.check_attention_census(hip_lib, dtype, batch=2, heads=2, sq=300, sk=200, d=64, prescaled=True)
     ec.check_attention_census(hip_lib, dtype, batch=1, heads=2, sq=1030, sk=330, d=128)
     ec.check_attention_census(hip_lib, dtype, batch=1, heads=2, sq=1100, sk=449, d=128, prescaled=True)
-    ec.check_attention_census(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, prescaled=True)
-    ec.check_attention_census(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, prescaled=True)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, prescaled=True, route=KEY_SPLIT)
+    ec.check_attention_census(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, prescaled=True, route=KEY_SPLIT)
 
 
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
@@ -341,8 +344,17 @@ def test_attention_dyadic_softmax(hip_lib, dtype):
     ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1100, sk=449, d=128, seed=1)
     ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1024, sk=2100, d=128, late_max=True)
     ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=2, sq=1024, sk=2100, d=128, late_max=True, f8_scores=True, seed=1)
-    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, seed=2)
-    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, seed=3)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8652, sk=8652, d=128, seed=2, route=KEY_SPLIT)
+    ec.check_attention_dyadic(hip_lib, dtype, batch=1, heads=24, sq=8704, sk=8704, d=128, f8_scores=True, seed=3, route=KEY_SPLIT)
+
+
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("kind", ["census", "dyadic"])
+@pytest.mark.parametrize("case", ec.ATTN_LAYOUT_CASES, ids=ec.attention_case_id)
+def test_attention_layouts(hip_lib, dtype, kind, case):
+    """census and dyadic softmax through the layouts the model graphs use, every operand inside NaN-poisoned buffers and the output inside sentinels; each
+    case asserts the kernel, the store form and the key split (mtx_attention_last_route) it is written for.  All rows of ec.ATTN_LAYOUT_CASES run here."""
+    ec.check_attention_layout_case(hip_lib, dtype, kind, case)
 
 
 # ---- exact inputs for the streaming kernels (stream_checks.py): norms within half a spacing of T plus a measured fp32 slack, element-wise kinds with zero differing elements
@@ -367,7 +379,7 @@ def test_groupnorm_exact(hip_lib, dtype, cfg):
 
 
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
-@pytest.mark.parametrize("check", [sc.check_ew_copy_gather, sc.check_ew_im2col, sc.check_ew_resample, sc.check_ew_dwconv, sc.check_ew_arith,
+@pytest.mark.parametrize("check", [sc.check_ew_copy_gather, sc.check_ew_im2col, sc.check_ew_im2col_patch, sc.check_ew_im2col_patch_embed, sc.check_ew_resample, sc.check_ew_dwconv, sc.check_ew_arith,
                                    sc.check_ew_grid_stride], ids=lambda f: f.__name__[9:])
 def test_elementwise_exact(hip_lib, dtype, check):
     check(hip_lib, dtype)

@@ -376,6 +376,16 @@ def test_attention_dyadic_softmax_late_maximum(emu_lib):
     ec.check_attention_dyadic(emu_lib, abi.F16, batch=1, heads=1, sq=1024, sk=2100, d=128, late_max=True, f8_scores=True, seed=1)
 
 
+@pytest.mark.parametrize("dtype", [abi.BF16, abi.F16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("kind", ["census", "dyadic"])
+@pytest.mark.parametrize("case", [c for c in ec.ATTN_LAYOUT_CASES if not c.get("gpu_only")], ids=ec.attention_case_id)
+def test_attention_layouts(emu_lib, dtype, kind, case):
+    """census and dyadic softmax through the layouts the model graphs use, every operand inside NaN-poisoned buffers and the output inside sentinels; each
+    case asserts the kernel, the store form and the key split (mtx_attention_last_route) it is written for.  The rows of ec.ATTN_LAYOUT_CASES marked gpu_only
+    (the 256-CU key-split shapes, batches and further layouts of the long-sequence kernel) run in test_ops_gpu.py alone."""
+    ec.check_attention_layout_case(emu_lib, dtype, kind, case)
+
+
 # ---- exact inputs for the streaming kernels (stream_checks.py): norms within half a spacing of T plus a measured fp32 slack, element-wise kinds with zero differing elements
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
 @pytest.mark.parametrize("cfg", sc.NORM_CASES)
@@ -398,7 +408,7 @@ def test_groupnorm_exact(emu_lib, dtype, cfg):
 
 
 @pytest.mark.parametrize("dtype", [abi.BF16, abi.F16])
-@pytest.mark.parametrize("check", [sc.check_ew_copy_gather, sc.check_ew_im2col, sc.check_ew_resample, sc.check_ew_dwconv, sc.check_ew_arith,
+@pytest.mark.parametrize("check", [sc.check_ew_copy_gather, sc.check_ew_im2col, sc.check_ew_im2col_patch, sc.check_ew_im2col_patch_embed, sc.check_ew_resample, sc.check_ew_dwconv, sc.check_ew_arith,
                                    sc.check_ew_grid_stride], ids=lambda f: f.__name__[9:])
 def test_elementwise_exact(emu_lib, dtype, check):
     check(emu_lib, dtype)

@@ -721,13 +721,51 @@ typedef struct mtx_beam_step_args {
   int32_t eos[4];
 } mtx_beam_step_args;
 
+/* ---- ABI 12, additive: attention over PACKED variable-length sequences, the boundaries in device memory, so that one recorded launch
+ * serves every combination of lengths (PaddleOCR-VL fills its decode slots from one packed vision pass and one packed prompt pass).
+ * Both ops read a DEVICE int32 table of row offsets seg[0 .. 8]: segment s is rows [seg[s], seg[s + 1]) of the packed buffers, an empty
+ * segment has equal offsets, seg[8] <= cap_rows.  The host cannot see the table: a table that is not non-decreasing, starts below 0 or ends
+ * above cap_rows makes the launch do nothing (checked workgroup-uniformly before any other access).  The grids are sized from cap_rows alone;
+ * a workgroup finds its segment by walking the nine offsets, no workgroup spans two segments, surplus workgroups leave before any barrier.
+ *
+ * MTX_OP_SEG_ATTN (mtx_segment_attention): non-causal attention, segment s attends to itself only.  q, k, v, o: 16-bit [cap_rows] rows with
+ * row and head strides in elements, as mtx_attn_args without the batch stride.  For every non-empty segment the o rows are, bit for bit,
+ * what mtx_attention (batch 1, sq = sk = the segment's length, same strides) writes for that segment alone through its short kernel (the
+ * kernels share one body).  Rows at or beyond seg[8] and the rows of empty segments are neither read nor written.  Built for d % 8 == 0,
+ * d <= 96 (MTX_ERR_UNSUPPORTED otherwise); q, k, v 16-byte aligned, o 8-byte aligned, strides as mtx_attention; cap_rows < 1, a null
+ * operand or a dtype other than bf16 / f16: MTX_ERR_INVALID.  Grid: heads * (cap_rows / 128 + MTX_SEGS_MAX) workgroups. */
+#define MTX_SEGS_MAX 8
+typedef struct mtx_seg_attn_args {
+  const void* q; const void* k; const void* v; void* o; const int32_t* seg;
+  int64_t heads, d, cap_rows;
+  int64_t q_ss, q_hs, k_ss, k_hs, v_ss, v_hs, o_ss, o_hs;
+  float scale; int32_t dtype;
+} mtx_seg_attn_args;
+
+/* MTX_OP_CAUSAL_PREFILL_SLOTS (mtx_causal_prefill_slots): the rows > 1 path of mtx_causal_attention for up to MTX_SLOTS_MAX prompts packed
+ * into one qkv buffer [cap_rows][ld_qkv] (q and k already rotated), each into its own EMPTY slot cache: table index s IS slot s, whose caches
+ * are k_cache + s * cache_stride, v_cache + s * cache_stride as in mtx_causal_step_batch_args.  For slot s with L = seg[s + 1] - seg[s],
+ * 1 <= L <= max_len: row i's k and v go to that slot's cache[i] and o [cap_rows][ld_o] gets causal attention inside the segment.  For
+ * L >= 2 the o rows and the slot's cache are, bit for bit, what mtx_causal_attention(rows = L, pos = 0) produces on that slot's operands
+ * alone (one body).  L == 1 runs through the same tile kernel (the single op would take its streaming kernel there), under the op's
+ * rounding contract.  A slot with an empty segment reads and writes nothing, neither its cache nor any o row.  Any L > max_len or a damaged
+ * table: the launch does nothing.  No state block is touched.  Limits of the single op (d == 128, heads % kv_heads == 0: MTX_ERR_UNSUPPORTED;
+ * 16-byte alignment, strides % 8, bf16 / f16); cap_rows < 1: MTX_ERR_INVALID.  Grid: (cap_rows / MTX_CAUSAL_TQ + MTX_SLOTS_MAX, heads). */
+typedef struct mtx_causal_prefill_slots_args {
+  const void* qkv; void* k_cache; void* v_cache; const int32_t* seg; void* o;
+  int32_t cap_rows, heads, kv_heads, d, max_len;
+  int64_t ld_qkv, ld_o, cache_stride;
+  float scale; int32_t dtype;
+} mtx_causal_prefill_slots_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
   MTX_OP_MASK_SELECT = 11, MTX_OP_PREPROC = 12, MTX_OP_YOLO_DECODE = 13, MTX_OP_DETR = 14, MTX_OP_QUANT = 15, MTX_OP_TAIL = 16, MTX_OP_TEXTCOLOR = 17,
   MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19, MTX_OP_CAUSAL_ATTN = 20, MTX_OP_GREEDY = 21,
   MTX_OP_CAUSAL_STEP_BATCH = 22, MTX_OP_GREEDY_BATCH = 23,
-  MTX_OP_ROWLIN_WIDE = 24, MTX_OP_DECODE_ATTN_BATCH = 25, MTX_OP_BEAM_STEP = 26
+  MTX_OP_ROWLIN_WIDE = 24, MTX_OP_DECODE_ATTN_BATCH = 25, MTX_OP_BEAM_STEP = 26,
+  MTX_OP_SEG_ATTN = 27, MTX_OP_CAUSAL_PREFILL_SLOTS = 28
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -747,6 +785,7 @@ typedef struct mtx_op {
     mtx_decode_attn_args dattn; mtx_rowlin_args rowlin; mtx_causal_attn_args cattn; mtx_greedy_args greedy;
     mtx_causal_step_batch_args cstepb; mtx_greedy_batch_args greedyb;
     mtx_decode_attn_batch_args dattnb; mtx_beam_step_args beam;      /* MTX_OP_ROWLIN_WIDE takes `rowlin` */
+    mtx_seg_attn_args segattn; mtx_causal_prefill_slots_args cprefs;
   } u;
 } mtx_op;
 
@@ -799,6 +838,8 @@ MTX_API int mtx_greedy_pick_batch(const mtx_greedy_batch_args* a, void* stream);
 MTX_API int mtx_row_linear_wide(const mtx_rowlin_args* a, void* stream);
 MTX_API int mtx_decode_attention_batch(const mtx_decode_attn_batch_args* a, void* stream);
 MTX_API int mtx_beam_step(const mtx_beam_step_args* a, void* stream);
+MTX_API int mtx_segment_attention(const mtx_seg_attn_args* a, void* stream);
+MTX_API int mtx_causal_prefill_slots(const mtx_causal_prefill_slots_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

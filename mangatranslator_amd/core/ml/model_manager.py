@@ -703,7 +703,9 @@ class ModelManager:
         `paddle_ocr_vl_storage` ("f16" | "bf16") picks the storage type before the first call, `paddle_ocr_vl_slots` (1 .. 8) how
         many crops `extract_text_with_paddle_ocr_vl` decodes together (`PaddleOcrVlHip(slots=)`: a set of key / value caches per slot, about
         44 MB at the published sizes; 1 = one crop at a time, nothing allocated).  The default is 8: of B = 1, 2, 4, 8 it gave the most tokens
-        per second on the MI355X, 5.0 x the single step at a 300-position cache (docs/experiments.md); the texts do not depend on it."""
+        per second on the MI355X, 5.0 x the single step at a 300-position cache (docs/experiments.md); the texts do not depend on it.
+        `paddle_ocr_vl_packed_prefill` (bool, default False; needs slots > 1): all free slots are filled from one packed vision pass and one
+        packed prompt pass on captured fixed-capacity plans (`PaddleOcrVlHip(packed_prefill=)`) instead of a vision and a prefill plan per crop."""
         with self._lock:
             if self.is_loaded(ModelType.PADDLE_OCR_VL):
                 return self.models[ModelType.PADDLE_OCR_VL]
@@ -721,7 +723,10 @@ class ModelManager:
                 slots = getattr(self, "paddle_ocr_vl_slots", 8)
                 if not isinstance(slots, int) or not 1 <= slots <= abi.SLOTS_MAX:
                     raise ModelError(f"paddle_ocr_vl_slots must be an integer 1 .. {abi.SLOTS_MAX}, not {slots!r}")
-                pair = load_pair(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16}[storage], slots=slots)
+                packed = getattr(self, "paddle_ocr_vl_packed_prefill", False)
+                if not isinstance(packed, bool):
+                    raise ModelError(f"paddle_ocr_vl_packed_prefill must be a bool, not {packed!r}")
+                pair = load_pair(root, device=self.device, dtype={"f16": abi.F16, "bf16": abi.BF16}[storage], slots=slots, packed_prefill=packed)
             except ModelError:
                 raise
             except Exception as e:

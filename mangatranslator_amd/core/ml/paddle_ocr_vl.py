@@ -33,6 +33,24 @@ decoder with multimodal rotary positions.
     Memory per slot: t_layers * 2 * (max_prompt + max_new_tokens) * t_kv * 128 * 2 bytes of cache + 4 * vocab of logits + 4 * max_new_tokens
     of output + (heads * 4 rounded up to 256) + heads * ceil(max_len / 64) * 528 bytes of attention workspace — at the wheel's default sizes
     (18 layers, 16 / 2 heads, vocabulary 103 424) and the default 1 344 + 1 024 positions 43.6 MB + 0.4 MB + 0.3 MB = 44.4 MB per slot;
+  * `packed_prefill=True` (needs slots > 1; off by default): what feeds the slots is ONE packed vision pass and ONE packed prompt pass for
+    all the free slots at once instead of a vision and a prefill plan per crop.  The plans have a fixed shape — a patch capacity, a row
+    capacity — and run a packed batch of variable-length sequences whose boundaries (an int32 [9] offset table) and whose per-grid tables
+    (resampled position rows, 2-D rotary rows, the 2 x 2 merge gather indices; token ids, rotary rows, the source row of every stream row)
+    are per-launch DATA the host writes for each pack, so one captured plan serves every combination of crop sizes: MTX_OP_SEG_ATTN in the
+    tower, MTX_OP_CAUSAL_PREFILL_SLOTS (table index = slot, straight into the slot caches) in the decoder, every other op the existing one
+    on more rows.  The fp32 stream is one row gather over [token embeddings | image rows].  Each segment's last row is gathered, the final
+    norm, the head and MTX_OP_GREEDY_BATCH run on `slots` rows against a STAGING state block in which only the slots being filled have
+    done = 0; the filled lanes are then copied into the slot state, so a slot that is decoding is never touched.  A crop's first token,
+    state lane and cache rows do not depend on its companions, its slot, its place in the pack or the rung: row-wise kernels and the two
+    segment kernels give that by construction, and the linears are pinned to a route that does not depend on M (`PACKED_GEMM_FLAGS`:
+    16-bit outputs on whole 256-tiles without the K-slice tail wherever the shape admits that kernel, fp32 outputs on the 128-tile family).
+    Capacities: a ladder of four rungs per plan, a factor of four apart, the top one serving `slots` prompts of `max_prompt`; a rung is
+    built on first use and captured.  The packed plans reuse one set of activation buffers for all layers.  Memory per rung at the wheel's
+    default widths, f16: 37.7 KB per patch of capacity for the vision plan, 46.6 KB per row for the text plan — with slots = 8 and the
+    default max_prompt the rungs are 672 / 2 688 / 10 752 / 43 008 patches = 25 / 101 / 406 MB / 1.6 GB and 168 / 672 / 2 688 / 10 752 rows
+    = 8 / 31 / 125 / 501 MB — plus, once, the fp32 [token embeddings | image rows] buffer (2 * slots * max_prompt rows of t_dim: 88 MB) and a
+    staging row of logits and of output per slot;
   * storage: f16 by default, bf16 selectable — weights and the linears' operands in that type, the residual stream and every norm input fp32.
 
 PARITY UNPINNED (nothing on the build machine can pin them; DESIGN.md's oracle table says the same):
@@ -57,6 +75,19 @@ from . import packing, vit_common
 
 HEAD_DIM = 128                      # the text decoder's head width MTX_OP_CAUSAL_ATTN is built for
 WHAT = "PaddleOCR-VL"
+# the linears of the packed plans: which kernel family runs, and how, must not depend on M (a crop's rows may not depend on its companions).
+# With these flags a 16-bit-output linear takes the 256-tile kernel whenever its shape admits it (K % 64 == 0, 16-byte rows — nothing of M)
+# and never the K-slice tail; fp32-output linears take the 128-tile family whatever M is (csrc/gemm.hip, gemm_route)
+PACKED_GEMM_FLAGS = abi.GEMM_FORCE_TILE256 | abi.GEMM_NO_SPLIT
+PACKED_RUNGS = 4                    # capacities per packed plan, a factor of PACKED_RUNG_RATIO apart
+PACKED_RUNG_RATIO = 4
+
+
+def packed_ladder(top: int) -> List[int]:
+    """the capacities of a packed plan, ascending, multiples of 8, the last one `top`"""
+    top = (int(top) + 7) // 8 * 8
+    rungs = sorted({max(8, (top // PACKED_RUNG_RATIO ** k + 7) // 8 * 8) for k in range(PACKED_RUNGS)})
+    return rungs
 
 
 # ---- checkpoint ---------------------------------------------------------------------------------------------------------------------------------
@@ -247,16 +278,23 @@ def text_rope_table(pos3: torch.Tensor, section: List[int], theta: float, d: int
 # ---- the model ----------------------------------------------------------------------------------------------------------------------------------
 class PaddleOcrVlHip:
     def __init__(self, state_dict: dict, hp: dict, device="cuda", lib=None, dtype: int = abi.F16, graph: bool = True, max_new_tokens: int = 1024,
-                 max_prompt: int = 1280 + 64, check_every: int = 8, route: Optional[Callable[[int, int, int], str]] = None, slots: int = 1):
+                 max_prompt: int = 1280 + 64, check_every: int = 8, route: Optional[Callable[[int, int, int], str]] = None, slots: int = 1,
+                 packed_prefill: bool = False):
         """hp: `hparams_from_config`; state_dict: `normalise_state_dict`'s names.  max_prompt: the longest prompt served (the processor's
         max_pixels bound gives at most 1 280 image tokens; the chat template adds a few tens); the cache holds max_prompt + max_new_tokens.
         slots: how many sequences `generate_many` decodes together (1 .. 8; 1 allocates nothing new), 2 * t_layers * max_len * t_kv * 128
-        elements of cache per slot plus a row of logits and of output (the module docstring has the sum)."""
+        elements of cache per slot plus a row of logits and of output (the module docstring has the sum).
+        packed_prefill: `generate_many` fills all free slots from one packed vision pass and one packed prompt pass (needs slots > 1)."""
         if dtype not in (abi.BF16, abi.F16):
             raise ModelError(f"{WHAT}: storage dtype must be f16 or bf16")
         if not 1 <= int(slots) <= abi.SLOTS_MAX:
             raise ModelError(f"{WHAT}: slots must be 1 .. {abi.SLOTS_MAX}, not {slots!r}")
         self.slots = int(slots)
+        if not isinstance(packed_prefill, bool):
+            raise ModelError(f"{WHAT}: packed_prefill must be a bool, not {packed_prefill!r}")
+        if packed_prefill and self.slots < 2:
+            raise ModelError(f"{WHAT}: packed_prefill fills decode slots and needs slots > 1")
+        self.packed = packed_prefill
         self.lib = lib if lib is not None else get_library()
         self.device = torch.device(device)
         self.hp, self.dtype, self.tdt = hp, dtype, {abi.BF16: torch.bfloat16, abi.F16: torch.float16}[dtype]
@@ -288,6 +326,18 @@ class PaddleOcrVlHip:
             # cos | sin row of rotary position r, all three axes equal: the token fed at cache position p of a prompt sits at r = p + delta
             p = torch.arange(self.max_len)
             self.slot_rope = self._c(text_rope_table(p[None].expand(3, -1), hp["mrope"], hp["theta"], HEAD_DIM).reshape(self.max_len, HEAD_DIM), f32)
+        self._pk_vis, self._pk_txt, self._grid_tables = {}, {}, {}
+        self.last_rungs = None                                       # (patch capacity, row capacity) of the last packed fill
+        if self.packed:
+            B = self.slots
+            self.pk_rows, self.pk_img = B * self.max_prompt, B * self.img_rows.shape[0]      # top capacities: text rows, merged image rows
+            self.pk_vis_ladder, self.pk_txt_ladder = packed_ladder(4 * self.pk_img), packed_ladder(self.pk_rows)
+            self.pk_rows = self.pk_txt_ladder[-1]
+            self.pk_cat = z(self.pk_rows + self.pk_vis_ladder[-1] // 4, C)         # fp32 [token embeddings | image rows]: the stream's gather source
+            self.pk_state = z(abi.SLOT_FIELDS, abi.SLOTS_MAX, dt=i32)            # the staging state block of a fill
+            self.pk_state[abi.SLOT_DONE] = 1
+            self.pk_out = z(B, self.max_new, dt=i32)
+            self.pk_logits = z(B, hp["vocab"])
 
     @classmethod
     def from_directory(cls, root, **kw):
@@ -397,12 +447,22 @@ class PaddleOcrVlHip:
         return plan
 
     # ---- the text decoder ------------------------------------------------------------------------
-    def _layers(self, pb, x, rows, rope, lin, close, slots: int = 0):
+    def _layers(self, pb, x, rows, rope, lin, close, slots: int = 0, packed=None):
         """the decoder layers on `rows` rows of the fp32 stream x; -> the stream after the last layer.  slots = B > 0: the rows are the
-        steps of B independent sequences on the slot caches (MTX_OP_CAUSAL_STEP_BATCH)"""
+        steps of B independent sequences on the slot caches (MTX_OP_CAUSAL_STEP_BATCH).  packed = (seg, pool): the rows are up to SLOTS_MAX
+        whole prompts packed row-wise, prompt s = rows [seg[s], seg[s + 1]) of the device table, into the EMPTY slot cache s
+        (MTX_OP_CAUSAL_PREFILL_SLOTS); every layer then works in the same activation buffers, kept in the dict `pool`"""
         hp = self.hp
         C, heads, kv, I = hp["t_dim"], hp["t_heads"], hp["t_kv"], hp["t_mlp"]
         qw = (heads + 2 * kv) * HEAD_DIM
+        seg, pool = packed if packed is not None else (None, None)
+
+        def buf(key, shape, dt):
+            if pool is None:
+                return pb.buf(shape, dt)
+            if key not in pool:
+                pool[key] = pb.buf(shape, dt)
+            return pool[key]
         ws = None
         if slots:
             ws = pb.buf((slots * abi.causal_ws_bytes(heads, self.max_len),), torch.uint8, zero=True)
@@ -411,10 +471,14 @@ class PaddleOcrVlHip:
         for i, Lr in enumerate(self.t_layers):
             tag = f"dec{i}"
             kc, vc = self.caches[i]
-            a = pb.norm(x, pb.buf((rows, C), self.tdt), rows, C, gamma=Lr["n1"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm1")
+            a = pb.norm(x, buf("norm1", (rows, C), self.tdt), rows, C, gamma=Lr["n1"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm1")
             qkv = lin(a, Lr["qkv"], qw, C, tag + ".qkv")
             pb.qk_rope(Act(qkv.view(1, 1, rows, qw), 1, 1, rows, (heads + kv) * HEAD_DIM), rope, HEAD_DIM, label=tag + ".rope")
-            if slots:
+            if seg is not None:
+                skc, svc = self.slot_caches[i]
+                o = pb.causal_prefill_slots(qkv, skc, svc, seg, buf("attn", (rows, heads * HEAD_DIM), self.tdt), rows, heads, kv, HEAD_DIM, self.max_len,
+                                            HEAD_DIM ** -0.5, label=tag + ".attn")
+            elif slots:
                 skc, svc = self.slot_caches[i]
                 o = pb.causal_step_batch(qkv, skc, svc, self.slot_state, pb.buf((rows, heads * HEAD_DIM), self.tdt), slots, heads, kv, HEAD_DIM, self.max_len,
                                          HEAD_DIM ** -0.5, workspace=ws, label=tag + ".attn")
@@ -422,28 +486,32 @@ class PaddleOcrVlHip:
                 o = pb.causal_attention(qkv, kc, vc, self.state[0:1], pb.buf((rows, heads * HEAD_DIM), self.tdt), rows, heads, kv, HEAD_DIM, self.max_len,
                                         HEAD_DIM ** -0.5, workspace=ws, label=tag + ".attn")
             x1 = close(o, Lr["o"], C, heads * HEAD_DIM, x, tag + ".o_proj")
-            b = pb.norm(x1, pb.buf((rows, C), self.tdt), rows, C, gamma=Lr["n2"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm2")
+            b = pb.norm(x1, buf("norm2", (rows, C), self.tdt), rows, C, gamma=Lr["n2"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label=tag + ".norm2")
             gu = lin(b, Lr["gu"], 2 * I, C, tag + ".gate_up")
             g4 = gu.view(1, 1, rows, 2 * I)
-            hmid = pb.ew(abi.EW_SWIGLU, Act(g4, 1, 1, rows, I, 0), b=Act(g4, 1, 1, rows, I, I), out=Act(pb.buf((1, 1, rows, I), self.tdt), 1, 1, rows, I),
+            hmid = pb.ew(abi.EW_SWIGLU, Act(g4, 1, 1, rows, I, 0), b=Act(g4, 1, 1, rows, I, I), out=Act(buf("swiglu", (1, 1, rows, I), self.tdt), 1, 1, rows, I),
                          label=tag + ".swiglu").t.view(rows, I)
             x = close(hmid, Lr["down"], C, I, x1, tag + ".down")
         return x
 
-    def _head(self, pb, x_last, advance, slots: int = 0):
-        """final norm, the head and the pick on the last row — or, with slots = B > 0, on the B rows of the batched step"""
+    def _head(self, pb, x_last, advance, slots: int = 0, staging: bool = False):
+        """final norm, the head and the pick on the last row — or, with slots = B > 0, on the B rows of the batched step; `staging`: on the B last
+        rows of a packed fill, against the staging logits, state block and output rows"""
         hp = self.hp
         C = hp["t_dim"]
         rows, logits = (slots, self.slot_logits) if slots else (1, self.logits)
+        state, out = (self.slot_state, self.slot_out) if slots else (self.state, self.out)
+        if staging:
+            logits, state, out = self.pk_logits, self.pk_state, self.pk_out
         a = pb.norm(x_last, pb.buf((rows, C), self.tdt), rows, C, gamma=self.W["t_norm"][0], eps=hp["t_eps"], kind=1, dtype=abi.F32, out_dtype=self.dtype, label="final_norm")
         if self.route(1, hp["vocab"], C) == "rowlin":
             pb.row_linear(a, self.W["head"][0], rows, hp["vocab"], C, out=logits, out_f32=True, label="head")
         else:
             pb.gemm(a, self.W["head"][0], rows, hp["vocab"], C, out=logits, out_f32=True, label="head")
         if slots:
-            pb.greedy_pick_batch(logits, self.slot_state, self.slot_out, slots, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
+            pb.greedy_pick_batch(logits, state, out, slots, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
         else:
-            pb.greedy_pick(logits, self.state, self.out, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
+            pb.greedy_pick(logits, state, out, hp["vocab"], self.max_new, eos=hp["eos"], advance=advance)
 
     def _prefill(self, T: int, start: int, n_img: int):
         key = (T, start, n_img)
@@ -515,6 +583,210 @@ class PaddleOcrVlHip:
         self._head(pb, x, advance=1, slots=B)
         self._step_b = pb.build()
         return self._step_b
+
+    # ---- the packed fill (packed_prefill=True) ----------------------------------------------------
+    def _grid(self, gh: int, gw: int):
+        """host tables of one patch grid, kept for the grids seen lately: resampled position rows fp32 [N, C], 2-D rotary rows fp32
+        [N, 2, d / 2], the 2 x 2 merge gather indices int32 [N] (relative to the image's first patch)"""
+        key = (gh, gw)
+        if key in self._grid_tables:
+            self._grid_tables[key] = self._grid_tables.pop(key)      # most recently used last
+            return self._grid_tables[key]
+        from transformers.vision_utils import get_vision_interpolation_indices_and_weights
+        hp = self.hp
+        side = hp["image"] // hp["patch"]
+        idx, wts = get_vision_interpolation_indices_and_weights(torch.tensor([[1, gh, gw]]), num_grid_per_side=side, mode="bilinear", align_corners=True,
+                                                                spatial_merge_size=1)
+        pos = (self.pos_table[idx] * wts[:, :, None].float()).sum(1).to(torch.float32).contiguous()
+        rope = vision_rope_table(gh, gw, hp["v_dim"] // hp["v_heads"])
+        hb, wb, m1, m2 = torch.meshgrid(torch.arange(gh // 2), torch.arange(gw // 2), torch.arange(2), torch.arange(2), indexing="ij")
+        src = ((hb * 2 + m1) * gw + wb * 2 + m2).reshape(-1).to(torch.int32)
+        self._grid_tables[key] = (pos, rope, src)
+        while len(self._grid_tables) > 16:
+            self._grid_tables.pop(next(iter(self._grid_tables)))
+        return self._grid_tables[key]
+
+    def _packed_vision(self, cap: int):
+        """the vision tower, the post norms, the 2 x 2 merge and the projector on `cap` patch rows that hold up to SEGS_MAX images packed row-wise;
+        the merged rows of all images land, packed in the same order, in the image half of `pk_cat`.  Every per-grid table is per-launch data"""
+        if cap in self._pk_vis:
+            return self._pk_vis[cap]
+        hp, W = self.hp, self.W
+        f32 = torch.float32
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        N, C, heads, Ct = cap, hp["v_dim"], hp["v_heads"], hp["t_dim"]
+        d, M = C // heads, cap // 4
+        patches = pb.buf((N, self.patch_kp), self.tdt, zero=True)
+        pos = pb.buf((N, C), f32, zero=True)
+        rope = pb.buf((N, 2, d // 2), f32, zero=True)
+        src = pb.buf((N,), torch.int32, zero=True)
+        seg = pb.buf((abi.SEGS_MAX + 1,), torch.int32, zero=True)
+        act = abi.ACT_GELU_TANH if hp["v_act"] == "gelu_pytorch_tanh" else abi.ACT_GELU
+        ln16, qkv, o, h = pb.buf((N, C), self.tdt), pb.buf((N, 3 * C), self.tdt), pb.buf((N, C), self.tdt), pb.buf((N, hp["v_mlp"]), self.tdt)
+        xa, xb = pb.buf((N, C), f32), pb.buf((N, C), f32)
+
+        def norm16(x, wb, label):
+            return pb.norm(x, ln16, N, C, gamma=wb[0], beta=wb[1], eps=hp["v_eps"], dtype=abi.F32, out_dtype=self.dtype, label=label)
+
+        def linear(a, wb, n, k, out, label, **kw):               # a 16-bit output: the M-independent route
+            return pb.gemm(a, wb[0], N, n, k, bias=wb[2], w_lo=wb[1], out=out, flags=PACKED_GEMM_FLAGS, label=label, **kw)
+
+        def close(a, wb, n, k, res, out, label, rows=N):         # stream <- res + a @ W^T + b in fp32: the 128-tile family whatever M is
+            return pb.gemm(a, wb[0], rows, n, k, bias=wb[2], w_lo=wb[1], res=res, res_f32=True, out_f32=True, out=out, label=label)
+        x = close(patches, W["pe"], C, self.patch_kp, pos, xa, "patch_embed")
+        st = (3 * C, d)
+        for i, Lr in enumerate(self.v_layers):
+            tag = f"vis{i}"
+            linear(norm16(x, Lr["ln1"], tag + ".ln1"), Lr["qkv"], 3 * C, C, qkv, tag + ".qkv")
+            pb.qk_rope(Act(qkv.view(1, 1, N, 3 * C), 1, 1, N, 2 * C), rope, d, label=tag + ".rope")
+            pb.segment_attention(qkv, qkv, qkv, o, seg, heads, d, N, st, st, st, (C, d), 1.0 / math.sqrt(d), k_off=C, v_off=2 * C, label=tag + ".attn")
+            x1 = close(o, Lr["proj"], C, C, x, xb, tag + ".proj")
+            linear(norm16(x1, Lr["ln2"], tag + ".ln2"), Lr["fc1"], hp["v_mlp"], C, h, tag + ".fc1", act=act)
+            x = close(h, Lr["fc2"], C, hp["v_mlp"], x1, xa, tag + ".fc2")
+        y32 = pb.norm(x, xb, N, C, gamma=W["v_ln"][0], beta=W["v_ln"][1], eps=hp["v_eps"], dtype=abi.F32, out_dtype=abi.F32, label="vis.post_ln")
+        y = pb.norm(y32, ln16, N, C, gamma=W["p_ln"][0], beta=W["p_ln"][1], eps=1e-5, dtype=abi.F32, out_dtype=self.dtype, label="proj.pre_norm")
+        # 2 x 2 merge: merged row (hb, wb) of an image = its four source rows side by side, so [N / 4][4 C] is a plain view
+        merged = pb.row_gather(y, o, src, N, C, label="proj.merge")
+        h1 = pb.gemm(merged, W["p1"][0], M, 4 * C, 4 * C, bias=W["p1"][2], w_lo=W["p1"][1], act=abi.ACT_GELU, flags=PACKED_GEMM_FLAGS, label="proj.linear_1")
+        pb.gemm(h1, W["p2"][0], M, Ct, 4 * C, bias=W["p2"][2], w_lo=W["p2"][1], out=self.pk_cat[self.pk_rows:self.pk_rows + M], out_f32=True, label="proj.linear_2")
+        plan = pb.build()
+        plan.patches, plan.pos, plan.rope, plan.src, plan.seg, plan.cap = patches, pos, rope, src, seg, cap
+        self._pk_vis[cap] = plan
+        return plan
+
+    def _packed_text(self, cap: int):
+        """the prompt pass on `cap` stream rows that hold up to `slots` prompts packed row-wise (table index = slot), then the head and the pick on
+        each segment's last row against the staging state block"""
+        if cap in self._pk_txt:
+            return self._pk_txt[cap]
+        hp, B = self.hp, self.slots
+        f32, i32 = torch.float32, torch.int32
+        C, R = hp["t_dim"], cap
+        pb = PlanBuilder(self.lib, self.device, self.dtype)
+        ids, src, last = pb.buf((R,), i32, zero=True), pb.buf((R,), i32, zero=True), pb.buf((abi.SLOTS_MAX,), i32, zero=True)
+        rope = pb.buf((R, 2, HEAD_DIM // 2), f32, zero=True)
+        seg = pb.buf((abi.SLOTS_MAX + 1,), i32, zero=True)
+        e16 = pb.row_gather(self.W["tok"], pb.buf((R, C), self.tdt), ids, R, C, label="embed")
+        pb.cvt_f32(Act(e16.view(1, 1, R, C), 1, 1, R, C), self.dtype, label="embed.f32", out=Act(self.pk_cat[:R].view(1, 1, R, C), 1, 1, R, C))
+        # a text row takes its own embedding, an image placeholder row its merged image row: one gather over [token embeddings | image rows]
+        x = pb.row_gather(self.pk_cat, pb.buf((R, C), f32), src, R, C, label="embed.stream", dtype=abi.F32)
+        pool = {}
+
+        def out_of(label, n, dt):
+            key = label.split(".", 1)[1]
+            if key not in pool:
+                pool[key] = pb.buf((R, n), dt)
+            return pool[key]
+
+        def lin(a, wb, n, k, label):                               # a 16-bit output: the M-independent route
+            return pb.gemm(a, wb[0], R, n, k, out=out_of(label, n, self.tdt), flags=PACKED_GEMM_FLAGS, label=label)
+
+        def close(a, wb, n, k, res, label):                        # fp32 output: the 128-tile family whatever M is
+            return pb.gemm(a, wb[0], R, n, k, res=res, res_f32=True, out_f32=True, out=out_of(label, n, f32), label=label)
+        x = self._layers(pb, x, R, rope, lin, close, packed=(seg, pool))
+        xl = pb.row_gather(x, pb.buf((B, C), f32), last, B, C, label="last_rows", dtype=abi.F32)
+        self._head(pb, xl, advance=1, slots=B, staging=True)
+        plan = pb.build()
+        plan.ids, plan.src, plan.last, plan.rope, plan.seg, plan.cap = ids, src, last, rope, seg, cap
+        self._pk_txt[cap] = plan
+        return plan
+
+    def _prepare(self, item):
+        """what a packed fill needs of one checked item, or the ModelError its prompt earns (placeholders that do not match the grid): no device work"""
+        hp = self.hp
+        ids = item["input_ids"][0].to(torch.long).cpu()
+        thw = item["image_grid_thw"]
+        gh, gw = int(thw[0, 1]), int(thw[0, 2])
+        is_img = ids == hp["image_token"]
+        pos3 = rope_positions(is_img, gh, gw, hp["merge"])
+        T = int(ids.numel())
+        return dict(ids=ids, T=T, gh=gh, gw=gw, is_img=is_img, pos3=pos3, next_rope=max(int(pos3.max()) + 1, 0),
+                    pix=item["pixel_values"].reshape(gh * gw, self.patch_k))
+
+    @staticmethod
+    def _rung(ladder, need, what):
+        for cap in ladder:
+            if cap >= need:
+                return cap
+        raise ModelError(f"{WHAT}: a pack of {need} {what} exceeds the largest packed plan ({ladder[-1]})")
+
+    def _fill_packed(self, assign):
+        """assign: [(slot, prepared item)] for FREE slots, at most one item per slot.  One vision pack (images in the order given), one text pack
+        (prompts in slot order, table index = slot), the pick on a staging state block, then the filled lanes move into the slot state.
+        Nothing of a slot that is not in `assign` is read or written"""
+        hp = self.hp
+        f32, i32 = torch.float32, torch.int32
+        assign = list(assign)
+        assert 1 <= len(assign) <= self.slots and len({s for s, _ in assign}) == len(assign)
+        # ---- vision pack
+        n_patches = sum(p["gh"] * p["gw"] for _, p in assign)
+        vis = self._packed_vision(self._rung(self.pk_vis_ladder, n_patches, "patches"))
+        vseg = torch.zeros(abi.SEGS_MAX + 1, dtype=i32)
+        src = torch.zeros(vis.cap, dtype=i32)
+        pix = torch.zeros(n_patches, self.patch_k)
+        pos = torch.empty(n_patches, hp["v_dim"], dtype=f32)
+        rope = torch.empty(n_patches, 2, hp["v_dim"] // hp["v_heads"] // 2, dtype=f32)
+        off, img_off = 0, {}
+        for k, (slot, p) in enumerate(assign):
+            n = p["gh"] * p["gw"]
+            g_pos, g_rope, g_src = self._grid(p["gh"], p["gw"])
+            pix[off:off + n], pos[off:off + n], rope[off:off + n], src[off:off + n] = p["pix"].to(f32), g_pos, g_rope, g_src + off
+            img_off[slot] = off // 4
+            off += n
+            vseg[k + 1:] = off
+        vis.patches[:n_patches, :self.patch_k].copy_(pix.to(self.tdt))
+        vis.pos[:n_patches].copy_(pos)
+        vis.rope[:n_patches].copy_(rope)
+        vis.src.copy_(src)
+        vis.seg.copy_(vseg)
+        # ---- text pack
+        by_slot = sorted(assign, key=lambda sp: sp[0])
+        n_rows = sum(p["T"] for _, p in by_slot)
+        txt = self._packed_text(self._rung(self.pk_txt_ladder, n_rows, "prompt rows"))
+        tseg = torch.zeros(abi.SLOTS_MAX + 1, dtype=i32)
+        ids, rows_src = torch.zeros(txt.cap, dtype=i32), torch.zeros(txt.cap, dtype=i32)
+        trope = torch.zeros(txt.cap, 2, HEAD_DIM // 2, dtype=f32)
+        last = torch.zeros(abi.SLOTS_MAX, dtype=i32)
+        state = torch.zeros(abi.SLOT_FIELDS, abi.SLOTS_MAX, dtype=i32)
+        state[abi.SLOT_DONE] = 1
+        off = 0
+        for slot, p in by_slot:
+            T = p["T"]
+            ids[off:off + T] = p["ids"].to(i32)
+            own = torch.arange(off, off + T, dtype=i32)
+            image = self.pk_rows + img_off[slot] + torch.arange(int(p["is_img"].sum()), dtype=i32)
+            own[p["is_img"]] = image
+            rows_src[off:off + T] = own
+            trope[off:off + T] = text_rope_table(p["pos3"], hp["mrope"], hp["theta"], HEAD_DIM)
+            off += T
+            tseg[slot + 1:] = off
+            last[slot] = off - 1
+            # the pick advances pos and the rotary row by one: the lane ends at pos = T, n_out = 1, rope row = the prompt's largest position id + 1
+            state[abi.SLOT_POS, slot], state[abi.SLOT_DONE, slot], state[abi.SLOT_ROPE, slot] = T - 1, 0, p["next_rope"] - 1
+        txt.ids.copy_(ids); txt.src.copy_(rows_src); txt.rope.copy_(trope); txt.last.copy_(last); txt.seg.copy_(tseg)
+        self.pk_state.copy_(state)
+        vis.run(graph=self._graph)
+        txt.run(graph=self._graph)
+        for slot, _ in by_slot:
+            self.slot_state[:, slot].copy_(self.pk_state[:, slot])
+            self.slot_out[slot, 0:1].copy_(self.pk_out[slot, 0:1])
+        self.last_rungs = (vis.cap, txt.cap)
+        return [p["T"] for _, p in assign]
+
+    def fill_slots(self, pairs, max_new_tokens: Optional[int] = None):
+        """packed fill of the given FREE slots, [(slot, item)], outside `generate_many` (tests, benchmarks): the item checks of `generate_many`,
+        then one vision pack and one text pack.  -> the prompt lengths"""
+        if not self.packed:
+            raise ModelError(f"{WHAT}: fill_slots needs packed_prefill=True")
+        budget = self.max_new if max_new_tokens is None else int(max_new_tokens)
+        assign = []
+        for slot, item in pairs:
+            if not 0 <= int(slot) < self.slots:
+                raise ModelError(f"{WHAT}: slot {slot!r} is outside 0 .. {self.slots - 1}")
+            self._check_item(item, budget)
+            assign.append((int(slot), self._prepare(item)))
+        with self._lock:
+            return self._fill_packed(assign)
 
     # ---- running ---------------------------------------------------------------------------------
     def _check_inputs(self, input_ids, pixel_values, image_grid_thw, kw):
@@ -618,7 +890,9 @@ class PaddleOcrVlHip:
     def generate_many(self, items, max_new_tokens: Optional[int] = None, check_every: Optional[int] = None) -> list:
         """`generate` for a list of prompts, up to `slots` of them in flight in one batched step plan: -> [int64 [1, T + n] | ModelError], in
         the order given, each tensor exactly what `generate` returns for that item.  A refused item leaves its ModelError in its place and
-        does not stop the others.  The host reads 20 bytes of state per slot every `check_every` steps."""
+        does not stop the others.  The host reads 20 bytes of state per slot every `check_every` steps.  With `packed_prefill` every look at
+        the state fills ALL free slots from the pending list in one vision pack and one text pack (no waiting: a single free slot is filled
+        alone through the same plans); the tokens are then the packed fill's, held to the oracle, not bit for bit `generate`'s."""
         budget = self.max_new if max_new_tokens is None else int(max_new_tokens)
         every = self.check_every if check_every is None else max(1, int(check_every))
         items = list(items)
@@ -648,7 +922,21 @@ class PaddleOcrVlHip:
             self.fill_log = []
             self.slot_state[abi.SLOT_DONE] = 1
             while pending or any(o is not None for o in owner):
-                for s in range(B):
+                assign = []                                          # packed fill: ALL free slots from the pending list in one vision and one text pack
+                for s in ([t for t in range(B) if owner[t] is None] if self.packed else ()):
+                    while pending:
+                        i = pending.pop()
+                        try:
+                            assign.append((s, i, self._prepare(items[i])))
+                            break
+                        except ModelError as e:                      # (a prompt whose placeholders do not match its grid: found before the pack is built,
+                            results[i] = e                           # it takes no slot)
+                if assign:
+                    self._fill_packed([(s, p) for s, _, p in assign])
+                    for s, i, _ in assign:
+                        self.fill_log.append((i, s, [(owner[t], n_out[t]) for t in range(B) if t != s and owner[t] is not None]))
+                        owner[s], n_out[s] = i, 1
+                for s in (() if self.packed else range(B)):
                     while owner[s] is None and pending:
                         i = pending.pop()
                         try:
@@ -691,7 +979,20 @@ class PaddleOcrVlHip:
         self._stepper().run(graph=self._graph)
         return self.logits[0].float().cpu().clone()
 
+    def slot_step_logits(self, slot: int, token: int) -> torch.Tensor:
+        """teacher forcing on the batched stepper (parity tests): feed `token` at slot `slot`'s current position instead of the model's own pick
+        -> fp32 logits [vocab] of the next.  The other slots keep their lanes (a finished or empty one sits out)"""
+        st = self.slot_state.cpu()
+        st[abi.SLOT_NOUT, slot], st[abi.SLOT_DONE, slot], st[abi.SLOT_TOKEN, slot] = 0, 0, int(token)
+        self.slot_state.copy_(st)
+        self._stepper_batch().run(graph=self._graph)
+        return self.slot_logits[slot].float().cpu().clone()
+
     def close(self):
+        for p in [*self._pk_vis.values(), *self._pk_txt.values()]:
+            p.close()
+        self._pk_vis.clear()
+        self._pk_txt.clear()
         for p in [self._step, self._step_b, *self._vis.values(), *self._pre.values()]:
             if p is not None:
                 p.close()

@@ -11,6 +11,8 @@
 // row (col = lane & 15) in S^T and in O^T, so the running max / sum / rescale are lane-local
 // (two xor-shuffles across the four 16-lane quads finish a row reduction), and P goes from the
 // S^T accumulators straight into the next MFMA's B operand without touching LDS.
+// The same body (attn_body.inc) serves attn_seg_kernel: up to MTX_SEGS_MAX sequences packed row-wise into one buffer, the boundaries in a
+// DEVICE table, one launch whatever the lengths (PaddleOCR-VL's vision tower over several crops).
 #include "mtx_device.h"
 #include <cstdlib>
 #include <type_traits>
@@ -43,185 +45,11 @@ constexpr int AT_QB = 128;     // query rows per workgroup
 // DP = head dim padded to a multiple of 32 (zero-filled); K row = SLOTS 16-byte slots.
 template <typename T, int DP>
 __global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
-  typedef typename Traits<T>::v8 v8;
-  typedef typename Traits<T>::v4 v4;
-  constexpr int KST = DP / 32;                 // k-steps of the S^T product
-  constexpr int DF = DP / 16;                  // d fragments of O^T
-  constexpr int SLOTS = DP <= 64 ? 8 : 16;
-  constexpr int KROW = SLOTS * 16;             // bytes per K row in LDS
-  constexpr int K_BYTES = AT_KV * KROW;
-  constexpr int VT_BYTES = DP * 128;           // [DP rows][64 keys] T
-  __shared__ __attribute__((aligned(16))) unsigned char smem[K_BYTES + VT_BYTES];
-  unsigned char* Ks = smem;
-  unsigned char* Vt = smem + K_BYTES;
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, q4 = lane >> 4;
-  const long bh = blockIdx.x / p.qblocks;
-  const long qb = blockIdx.x % p.qblocks;
-  const long b = bh / p.heads, h = bh % p.heads;
-  const long q0 = qb * AT_QB + wv * AT_QW;
-  const T* Q = reinterpret_cast<const T*>(p.q) + b * p.q_bs + h * p.q_hs;
-  const T* K = reinterpret_cast<const T*>(p.k) + b * p.k_bs + h * p.k_hs;
-  const T* V = reinterpret_cast<const T*>(p.v) + b * p.v_bs + h * p.v_hs;
-  T* O = reinterpret_cast<T*>(p.o) + b * p.o_bs + h * p.o_hs;
-  const int dch = (int)(p.d / 8);              // valid 16-byte chunks per row
-
-  // Q fragments (B operand: col = query row, 8 consecutive d per lane), kept in registers
-  v8 qf[2][KST];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int ks = 0; ks < KST; ++ks) {
-      const long qr = q0 + f * 16 + l15;
-      const int ch = ks * 4 + q4;
-      u32x4 raw = u32x4{0u, 0u, 0u, 0u};
-      if (qr < p.sq && ch < dch) raw = *reinterpret_cast<const u32x4*>(Q + qr * p.q_ss + ch * 8);
-      qf[f][ks] = __builtin_bit_cast(v8, raw);
-    }
-
-  f32x4 oacc[2][DF];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int d = 0; d < DF; ++d) oacc[f][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float mrun[2] = {-1.0e30f, -1.0e30f};
-  float lrun[2] = {0.f, 0.f};
-
-  constexpr int KCH = AT_KV * (DP / 8);        // 16-byte chunks per K (or V) tile
-  constexpr int NLD = (KCH + 255) / 256;
-  u32x4 rk[NLD], rv[NLD];
-  auto load_tile = [&](long k0) {
-#pragma unroll
-    for (int it = 0; it < NLD; ++it) {
-      const int idx = tid + it * 256;
-      const int ch = idx % (DP / 8), row = idx / (DP / 8);
-      u32x4 a = u32x4{0u, 0u, 0u, 0u}, c = u32x4{0u, 0u, 0u, 0u};
-      if (idx < KCH && k0 + row < p.sk && ch < dch) {
-        a = *reinterpret_cast<const u32x4*>(K + (k0 + row) * p.k_ss + ch * 8);
-        c = *reinterpret_cast<const u32x4*>(V + (k0 + row) * p.v_ss + ch * 8);
-      }
-      rk[it] = a; rv[it] = c;
-    }
-  };
-
-  const long ntiles = (p.sk + AT_KV - 1) / AT_KV;
-  load_tile(0);
-  for (long t = 0; t < ntiles; ++t) {
-    const long k0 = t * AT_KV;
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < NLD; ++it) {
-      const int idx = tid + it * 256;
-      if (idx < KCH) {
-        const int ch = idx % (DP / 8), row = idx / (DP / 8);
-        *reinterpret_cast<u32x4*>(Ks + row * KROW + ((ch ^ (row & (SLOTS - 1))) << 4)) = rk[it];
-        // V transposed: Vt[d][key], 8-byte granules (4 keys) XOR-swizzled by (d & 15)
-        const typename Traits<T>::v8 vv = __builtin_bit_cast(v8, rv[it]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int dr = ch * 8 + e;
-          *reinterpret_cast<T*>(Vt + dr * 128 + ((((row >> 2) ^ (dr & 15))) << 3) + ((row & 3) << 1)) = vv[e];
-        }
-      }
-    }
-    __syncthreads();
-    if (t + 1 < ntiles) load_tile(k0 + AT_KV);
-
-    // ---- S^T = K Q^T : sacc[f][kf] holds keys kf*16 + q4*4 + r for query f*16 + l15 -----------
-    f32x4 sacc[2][4];
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int kf = 0; kf < 4; ++kf) sacc[f][kf] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KST; ++ks) {
-      const int ch = ks * 4 + q4;
-#pragma unroll
-      for (int kf = 0; kf < 4; ++kf) {
-        const int row = kf * 16 + l15;
-        const v8 kfr = *reinterpret_cast<const v8*>(Ks + row * KROW + ((ch ^ (row & (SLOTS - 1))) << 4));
-#pragma unroll
-        for (int f = 0; f < 2; ++f) sacc[f][kf] = Traits<T>::mfma(kfr, qf[f][ks], sacc[f][kf]);
-      }
-    }
-
-    // ---- online softmax (base-2), lane-local per query row --------------------------------------
-    v8 pb[2][2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      float tmax = -1.0e30f;
-#pragma unroll
-      for (int kf = 0; kf < 4; ++kf)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long key = k0 + kf * 16 + q4 * 4 + r;
-          float s = sacc[f][kf][r] * p.scale_log2;
-          if (key >= p.sk) s = -1.0e30f;
-          sacc[f][kf][r] = s;
-          tmax = s > tmax ? s : tmax;
-        }
-      { float o1 = __shfl_xor(tmax, 16, 64); tmax = o1 > tmax ? o1 : tmax; }
-      { float o2 = __shfl_xor(tmax, 32, 64); tmax = o2 > tmax ? o2 : tmax; }
-      const float mnew = tmax > mrun[f] ? tmax : mrun[f];
-      const float alpha = exp2f(mrun[f] - mnew);
-      mrun[f] = mnew;
-      float psum = 0.f;
-#pragma unroll
-      for (int kf = 0; kf < 4; ++kf)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = exp2f(sacc[f][kf][r] - mnew);
-          psum += pv;
-          // B operand of O^T = V^T P^T: k-slot q4*8 + e  <->  key (kk*32) + (e<4 ? q4*4+e : 16+q4*4+e-4)
-          pb[f][kf >> 1][(kf & 1) * 4 + r] = from_f32<T>(pv);
-        }
-      lrun[f] = lrun[f] * alpha + psum;
-#pragma unroll
-      for (int d = 0; d < DF; ++d) {
-        oacc[f][d][0] *= alpha; oacc[f][d][1] *= alpha; oacc[f][d][2] *= alpha; oacc[f][d][3] *= alpha;
-      }
-    }
-
-    // ---- O^T += V^T P^T ------------------------------------------------------------------------
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-      for (int d = 0; d < DF; ++d) {
-        const int dr = d * 16 + l15;
-        const int g0 = kk * 8 + q4;            // granule of keys kk*32 + q4*4 .. +3
-        const int g1 = kk * 8 + 4 + q4;        // granule of keys kk*32 + 16 + q4*4 .. +3
-        const v4 lo = *reinterpret_cast<const v4*>(Vt + dr * 128 + ((g0 ^ (dr & 15)) << 3));
-        const v4 hi = *reinterpret_cast<const v4*>(Vt + dr * 128 + ((g1 ^ (dr & 15)) << 3));
-        v8 vf;
-        vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-        vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) oacc[f][d] = Traits<T>::mfma(vf, pb[f][kk], oacc[f][d]);
-      }
-    }
-  }
-
-  // ---- finish: row sums across the 4 quads, normalise, store 4 consecutive d per lane ----------
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    float l = lrun[f];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    const long qr = q0 + f * 16 + l15;
-    if (qr < p.sq) {
-#pragma unroll
-      for (int d = 0; d < DF; ++d) {
-        const int dc = d * 16 + q4 * 4;
-        if (dc < p.d) {
-          v4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = from_f32<T>(oacc[f][d][r] * inv);
-          *reinterpret_cast<v4*>(O + qr * p.o_ss + dc) = o;
-        }
-      }
-    }
-  }
+#define ATTN_BODY_BH blockIdx.x / p.qblocks
+#define ATTN_BODY_QB blockIdx.x % p.qblocks
+#include "attn_body.inc"
+#undef ATTN_BODY_BH
+#undef ATTN_BODY_QB
 }
 
 // =====================================================================================================
@@ -750,6 +578,51 @@ __global__ __launch_bounds__(256) void attn_merge_q8_kernel(AttnParams p) {
   }
 }
 
+// ---- attention over packed segments (MTX_OP_SEG_ATTN) ----------------------------------------------------------------------------------------
+// The short kernel for up to MTX_SEGS_MAX sequences packed row-wise into one buffer; segment s is rows [seg[s], seg[s + 1]) of a DEVICE table.
+// Grid: heads x (cap_rows / AT_QB + MTX_SEGS_MAX) query blocks — sum_s ceil(len_s / AT_QB) never exceeds that — so the launch does not depend
+// on the lengths.  A workgroup walks the nine offsets, takes the segment its block index falls into and runs attn_body.inc on that segment's
+// rows as a sequence of its own: a segment's rows are bit for bit attn_kernel's.  A damaged table or a surplus block leaves before any barrier.
+struct AttnSegParams {
+  const unsigned char* q; const unsigned char* k; const unsigned char* v; unsigned char* o; const int* seg;
+  long heads, d, cap_rows;
+  long q_ss, q_hs, k_ss, k_hs, v_ss, v_hs, o_ss, o_hs;
+  float scale_log2;
+  unsigned qblocks;              // cap_rows / AT_QB + MTX_SEGS_MAX
+};
+
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void attn_seg_kernel(AttnSegParams s) {
+  const long head = blockIdx.x / s.qblocks;
+  long vb = blockIdx.x % s.qblocks;
+  // (workgroup-uniform) the table is checked whole before anything else is touched
+  long prev = s.seg[0], row0 = 0, len = -1;
+  bool ok = prev >= 0;
+#pragma unroll
+  for (int i = 0; i < MTX_SEGS_MAX; ++i) {
+    const long next = s.seg[i + 1];
+    ok = ok && next >= prev;
+    const long nb = (next - prev + AT_QB - 1) / AT_QB;
+    if (ok && len < 0) {
+      if (vb < nb) { row0 = prev; len = next - prev; }
+      else vb -= nb;
+    }
+    prev = next;
+  }
+  if (!ok || prev > s.cap_rows || len < 0) return;
+  AttnParams p = {};
+  p.q = s.q + row0 * s.q_ss * (long)sizeof(T); p.k = s.k + row0 * s.k_ss * (long)sizeof(T);
+  p.v = s.v + row0 * s.v_ss * (long)sizeof(T); p.o = s.o + row0 * s.o_ss * (long)sizeof(T);
+  p.batch = 1; p.heads = s.heads; p.sq = len; p.sk = len; p.d = s.d;
+  p.q_ss = s.q_ss; p.q_hs = s.q_hs; p.k_ss = s.k_ss; p.k_hs = s.k_hs; p.v_ss = s.v_ss; p.v_hs = s.v_hs; p.o_ss = s.o_ss; p.o_hs = s.o_hs;
+  p.scale_log2 = s.scale_log2;
+#define ATTN_BODY_BH head
+#define ATTN_BODY_QB vb
+#include "attn_body.inc"
+#undef ATTN_BODY_BH
+#undef ATTN_BODY_QB
+}
+
 // kernel family (MTX_ATTN_ROUTE_LONG, or the short kernel's padded head width), MTX_ATTN_ROUTE_* flags, n_full, split of this thread's last launch
 static thread_local int g_last_route[4] = {0, 0, 0, 1};
 void attn_last_route(int* out) { for (int i = 0; i < 4; ++i) out[i] = g_last_route[i]; }
@@ -839,6 +712,34 @@ int attn_launch(const mtx_attn_args* a, void* stream, const char** err) {
   int rc = MTX_OK;
   if (!with_storage_type(a->dtype, [&](auto t) { rc = launch_attn_t<typename decltype(t)::type>(p, stream); })) { *err = "attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
   return rc;
+}
+
+int seg_attn_launch(const mtx_seg_attn_args* a, void* stream, const char** err) {
+  if (!a->q || !a->k || !a->v || !a->o || !a->seg) { *err = "segment_attention: null operand"; return MTX_ERR_INVALID; }
+  if (a->dtype != MTX_BF16 && a->dtype != MTX_F16) { *err = "segment_attention: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  if (a->d < 8 || a->d > 96 || a->d % 8) { *err = "segment_attention: built for head dims that are multiples of 8, <= 96"; return MTX_ERR_UNSUPPORTED; }
+  if (a->q_ss % 8 || a->k_ss % 8 || a->v_ss % 8 || a->o_ss % 4 || a->q_hs % 8 || a->k_hs % 8 || a->v_hs % 8 || a->o_hs % 4) {
+    *err = "segment_attention: strides must keep 16-byte alignment"; return MTX_ERR_INVALID; }
+  if ((((size_t)a->q | (size_t)a->k | (size_t)a->v) & 15) != 0 || ((size_t)a->o & 7) != 0 || ((size_t)a->seg & 3) != 0) {
+    *err = "segment_attention: q, k, v must be 16-byte aligned, o 8-byte aligned"; return MTX_ERR_INVALID; }
+  if (a->heads < 1 || a->cap_rows < 1) { *err = "segment_attention: empty problem"; return MTX_ERR_INVALID; }
+  const int64_t qblocks = a->cap_rows / AT_QB + MTX_SEGS_MAX;
+  if (a->cap_rows > 0x7fffffffLL || a->heads * qblocks > 0x7fffffffLL) { *err = "segment_attention: too many rows or heads"; return MTX_ERR_INVALID; }
+  AttnSegParams p;
+  p.q = (const unsigned char*)a->q; p.k = (const unsigned char*)a->k; p.v = (const unsigned char*)a->v; p.o = (unsigned char*)a->o;
+  p.seg = a->seg;
+  p.heads = a->heads; p.d = a->d; p.cap_rows = a->cap_rows;
+  p.q_ss = a->q_ss; p.q_hs = a->q_hs; p.k_ss = a->k_ss; p.k_hs = a->k_hs; p.v_ss = a->v_ss; p.v_hs = a->v_hs; p.o_ss = a->o_ss; p.o_hs = a->o_hs;
+  p.scale_log2 = a->scale * 1.4426950408889634f;          // as attn_launch forms it
+  p.qblocks = (unsigned)qblocks;
+  const unsigned grid = (unsigned)(a->heads * qblocks);
+  with_storage_type(a->dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if (p.d <= 32) MTX_LAUNCH((attn_seg_kernel<T, 32>), dim3(grid), dim3(256), 0, stream, p);
+    else if (p.d <= 64) MTX_LAUNCH((attn_seg_kernel<T, 64>), dim3(grid), dim3(256), 0, stream, p);
+    else MTX_LAUNCH((attn_seg_kernel<T, 96>), dim3(grid), dim3(256), 0, stream, p);
+  });
+  return MTX_OK;
 }
 
 }  // namespace mtx

@@ -19,6 +19,10 @@
 //                       mtx_greedy_batch_args): the slot is folded into the grid, every slot has its own cache, workspace region and lane of
 //                       the int32 [5][8] state block; the step's body is causal_step_body.inc, included in both step kernels, so a slot's
 //                       result is bit for bit the single op's.  A finished or empty slot leaves before any barrier or ticket.
+//   packed prompts      the prefill for up to MTX_SLOTS_MAX prompts packed row-wise into one qkv buffer, each into its own empty slot cache, in
+//                       one launch (mtx_causal_prefill_slots_args): the boundaries are a DEVICE table of row offsets, the grid is sized from
+//                       the buffer's capacity, a workgroup finds its prompt by walking the table; the body is causal_prefill_body.inc, included
+//                       in both prefill kernels, so a prompt's rows and cache are bit for bit the single op's at pos = 0.
 #include "mtx_device.h"
 #include <limits.h>
 
@@ -49,139 +53,11 @@ template <> __device__ __forceinline__ void p_split<_Float16>(float p, _Float16&
 
 template <typename T>
 __global__ __launch_bounds__(256) void causal_prefill_kernel(mtx_causal_attn_args p) {
-  typedef typename Traits<T>::v8 v8;
-  typedef typename Traits<T>::v4 v4;
-  __shared__ u32x4 Vs4[CA_TK * CA_VROW / 8];
-  T* Vs = reinterpret_cast<T*>(Vs4);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, q4 = lane >> 4;
-  const int pos = *p.pos;
-  if (pos < 0 || pos > p.max_len - p.rows) return;                 // (workgroup-uniform) nothing is read or written outside the cache
-  const int G = p.heads / p.kv_heads;
-  const int h = blockIdx.y, kvh = h / G;
-  const int q0 = blockIdx.x * CA_TQ;
-  const long kvw = (long)p.kv_heads * CA_D;
-  const T* QKV = reinterpret_cast<const T*>(p.qkv);
-  const long koff = (long)p.heads * CA_D + (long)kvh * CA_D, voff = koff + kvw;
-  T* KC = reinterpret_cast<T*>(p.k_cache) + (long)kvh * CA_D;
-  T* VC = reinterpret_cast<T*>(p.v_cache) + (long)kvh * CA_D;
-
-  // the rows' k and v go to cache[pos + i], once per kv head (nobody reads those positions in this launch)
-  if (h % G == 0) {
-    for (int it = tid; it < CA_TQ * 32; it += 256) {
-      const int ch = it & 15, row = (it >> 4) & (CA_TQ - 1), which = it >> 10;
-      const int qi = q0 + row;
-      if (qi < p.rows) {
-        const T* src = QKV + (long)qi * p.ld_qkv + (which ? voff : koff) + ch * 8;
-        T* dst = (which ? VC : KC) + (long)(pos + qi) * kvw + ch * 8;
-        *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
-      }
-    }
-  }
-
-  const int qw0 = q0 + wave * 16;                                   // the wave's first query row
-  const bool wave_active = qw0 < p.rows;
-  const int qi = qw0 + l15;
-  const int qc = qi < p.rows ? qi : p.rows - 1;                     // rows past the end compute on the last row and are not stored
-  const int kmax = pos + p.rows - 1;                                // the last key of the launch
-  const int wave_last = pos + (qw0 + 15 < p.rows ? qw0 + 15 : p.rows - 1);      // the last key any row of this wave may see
-  const int wg_last = pos + (q0 + CA_TQ - 1 < p.rows ? q0 + CA_TQ - 1 : p.rows - 1);
-  const int ntiles = wg_last / CA_TK + 1;                           // key tiles wholly in the future are skipped
-
-  v8 qf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const v8*>(QKV + (long)qc * p.ld_qkv + (long)h * CA_D + ks * 32 + q4 * 8);
-
-  f32x4 ohi[8], olo[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) { ohi[d] = f32x4{0.f, 0.f, 0.f, 0.f}; olo[d] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  float m = CA_NEG, l = 0.f;
-
-  for (int t = 0; t < ntiles; ++t) {
-    const int j0 = t * CA_TK;
-    __syncthreads();                                                // the previous tile's V reads are done
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int idx = tid + it * 256, ch = idx & 15, row = idx >> 4;
-      int j = j0 + row;
-      j = j < kmax ? j : kmax;                                      // keys past the launch repeat the last one: their weight is 0
-      const T* src = j < pos ? VC + (long)j * kvw : QKV + (long)(j - pos) * p.ld_qkv + voff;
-      *reinterpret_cast<u32x4*>(Vs + row * CA_VROW + ch * 8) = *reinterpret_cast<const u32x4*>(src + ch * 8);
-    }
-    __syncthreads();
-    if (!wave_active || j0 > wave_last) continue;                   // (wave-uniform) this wave's rows end before the tile
-
-    // ---- S^T = K Q^T: sacc[s][r] is key j0 + 16 s + 4 q4 + r for query row l15
-    f32x4 sacc[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      sacc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-      int j = j0 + s * 16 + l15;
-      j = j < kmax ? j : kmax;
-      const T* kp = (j < pos ? KC + (long)j * kvw : QKV + (long)(j - pos) * p.ld_qkv + koff) + q4 * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) sacc[s] = Traits<T>::mfma(*reinterpret_cast<const v8*>(kp + ks * 32), qf[ks], sacc[s]);
-    }
-
-    // ---- online softmax; the mask is causal: key j counts for row i iff j <= pos + i
-    float sc[8];
-    float tmax = CA_NEG;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int key = j0 + (e >> 2) * 16 + q4 * 4 + (e & 3);
-      const float s = key <= pos + qc ? sacc[e >> 2][e & 3] * p.scale : CA_NEG;
-      sc[e] = s;
-      tmax = s > tmax ? s : tmax;
-    }
-    { const float o1 = __shfl_xor(tmax, 16, 64); tmax = o1 > tmax ? o1 : tmax; }
-    { const float o2 = __shfl_xor(tmax, 32, 64); tmax = o2 > tmax ? o2 : tmax; }
-    const float mnew = tmax > m ? tmax : m;
-    const float alpha = __expf(m - mnew);
-    m = mnew;
-    v8 phi, plo;
-    float psum = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int key = j0 + (e >> 2) * 16 + q4 * 4 + (e & 3);
-      const float pv = key <= pos + qc ? __expf(sc[e] - mnew) : 0.f;      // (a masked key weighs 0 even while the row has seen no key at all)
-      psum += pv;
-      T hi, lo;
-      p_split<T>(pv, hi, lo);
-      phi[e] = hi; plo[e] = lo;                                     // k-slot 8 q4 + e  <->  key j0 + (e < 4 ? 4 q4 + e : 16 + 4 q4 + e - 4)
-    }
-    l = l * alpha + psum;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { ohi[d][r] *= alpha; olo[d][r] *= alpha; }
-    }
-
-    // ---- O^T += V^T P^T: lane (l15, q4) receives V[4 q4 + 0..3][16 d + l15] and V[16 + 4 q4 + 0..3][16 d + l15]
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      const T* a = Vs + (q4 * 4 + (l15 >> 2)) * CA_VROW + d * 16 + (l15 & 3) * 4;
-      const v4 v0 = lds_read_tr16<T>(a);
-      const v4 v1 = lds_read_tr16<T>(a + 16 * CA_VROW);
-      v8 vf;
-      vf[0] = v0[0]; vf[1] = v0[1]; vf[2] = v0[2]; vf[3] = v0[3];
-      vf[4] = v1[0]; vf[5] = v1[1]; vf[6] = v1[2]; vf[7] = v1[3];
-      ohi[d] = Traits<T>::mfma(vf, phi, ohi[d]);
-      olo[d] = Traits<T>::mfma(vf, plo, olo[d]);
-    }
-  }
-
-  // ---- row sums across the 4 quads, normalise, store 4 consecutive d per lane
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
-  if (qi < p.rows) {
-    T* O = reinterpret_cast<T*>(p.o) + (long)qi * p.ld_o + (long)h * CA_D + q4 * 4;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      v4 o;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = from_f32<T>((ohi[d][r] + olo[d][r] * LoScale<T>::inv) / l);      // l >= 1: the key at the running maximum weighs exp(0)
-      *reinterpret_cast<v4*>(O + d * 16) = o;
-    }
-  }
+#define CA_PREFILL_POS *p.pos
+#define CA_PREFILL_QB blockIdx.x
+#include "causal_prefill_body.inc"
+#undef CA_PREFILL_POS
+#undef CA_PREFILL_QB
 }
 
 // ---- the step --------------------------------------------------------------------------------------------------------------------------
@@ -405,6 +281,63 @@ int greedy_batch_launch(const mtx_greedy_batch_args* a, void* stream, const char
   const int chunks = (int)(((long)a->vocab + MTX_GREEDY_CHUNK - 1) / MTX_GREEDY_CHUNK);
   MTX_LAUNCH(greedy_chunk_batch_kernel<MTX_SLOTS_MAX>, dim3((unsigned)chunks, (unsigned)a->slots), dim3(256), 0, stream, *a, chunks);
   MTX_LAUNCH(greedy_final_batch_kernel<MTX_SLOTS_MAX>, dim3((unsigned)a->slots), dim3(64), 0, stream, *a, chunks);
+  return MTX_OK;
+}
+
+// ---- the packed prompt pass (MTX_OP_CAUSAL_PREFILL_SLOTS) ------------------------------------------------------------------------------------
+// causal_prefill_kernel for up to MTX_SLOTS_MAX prompts packed into one qkv buffer, prompt s = rows [seg[s], seg[s + 1]) of a DEVICE table,
+// each into its own empty slot cache.  Grid (cap_rows / CA_TQ + MTX_SLOTS_MAX, heads): sum_s ceil(L_s / CA_TQ) never exceeds the first
+// figure, so the launch does not depend on the lengths.  A workgroup walks the nine offsets, takes the slot its block index falls into and
+// runs causal_prefill_body.inc on that slot's rows and cache at pos = 0.  A damaged table, a prompt longer than the cache or a surplus block
+// leaves before any barrier.  (Templates behind every kernel the module held before.)
+template <typename T>
+__global__ __launch_bounds__(256) void causal_prefill_slots_kernel(mtx_causal_prefill_slots_args b) {
+  long vb = blockIdx.x;
+  // (workgroup-uniform) the table is checked whole before anything else is touched
+  long prev = b.seg[0], row0 = 0, len = -1;
+  int slot = 0;
+  bool ok = prev >= 0;
+#pragma unroll
+  for (int i = 0; i < MTX_SLOTS_MAX; ++i) {
+    const long next = b.seg[i + 1];
+    ok = ok && next >= prev && next - prev <= (long)b.max_len;
+    const long nb = (next - prev + CA_TQ - 1) / CA_TQ;
+    if (ok && len < 0) {
+      if (vb < nb) { row0 = prev; len = next - prev; slot = i; }
+      else vb -= nb;
+    }
+    prev = next;
+  }
+  if (!ok || prev > (long)b.cap_rows || len < 0) return;
+  mtx_causal_attn_args p;
+  p.qkv = reinterpret_cast<const T*>(b.qkv) + row0 * b.ld_qkv;
+  p.k_cache = reinterpret_cast<T*>(b.k_cache) + (long)slot * b.cache_stride;
+  p.v_cache = reinterpret_cast<T*>(b.v_cache) + (long)slot * b.cache_stride;
+  p.pos = nullptr;
+  p.o = reinterpret_cast<T*>(b.o) + row0 * b.ld_o;
+  p.rows = (int)len; p.heads = b.heads; p.kv_heads = b.kv_heads; p.d = b.d; p.max_len = b.max_len;
+  p.ld_qkv = b.ld_qkv; p.ld_o = b.ld_o;
+  p.scale = b.scale; p.dtype = b.dtype;
+  p.workspace = nullptr; p.workspace_bytes = 0;
+#define CA_PREFILL_POS 0
+#define CA_PREFILL_QB (unsigned)vb
+#include "causal_prefill_body.inc"
+#undef CA_PREFILL_POS
+#undef CA_PREFILL_QB
+}
+
+int causal_prefill_slots_launch(const mtx_causal_prefill_slots_args* a, void* stream, const char** err) {
+  if (!a->qkv || !a->k_cache || !a->v_cache || !a->seg || !a->o) { *err = "causal_prefill_slots: null operand"; return MTX_ERR_INVALID; }
+  if (a->d != CA_D) { *err = "causal_prefill_slots: only head width 128 is built"; return MTX_ERR_UNSUPPORTED; }
+  if (a->heads < 1 || a->kv_heads < 1 || a->heads % a->kv_heads) { *err = "causal_prefill_slots: heads must be a multiple of kv_heads"; return MTX_ERR_UNSUPPORTED; }
+  if (a->heads > 65535 || a->max_len < 1 || a->cap_rows < 1) { *err = "causal_prefill_slots: needs cap_rows >= 1, max_len >= 1, heads <= 65535"; return MTX_ERR_INVALID; }
+  const long qkv_w = ((long)a->heads + 2L * a->kv_heads) * CA_D;
+  if (a->ld_qkv % 8 || a->ld_o % 8 || a->ld_qkv < qkv_w || a->ld_o < (long)a->heads * CA_D) { *err = "causal_prefill_slots: row strides must be multiples of 8 and cover the row"; return MTX_ERR_INVALID; }
+  if (a->cache_stride % 8 || a->cache_stride < (long)a->max_len * a->kv_heads * CA_D) { *err = "causal_prefill_slots: cache_stride must be a multiple of 8 and cover one cache"; return MTX_ERR_INVALID; }
+  if ((((size_t)a->qkv | (size_t)a->k_cache | (size_t)a->v_cache | (size_t)a->o) & 15) != 0 || ((size_t)a->seg & 3) != 0) { *err = "causal_prefill_slots: operands must be 16-byte aligned"; return MTX_ERR_INVALID; }
+  if (a->dtype != MTX_BF16 && a->dtype != MTX_F16) { *err = "causal_prefill_slots: dtype must be bf16 or f16"; return MTX_ERR_INVALID; }
+  const dim3 grid((unsigned)(a->cap_rows / CA_TQ + MTX_SLOTS_MAX), (unsigned)a->heads);
+  MTX_LAUNCH_T(a->dtype, causal_prefill_slots_kernel, grid, dim3(256), stream, *a);
   return MTX_OK;
 }
 

@@ -353,7 +353,8 @@ class PlanBuilder:
         if res_f32:
             assert out_f32 and res is not None
             g.res_dtype = abi.F32
-        if ((m >= 2048 and n >= 1024 and k >= 512) or (m >= 256 and k >= 8192) or (flags & abi.GEMM_FORCE_TILE256)) and batch == 1 and not out_f32:
+        whole_tiles = (flags & abi.GEMM_FORCE_TILE256) and (flags & abi.GEMM_NO_SPLIT)      # forced onto whole 256-tiles: the scratch would never be used
+        if ((m >= 2048 and n >= 1024 and k >= 512) or (m >= 256 and k >= 8192) or (flags & abi.GEMM_FORCE_TILE256)) and batch == 1 and not out_f32 and not whole_tiles:
             # large problems: one shared scratch per plan for the K-slice tail of the 256-tile kernel (ops of a plan run in order)
             # (side-lane ops run beside main-lane ops: they get a scratch of their own)
             ws_name = "_gemm_ws_side" if self._side else "_gemm_ws"
@@ -476,6 +477,38 @@ class PlanBuilder:
             a.eos[i] = e
         self._add(abi.OP_GREEDY_BATCH, a, label)
         return state
+
+    def segment_attention(self, q, k, v, o, seg, heads, d, cap_rows, q_str, k_str, v_str, o_str, scale, q_off=0, k_off=0, v_off=0, o_off=0,
+                          label="seg_attn"):
+        """MTX_OP_SEG_ATTN: non-causal attention over up to SEGS_MAX sequences packed row-wise into [cap_rows] rows; `seg` (int32
+        [SEGS_MAX + 1] row offsets) lives on the device, so the recorded op serves every combination of lengths.  *_str = (row stride, head
+        stride) in elements.  A segment's rows are bit for bit `attention`'s (batch 1, short kernel) on that segment alone"""
+        assert seg.dtype == torch.int32 and seg.numel() >= abi.SEGS_MAX + 1 and seg.is_contiguous()
+        a = abi.SegAttnArgs()
+        a.q, a.k, a.v, a.o, a.seg = _ptr(q, q_off), _ptr(k, k_off), _ptr(v, v_off), _ptr(o, o_off), _ptr(seg)
+        a.heads, a.d, a.cap_rows = heads, d, cap_rows
+        a.q_ss, a.q_hs = q_str
+        a.k_ss, a.k_hs = k_str
+        a.v_ss, a.v_hs = v_str
+        a.o_ss, a.o_hs = o_str
+        a.scale, a.dtype = scale, self.dtype
+        self._add(abi.OP_SEG_ATTN, a, label)
+        return o
+
+    def causal_prefill_slots(self, qkv, k_cache, v_cache, seg, o, cap_rows, heads, kv_heads, d, max_len, scale, cache_stride=None, ld_qkv=None,
+                             ld_o=None, label="causal_prefill_slots"):
+        """MTX_OP_CAUSAL_PREFILL_SLOTS: the rows > 1 path of `causal_attention` for up to SLOTS_MAX prompts packed into qkv [cap_rows, ld_qkv],
+        prompt s = rows [seg[s], seg[s + 1]) into the EMPTY slot cache s of [slots, max_len, kv_heads * d] (slot stride `cache_stride`
+        elements); `seg` (int32 [SLOTS_MAX + 1]) lives on the device.  An empty segment leaves its slot alone"""
+        assert seg.dtype == torch.int32 and seg.numel() >= abi.SLOTS_MAX + 1 and seg.is_contiguous()
+        a = abi.CausalPrefillSlotsArgs()
+        a.qkv, a.k_cache, a.v_cache, a.seg, a.o = _ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(seg), _ptr(o)
+        a.cap_rows, a.heads, a.kv_heads, a.d, a.max_len = cap_rows, heads, kv_heads, d, max_len
+        a.ld_qkv, a.ld_o = (ld_qkv or (heads + 2 * kv_heads) * d), (ld_o or heads * d)
+        a.cache_stride = cache_stride if cache_stride is not None else max_len * kv_heads * d
+        a.scale, a.dtype = scale, self.dtype
+        self._add(abi.OP_CAUSAL_PREFILL_SLOTS, a, label)
+        return o
 
     def row_linear(self, a_t, w_t, rows, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE, res=None, ldres=None,
                    alpha=1.0, out_f32=False, label="rowlin"):

@@ -513,6 +513,77 @@ def paddleocr_batch(reps=3, windows=4, iters=60):
                   f"{n * base / best:.2f} x the single step ({plan.n_ops} launches)", flush=True)
 
 
+def paddleocr_fill(reps=3):
+    """what feeds PaddleOCR-VL's decode slots, per crop against packed (`PaddleOcrVlHip(slots=8, packed_prefill=True)`): f16, the widths of
+    `paddleocr`, eight items with the grids of the published-width checks, cycled.  Wall ms, each figure ending in a synchronise, the two
+    paths alternating inside a repetition, best of `reps` with the spread (max - min) beside it: the per-crop fill of 8 slots with its plans
+    warm, the same with eight DISTINCT grids (the page case: the bounded plan caches rebuild, plan builds included), the packed fill of 8;
+    one per-crop fill against a packed fill of 1 (the steady-state refill).  Then the plans alone: vision per crop, the packed plans."""
+    import time
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import paddle_ocr_vl_checks as pc
+
+    def items_of(grids):
+        out = []
+        for k, grid in enumerate(grids):
+            ids, pix, thw = pc.make_inputs(k, grid=grid)
+            out.append(dict(input_ids=ids, pixel_values=pix, image_grid_thw=thw))
+        return out
+    cycle = [(20, 28), (28, 40), (8, 12)]
+    warm_items = items_of([cycle[k % 3] for k in range(8)])
+    page_items = items_of([(20, 28), (28, 40), (8, 12), (16, 20), (12, 24), (24, 24), (10, 30), (18, 22)])
+    kw = dict(real=True, max_new_tokens=1024, max_prompt=1344, slots=8)
+    per_crop, packed = pc.hip_model(lib, abi.F16, 0, **kw), pc.hip_model(lib, abi.F16, 0, packed_prefill=True, **kw)
+
+    def empty(m):
+        m.slot_state.zero_(); m.slot_state[abi.SLOT_DONE] = 1
+
+    def wall(f):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    runs = {
+        "per-crop fill of 8, plans warm": lambda: [per_crop._fill_slot(s, it) for s, it in enumerate(warm_items)],
+        "per-crop fill of 8, eight distinct grids (plan builds included)": lambda: [per_crop._fill_slot(s, it) for s, it in enumerate(page_items)],
+        "packed fill of 8": lambda: packed.fill_slots(list(enumerate(warm_items))),
+        "packed fill of 8, eight distinct grids": lambda: packed.fill_slots(list(enumerate(page_items))),
+        "one per-crop fill (20 x 28)": lambda: per_crop._fill_slot(0, warm_items[0]),
+        "packed fill of 1 (20 x 28)": lambda: packed.fill_slots([(0, warm_items[0])]),
+    }
+    for name in ("per-crop fill of 8, plans warm", "packed fill of 8", "packed fill of 8, eight distinct grids", "packed fill of 1 (20 x 28)"):      # warm: plans, graphs
+        for _ in range(2):
+            empty(packed); runs[name]()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in runs}
+    page, page_packed = "per-crop fill of 8, eight distinct grids (plan builds included)", "packed fill of 8, eight distinct grids"
+    for _ in range(reps):
+        for name in (page, page_packed, None, "per-crop fill of 8, plans warm", "packed fill of 8", "one per-crop fill (20 x 28)", "packed fill of 1 (20 x 28)"):
+            empty(packed); empty(per_crop)
+            if name is None:                                       # the page case has turned the bounded plan caches over: warm them again, untimed
+                runs["per-crop fill of 8, plans warm"]()
+                continue
+            ms[name].append(wall(runs[name]))
+    print(f"paddleocr_fill f16, 8 slots, max_prompt 1344; packed ladders {packed.pk_vis_ladder} patches / {packed.pk_txt_ladder} rows", flush=True)
+    for name, v in ms.items():
+        print(f"  {name}: {min(v):.2f} ms (spread {max(v) - min(v):.2f} over {reps} repetitions)", flush=True)
+    a, b = min(ms["per-crop fill of 8, plans warm"]), min(ms["packed fill of 8"])
+    c, d = min(ms["one per-crop fill (20 x 28)"]), min(ms["packed fill of 1 (20 x 28)"])
+    print(f"  packed 8 against per-crop 8 (warm): {a / b:.2f} x; the page case: {min(ms[page]) / min(ms[page_packed]):.2f} x; "
+          f"packed 1 against one per-crop fill: {c / d:.2f} x", flush=True)
+    # the plans alone (event-timed replays)
+    for grid in cycle:
+        vis = per_crop._vision(*grid)
+        vis.time(2)
+        print(f"  vision plan per crop, grid {grid[0]} x {grid[1]} ({grid[0] * grid[1]} patches): {min(vis.time(5) for _ in range(reps)):.3f} ms eager ({vis.n_ops} launches)", flush=True)
+    empty(packed); packed.fill_slots(list(enumerate(warm_items)))
+    for what, plans in (("vision", packed._pk_vis), ("text", packed._pk_txt)):
+        for cap, plan in sorted(plans.items()):
+            plan.time(2, graph=True)
+            print(f"  packed {what} plan, capacity {cap}: {min(plan.time(5, graph=True) for _ in range(reps)):.3f} ms per replay ({plan.n_ops} launches)", flush=True)
+    per_crop.close(); packed.close()
+
+
 def mangaocr_batch(reps=3, iters=40, crops=16):
     """manga-ocr's batched step graph (`MangaOcrHip(slots=S)._stepper_batch()`: wide row linears, group-batched attention, the beam search on the
     device) at S = 1, 2, 4, 8 beside today's 4-row step graph: published widths, f16, 4 beams, a 300-position cache.  Whole-graph replays; the
@@ -619,6 +690,9 @@ if __name__ == "__main__":
     while args:
         if args[0] == "mangaocr_batch":
             mangaocr_batch(); args = args[1:]
+            continue
+        if args[0] == "paddleocr_fill":
+            paddleocr_fill(); args = args[1:]
             continue
         if args[0] == "paddleocr":
             paddleocr(); paddleocr_batch(); args = args[1:]

@@ -758,6 +758,34 @@ typedef struct mtx_causal_prefill_slots_args {
   float scale; int32_t dtype;
 } mtx_causal_prefill_slots_args;
 
+/* ---- ABI 12, additive: attention with an additive relative-position ("Toeplitz") bias and a key count in device memory (csrc/relattn.hip):
+ * the one attention of FLUX's prompt encoders — Qwen3, T5-XXL and CLIP-L, which the reference runs through transformers on first use
+ * (core/image/inpainting.py:846-873, :1110-1124; here core/ml/text_encoders.py).
+ *
+ * MTX_OP_REL_ATTN (mtx_rel_attention):
+ *   o[i, h] = sum_j softmax_j( scale * q[i, h] . k[j, g] + rel[h][j - i + s - 1] ) v[j, g]   over j < min(s, n_keys),  g = h / (heads / kv_heads)
+ *   q, k, v, o   16-bit [s] rows, row and head strides in elements as in mtx_seg_attn_args; k and v hold kv_heads heads
+ *   rel          fp32 [heads][ld_rel], ld_rel >= 2 s - 1, entry (h, j - i + s - 1); 4-byte aligned only; NULL = no bias.  The bias is added
+ *                AFTER the scale.  An entry <= MTX_REL_MASKED (-inf included) gives that key a weight of exactly 0: the causal mask is the
+ *                table "0 up to entry s - 1, masked above"
+ *   n_keys       DEVICE int32 scalar, so that one recorded op serves every prompt length; NULL = s; values above s count as s
+ * Scores, softmax and accumulation in fp32, ONE rounding to `dtype` (scores are fp32 sums of exact 16-bit products; the softmax weights
+ * reach the matrix pipe as a high and a low 16-bit half, 16+ bits in all, as in mtx_causal_attention).  A query row with no visible key
+ * (n_keys <= 0 included) gets a zero row, never a NaN.  Identical calls give identical bytes (no atomics, fixed order).  Nothing outside
+ * the d columns of each (row < s, head) of o is written; nothing of q, k, v at rows >= s is read (nor of k, v at rows >= n_keys).
+ * Built for d = 64 / 128, 1 <= s <= MTX_REL_ATTN_SMAX, heads % kv_heads == 0 (MTX_ERR_UNSUPPORTED otherwise).  A null q / k / v / o, a
+ * dtype other than bf16 / f16, ld_rel < 2 s - 1, q / k / v / o not 16-byte aligned or a stride that is no multiple of 8: MTX_ERR_INVALID.
+ * Grid: (ceil(s / MTX_REL_ATTN_TQ), heads); no tile is skipped whatever the table holds. */
+#define MTX_REL_ATTN_TQ 64
+#define MTX_REL_ATTN_SMAX 1024
+#define MTX_REL_MASKED (-1.0e30f)
+typedef struct mtx_rel_attn_args {
+  const void* q; const void* k; const void* v; void* o; const float* rel; const int32_t* n_keys;
+  int64_t q_ss, q_hs, k_ss, k_hs, v_ss, v_hs, o_ss, o_hs, ld_rel;
+  int32_t heads, kv_heads, s, d;
+  float scale; int32_t dtype;
+} mtx_rel_attn_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
@@ -765,7 +793,8 @@ typedef enum mtx_op_kind {
   MTX_OP_DECODE_ATTN = 18, MTX_OP_ROWLIN = 19, MTX_OP_CAUSAL_ATTN = 20, MTX_OP_GREEDY = 21,
   MTX_OP_CAUSAL_STEP_BATCH = 22, MTX_OP_GREEDY_BATCH = 23,
   MTX_OP_ROWLIN_WIDE = 24, MTX_OP_DECODE_ATTN_BATCH = 25, MTX_OP_BEAM_STEP = 26,
-  MTX_OP_SEG_ATTN = 27, MTX_OP_CAUSAL_PREFILL_SLOTS = 28
+  MTX_OP_SEG_ATTN = 27, MTX_OP_CAUSAL_PREFILL_SLOTS = 28,
+  MTX_OP_REL_ATTN = 29
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -786,6 +815,7 @@ typedef struct mtx_op {
     mtx_causal_step_batch_args cstepb; mtx_greedy_batch_args greedyb;
     mtx_decode_attn_batch_args dattnb; mtx_beam_step_args beam;      /* MTX_OP_ROWLIN_WIDE takes `rowlin` */
     mtx_seg_attn_args segattn; mtx_causal_prefill_slots_args cprefs;
+    mtx_rel_attn_args relattn;
   } u;
 } mtx_op;
 
@@ -840,6 +870,7 @@ MTX_API int mtx_decode_attention_batch(const mtx_decode_attn_batch_args* a, void
 MTX_API int mtx_beam_step(const mtx_beam_step_args* a, void* stream);
 MTX_API int mtx_segment_attention(const mtx_seg_attn_args* a, void* stream);
 MTX_API int mtx_causal_prefill_slots(const mtx_causal_prefill_slots_args* a, void* stream);
+MTX_API int mtx_rel_attention(const mtx_rel_attn_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

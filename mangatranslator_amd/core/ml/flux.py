@@ -454,6 +454,9 @@ class FluxVAEHip:
         return self._plans[key]
 
 
+PROMPTS_KEPT = 4                      # encoded prompts a pipeline keeps beside the stored one (`set_text_encoder`)
+
+
 class FluxKontextHip:
     """diffusers-pipeline-shaped callable built from the two graphs above."""
 
@@ -464,6 +467,7 @@ class FluxKontextHip:
         self._graph = graph and not dit.lib.is_simulator
         self._lock = threading.Lock()
         self._embeds = None
+        self._stored_prompt, self._text_encoder, self._encoded = None, None, {}
         self.calls = 0                # pipeline invocations (benchmarks assert the expected number of FLUX regions ran)
         self.completed = 0            # ... that returned an image (a call that raised is caught by the OSB stage and becomes a flat fill)
         # First-block cache (reference core/ml/model_manager.py:1159-1162: nunchaku's apply_cache_on_pipe(pipeline, residual_diff_threshold=)).
@@ -474,11 +478,26 @@ class FluxKontextHip:
         self.residual_diff_threshold = 0.0
         self.cache_stats = {"steps": 0, "skipped": 0}      # over the pipeline's lifetime; `last["skipped_steps"]` holds the last call's count
 
-    def set_prompt_embeds(self, prompt_embeds: torch.Tensor, pooled: torch.Tensor):
-        """T5 / CLIP embeddings of the (fixed) prompt — computed once per process by the caller."""
+    def set_prompt_embeds(self, prompt_embeds: torch.Tensor, pooled: torch.Tensor, prompt=None):
+        """T5 / CLIP embeddings of the (fixed) prompt — computed once per process by the caller.  prompt: the text they encode (the stored
+        file's metadata), which `encode_prompt` compares against once a text encoder is attached"""
         self._embeds = (prompt_embeds.reshape(-1, prompt_embeds.shape[-1]), pooled.reshape(-1))
+        self._stored_prompt = prompt
+
+    def set_text_encoder(self, fn):
+        """fn(prompt) -> (T5 sequence [512, 4096], CLIP pooled [768]): `encode_prompt` calls it for a prompt other than the stored one and keeps
+        the last few results; None detaches it (a foreign prompt then gets the stored tensors, as before the hook existed)"""
+        self._text_encoder, self._encoded = fn, {}
 
     def encode_prompt(self, prompt=None, prompt_2=None, device=None, **kw):
+        if self._text_encoder is not None and prompt is not None and prompt != self._stored_prompt:
+            if prompt not in self._encoded:
+                if len(self._encoded) >= PROMPTS_KEPT:
+                    self._encoded.pop(next(iter(self._encoded)))
+                seq, pooled = self._text_encoder(prompt)
+                self._encoded[prompt] = (seq.reshape(-1, seq.shape[-1]).to(self.device), pooled.reshape(-1).to(self.device))
+            seq, pooled = self._encoded[prompt]
+            return seq[None], pooled[None], None
         if self._embeds is None:
             raise ModelError("no prompt embeddings: the loader encodes the fixed prompt once when the snapshot's text_encoder/, text_encoder_2/, tokenizer/, tokenizer_2/ "
                              "folders are staged next to transformer/ (core/ml/prompt_embeds.py); otherwise run `python tools/export_prompt_embeds.py kontext <pipeline "

@@ -34,7 +34,7 @@ from ...hip.lib import get_library
 from ...hip.plan import Act, PlanBuilder, PlanCache, glu_interleave
 from ...utils.exceptions import ModelError
 from .dit_graph import DiTStep, ModulationCache, Weight, quantize_weight
-from .flux import FluxVAEHip, _rows, rope_table, sinusoid, synthetic_provider  # noqa: F401  (re-exported for callers)
+from .flux import PROMPTS_KEPT, FluxVAEHip, _rows, rope_table, sinusoid, synthetic_provider  # noqa: F401  (re-exported for callers)
 
 
 def compute_empirical_mu(image_seq_len: int, num_steps: int) -> float:
@@ -330,22 +330,38 @@ class Flux2KleinHip:
         self._graph = graph and not dit.lib.is_simulator
         self._lock = threading.Lock()
         self._embeds = None
+        self._stored_prompt, self._text_encoder, self._encoded = None, None, {}
         self.calls = 0                # pipeline invocations
         self.completed = 0            # ... that returned an image (a call that raised is caught by the OSB stage and becomes a flat fill)
 
-    def set_prompt_embeds(self, prompt_embeds: torch.Tensor):
-        """Qwen3 hidden states of the (fixed) prompt — computed once per process by the caller"""
+    def set_prompt_embeds(self, prompt_embeds: torch.Tensor, prompt=None):
+        """Qwen3 hidden states of the (fixed) prompt — computed once per process by the caller.  prompt: the text they encode (the stored
+        file's metadata), which `encode_prompt` compares against once a text encoder is attached"""
         self._embeds = prompt_embeds.reshape(-1, prompt_embeds.shape[-1])
+        self._stored_prompt = prompt
+
+    def set_text_encoder(self, fn):
+        """fn(prompt) -> Qwen3 hidden states [512, joint_dim]: `encode_prompt` calls it for a prompt other than the stored one and keeps the last
+        few results; None detaches it (a foreign prompt then gets the stored tensor, as before the hook existed)"""
+        self._text_encoder, self._encoded = fn, {}
 
     def encode_prompt(self, prompt=None, device=None, **kw):
-        if self._embeds is None:
+        embeds = self._embeds
+        if self._text_encoder is not None and prompt is not None and prompt != self._stored_prompt:
+            if prompt not in self._encoded:
+                if len(self._encoded) >= PROMPTS_KEPT:
+                    self._encoded.pop(next(iter(self._encoded)))
+                e = self._text_encoder(prompt)
+                self._encoded[prompt] = e.reshape(-1, e.shape[-1]).to(self.device)
+            embeds = self._encoded[prompt]
+        if embeds is None:
             raise ModelError("no prompt embeddings: the loader encodes the fixed prompt once when the snapshot's text_encoder/ and tokenizer/ folders are staged next to "
                              "transformer/ (core/ml/prompt_embeds.py); otherwise run `python tools/export_prompt_embeds.py klein <pipeline snapshot>` (writes "
                              "prompt_embeds.safetensors) or hand the tensor to set_prompt_embeds()")
-        n = self._embeds.shape[0]
+        n = embeds.shape[0]
         text_ids = torch.zeros(1, n, 4)
         text_ids[0, :, 3] = torch.arange(n)
-        return self._embeds[None], text_ids
+        return embeds[None], text_ids
 
     @staticmethod
     def _reference_image(image):

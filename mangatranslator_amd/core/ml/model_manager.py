@@ -211,6 +211,10 @@ class ModelManager:
             self.hf_token = None
             self.flux_hf_token = None
             self.flux_inference_lock = threading.Lock()
+            # who encodes FLUX's prompt.  "wheel" (the default): `transformers` on the host, once, at the first load of a staged snapshot.
+            # "hip": the encoders of core/ml/text_encoders.py on the device — for that first encode, and attached to the pipeline
+            # (`set_text_encoder`) so that a prompt other than the stored one is encoded instead of silently getting the stored tensors
+            self.flux_prompt_encoder = "wheel"
             self._tls = threading.local()           # .replica: which instance set of the front-half models this thread is served from
             # SAM-2.1 arithmetic.  "high" (the default): hi + lo weight pairs in the trunk / neck, fp32 residual stream and an fp32 mask decoder
             # (core/ml/sam2.py) — 5.1e-5 of a page's mask pixels differ from the fp32 reference after `> 0` (the reference keeps exactly
@@ -520,10 +524,23 @@ class ModelManager:
         have = [False]
         if rank0:
             from .prompt_embeds import ensure_prompt_embeds
-            have = [bool(ensure_prompt_embeds(root, pipeline, device=self.device, log=lambda msg: log_message(msg, always_print=True)))]
+            have = [bool(ensure_prompt_embeds(root, pipeline, device=self.device, log=lambda msg: log_message(msg, always_print=True),
+                                              backend=self.flux_prompt_encoder))]
         if _dist_on() and not self._local_reads():
             dist.broadcast_object_list(have, src=0)
         return bool(have[0])
+
+    def _attach_prompt_encoder(self, pipe, root: Path, pipeline: str) -> None:
+        """flux_prompt_encoder "hip" with the snapshot's encoder folders staged: the pipeline's `encode_prompt` encodes a prompt other than the
+        stored one with core/ml/text_encoders.py (the encoder is built, run and closed again per new prompt; the pipeline keeps the result)"""
+        from . import prompt_embeds as pe
+        if self.flux_prompt_encoder != "hip" or not pe.encoders_staged(root, pipeline):
+            return
+        device = self.device
+        if pipeline == "kontext":
+            pipe.set_text_encoder(lambda prompt: pe.encode_kontext_hip(root, prompt, device))
+        else:
+            pipe.set_text_encoder(lambda prompt: pe.encode_klein_hip(root, prompt, device))
 
     def _detector_from_state_dict(self, sd: dict, default_names: Optional[dict] = None, metadata: Optional[dict] = None):
         """ultralytics detector state dict (from the `.pt` itself or its safetensors export) -> the graph of its family: YOLOv8-seg
@@ -881,8 +898,9 @@ class ModelManager:
             pipe = FluxKontextHip(dit, vae)
             emb = root / "prompt_embeds.safetensors"
             if self._prompt_embeds_ready(root, "kontext"):
-                e = self._read_safetensors(emb)
-                pipe.set_prompt_embeds(e["prompt_embeds"], e["pooled_prompt_embeds"])
+                e, md = self._read_safetensors_with_metadata(emb)
+                pipe.set_prompt_embeds(e["prompt_embeds"], e["pooled_prompt_embeds"], prompt=(md or {}).get("prompt"))
+            self._attach_prompt_encoder(pipe, root, "kontext")
             self.models[mt] = pipe
             log_message(f"Flux Kontext pipeline loaded (libmtx_hip graphs, {'fp8 + ' if dit.fp8 else ''}bf16).", verbose=verbose)
             return pipe
@@ -945,7 +963,9 @@ class ModelManager:
             pipe = flux2.Flux2KleinHip(dit, vae)
             emb = root / "prompt_embeds.safetensors"
             if self._prompt_embeds_ready(root, "klein"):
-                pipe.set_prompt_embeds(self._read_safetensors(emb)["prompt_embeds"])
+                e, md = self._read_safetensors_with_metadata(emb)
+                pipe.set_prompt_embeds(e["prompt_embeds"], prompt=(md or {}).get("prompt"))
+            self._attach_prompt_encoder(pipe, root, "klein")
             self.models[model_type] = pipe
             log_message(f"Flux.2 Klein {variant.upper()} model loaded successfully (libmtx_hip graphs, {'fp8 + ' if self.flux_klein_fp8 else ''}bf16).", verbose=verbose)
             return pipe

@@ -12,6 +12,10 @@ What is restated from diffusers (absent here; pinned at the versions in the refe
            T5 tokenizer max_length 512, padding "max_length" -> text_encoder_2(...)[0] [512, 4096]   (both bf16)
   Klein    Flux2KleinPipeline._get_qwen3_prompt_embeds: chat template (user message, add_generation_prompt, thinking off), max_length 512,
            hidden states of layers (9, 18, 27) concatenated on the feature axis -> [512, 3 * hidden]
+
+`backend="hip"` (ModelManager.flux_prompt_encoder) computes the same tensors with core/ml/text_encoders.py instead: the encoders run as
+libmtx_hip plans on the device, only the tokenizers stay with the wheel (host side, like PaddleOCR-VL's processor).  `encode_klein_hip` /
+`encode_kontext_hip` are also what the pipelines' `set_text_encoder` hook calls for a prompt other than the stored one.
 """
 from pathlib import Path
 
@@ -50,9 +54,7 @@ def export_kontext(repo: Path, out: Path, device: str, sdnq: bool, prompt: str =
         ids2 = tok2([prompt], padding="max_length", max_length=512, truncation=True, return_tensors="pt").input_ids.to(device)
         seq = t5(ids2, output_hidden_states=False)[0][0]
     out.parent.mkdir(parents=True, exist_ok=True)
-    _save_atomically({"prompt_embeds": seq.to(torch.bfloat16).cpu().contiguous(), "pooled_prompt_embeds": pooled.to(torch.bfloat16).cpu().contiguous()}, out,
-              metadata={"prompt": prompt, "max_sequence_length": "512", "encoders": "CLIP-L pooler_output + T5-XXL last_hidden_state"})
-    return {"prompt_embeds": tuple(seq.shape), "pooled_prompt_embeds": tuple(pooled.shape)}
+    return _save_kontext(seq, pooled, out, prompt)
 
 
 def export_klein(repo: Path, out: Path, device: str, sdnq: bool, prompt: str = None):
@@ -70,10 +72,109 @@ def export_klein(repo: Path, out: Path, device: str, sdnq: bool, prompt: str = N
         seq = torch.stack([hs[k] for k in QWEN3_LAYERS], dim=1)[0]                   # [3, L, H]
         seq = seq.permute(1, 0, 2).reshape(seq.shape[1], -1)                          # [L, 3 H]
     out.parent.mkdir(parents=True, exist_ok=True)
+    return _save_klein(seq, out, prompt)
+
+
+def _save_kontext(seq, pooled, out: Path, prompt: str):
+    import torch
+    _save_atomically({"prompt_embeds": seq.to(torch.bfloat16).cpu().contiguous(), "pooled_prompt_embeds": pooled.to(torch.bfloat16).cpu().contiguous()}, out,
+              metadata={"prompt": prompt, "max_sequence_length": "512", "encoders": "CLIP-L pooler_output + T5-XXL last_hidden_state"})
+    return {"prompt_embeds": tuple(seq.shape), "pooled_prompt_embeds": tuple(pooled.shape)}
+
+
+def _save_klein(seq, out: Path, prompt: str):
+    import torch
     _save_atomically({"prompt_embeds": seq.to(torch.bfloat16).cpu().contiguous()}, out,
               metadata={"prompt": prompt, "max_sequence_length": "512", "encoders": f"Qwen3 hidden states of layers {QWEN3_LAYERS}"})
     return {"prompt_embeds": tuple(seq.shape)}
 
+
+# ---- the same tensors on the HIP path (core/ml/text_encoders.py) -------------------------------------------------------------------------------
+def _encoder_weights(folder: Path, cls):
+    """(state dict, config dict) of a staged encoder folder without building the wheel's module: the safetensors shards as they are, or, for
+    an SDNQ-packed folder, de-quantised against the shapes of `cls` built on the meta device"""
+    import json
+    import torch
+    config = json.loads((folder / "config.json").read_text())
+    if _sdnq_packed(folder):
+        from transformers import AutoConfig
+        from .sdnq import dequantized_state_dict
+        cfg = AutoConfig.from_pretrained(str(folder))
+        with torch.device("meta"):
+            model = cls.from_config(cfg) if hasattr(cls, "from_config") else cls(cfg)
+        return dequantized_state_dict(folder, {k: tuple(v.shape) for k, v in model.state_dict().items()}, dtype=torch.bfloat16), config
+    from safetensors.torch import load_file
+    shards = sorted(folder.glob("*.safetensors"))
+    if not shards:
+        raise FileNotFoundError(f"{folder}: no safetensors shard")
+    sd = {}
+    for shard in shards:
+        sd.update(load_file(str(shard)))
+    return sd, config
+
+
+def encode_klein_hip(repo: Path, prompt: str, device, lib=None):
+    """`export_klein`'s tensor [512, 3 * hidden] (bf16, host) for `prompt`, from Qwen3EncoderHip: the same tokenizer calls, the encoder built,
+    run once and closed again"""
+    import torch
+    from transformers import AutoModelForCausalLM, AutoTokenizer
+    from .text_encoders import Qwen3EncoderHip
+    repo = Path(repo)
+    tok = AutoTokenizer.from_pretrained(str(repo / "tokenizer"))
+    text = tok.apply_chat_template([{"role": "user", "content": prompt}], tokenize=False, add_generation_prompt=True, enable_thinking=False)
+    t = tok([text], padding="max_length", max_length=512, truncation=True, return_tensors="pt")
+    mask = t.attention_mask[0].bool()
+    n_valid = int(mask.sum())
+    if n_valid < 1 or not bool(mask[:n_valid].all()):
+        raise ValueError("the tokenizer must pad on the right: the encoder's key limit counts the leading real tokens")
+    sd, config = _encoder_weights(repo / "text_encoder", AutoModelForCausalLM)
+    enc = Qwen3EncoderHip(sd, config, taps=QWEN3_LAYERS, device=device, lib=lib)
+    try:
+        return enc.encode_ids(t.input_ids[0], n_valid).to(torch.bfloat16).cpu().contiguous()
+    finally:
+        enc.close()
+
+
+def encode_kontext_hip(repo: Path, prompt: str, device, lib=None):
+    """`export_kontext`'s pair (T5 sequence [512, 4096], CLIP pooled [768]) (bf16, host) for `prompt`, from T5EncoderHip and ClipTextHip; one
+    encoder is resident at a time"""
+    import torch
+    from transformers import AutoTokenizer, CLIPTextModel, T5EncoderModel
+    from .text_encoders import ClipTextHip, T5EncoderHip
+    repo = Path(repo)
+    tok, tok2 = AutoTokenizer.from_pretrained(str(repo / "tokenizer")), AutoTokenizer.from_pretrained(str(repo / "tokenizer_2"))
+    ids = tok([prompt], padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids[0]
+    ids2 = tok2([prompt], padding="max_length", max_length=512, truncation=True, return_tensors="pt").input_ids[0]
+    sd, config = _encoder_weights(repo / "text_encoder", CLIPTextModel)
+    clip = ClipTextHip(sd, config, device=device, lib=lib)
+    try:
+        pooled = clip.pooled(ids).to(torch.bfloat16).cpu().contiguous()
+    finally:
+        clip.close()
+    sd, config = _encoder_weights(repo / "text_encoder_2", T5EncoderModel)
+    t5 = T5EncoderHip(sd, config, device=device, lib=lib)
+    try:
+        seq = t5.encode_ids(ids2).to(torch.bfloat16).cpu().contiguous()
+    finally:
+        t5.close()
+    return seq, pooled
+
+
+def export_kontext_hip(repo: Path, out: Path, device, prompt: str = KONTEXT_PROMPT, lib=None):
+    seq, pooled = encode_kontext_hip(repo, prompt, device, lib)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    return _save_kontext(seq, pooled, out, prompt)
+
+
+def export_klein_hip(repo: Path, out: Path, device, prompt: str = None, lib=None):
+    if prompt is None:
+        from ..image.inpainting import KLEIN_PROMPT as prompt
+    seq = encode_klein_hip(repo, prompt, device, lib)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    return _save_klein(seq, out, prompt)
+
+
+BACKENDS = ("wheel", "hip")
 
 
 
@@ -114,11 +215,14 @@ def encoders_staged(repo: Path, pipeline: str) -> bool:
     return all((repo / n).is_dir() for n in need)
 
 
-def ensure_prompt_embeds(repo: Path, pipeline: str, device="cpu", log=None) -> bool:
+def ensure_prompt_embeds(repo: Path, pipeline: str, device="cpu", log=None, backend: str = "wheel", lib=None) -> bool:
     """`repo / "prompt_embeds.safetensors"` exists afterwards?  Present already: True.  Absent and the snapshot's text encoder(s) and
     tokenizer(s) are staged: they are loaded once through `transformers`, the fixed prompt is encoded (the reference's first-use encode,
     inpainting.py:846-873 / :1110-1124), the file is written, the encoders are dropped.  Absent and nothing to make it from: False — the
-    pipeline's `encode_prompt` then raises the ModelError that names `tools/export_prompt_embeds.py`.  Called by rank 0 only."""
+    pipeline's `encode_prompt` then raises the ModelError that names `tools/export_prompt_embeds.py`.  Called by rank 0 only.
+    backend "hip": the same file, keys and metadata from the encoders of core/ml/text_encoders.py on `device` (library `lib`)."""
+    if backend not in BACKENDS:
+        raise ValueError(f"prompt encoder backend must be one of {BACKENDS}, not {backend!r}")
     out = repo / "prompt_embeds.safetensors"
     if out.exists() and _readable(out):
         return True
@@ -142,8 +246,11 @@ def ensure_prompt_embeds(repo: Path, pipeline: str, device="cpu", log=None) -> b
     except OSError:
         pass                                    # read-only snapshot folder: encode anyway (the save will say so)
     try:
-        sdnq = _sdnq_packed(repo / "text_encoder") or (pipeline == "kontext" and _sdnq_packed(repo / "text_encoder_2"))
-        shapes = export_kontext(repo, out, str(device), sdnq) if pipeline == "kontext" else export_klein(repo, out, str(device), sdnq)
+        if backend == "hip":
+            shapes = export_kontext_hip(repo, out, device, lib=lib) if pipeline == "kontext" else export_klein_hip(repo, out, device, lib=lib)
+        else:
+            sdnq = _sdnq_packed(repo / "text_encoder") or (pipeline == "kontext" and _sdnq_packed(repo / "text_encoder_2"))
+            shapes = export_kontext(repo, out, str(device), sdnq) if pipeline == "kontext" else export_klein(repo, out, str(device), sdnq)
         if log is not None:
             log(f"prompt embeddings encoded once from the staged text encoder(s) and kept: {out} {shapes}")
         return True

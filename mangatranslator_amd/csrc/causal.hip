@@ -37,20 +37,6 @@ constexpr int CA_VROW = CA_D + 16;        // LDS row of the V tile in elements: 
 constexpr float CA_NEG = -1.0e30f;        // running maximum before the first key (finite: exp(CA_NEG - m) is 0, never NaN)
 static_assert(CA_TQ == 64 && CA_TK == 32 && CA_S % 16 == 0 && CA_REC >= 4 + CA_D, "tile constants of include/mtx_hip.h");
 
-// p in [0, 1] as two 16-bit halves: p ~ hi + lo * LoScale<T>::inv
-template <typename T> struct LoScale;
-template <> struct LoScale<__bf16> { static constexpr float mul = 1.f, inv = 1.f; };
-template <> struct LoScale<_Float16> { static constexpr float mul = 4096.f, inv = 1.f / 4096.f; };
-template <typename T> __device__ __forceinline__ void p_split(float p, T& hi, T& lo);
-template <> __device__ __forceinline__ void p_split<__bf16>(float p, __bf16& hi, __bf16& lo) {
-  hi = (__bf16)p;
-  lo = (__bf16)(p - (float)hi);
-}
-template <> __device__ __forceinline__ void p_split<_Float16>(float p, _Float16& hi, _Float16& lo) {
-  hi = p < 6.103515625e-5f ? (_Float16)0.f : (_Float16)p;          // below 2^-14 the high half would be subnormal: the scaled low half takes it all
-  lo = (_Float16)((p - (float)hi) * 4096.f);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void causal_prefill_kernel(mtx_causal_attn_args p) {
 #define CA_PREFILL_POS *p.pos

@@ -176,6 +176,20 @@ template <> __device__ __forceinline__ _Float16 from_f32<_Float16>(float v) {
   return (_Float16)v;
 }
 
+// a softmax weight p in [0, 1] as two 16-bit halves for the matrix pipe: p ~ hi + lo * LoScale<T>::inv (causal.hip, relattn.hip)
+template <typename T> struct LoScale;
+template <> struct LoScale<__bf16> { static constexpr float mul = 1.f, inv = 1.f; };
+template <> struct LoScale<_Float16> { static constexpr float mul = 4096.f, inv = 1.f / 4096.f; };
+template <typename T> __device__ __forceinline__ void p_split(float p, T& hi, T& lo);
+template <> __device__ __forceinline__ void p_split<__bf16>(float p, __bf16& hi, __bf16& lo) {
+  hi = (__bf16)p;
+  lo = (__bf16)(p - (float)hi);
+}
+template <> __device__ __forceinline__ void p_split<_Float16>(float p, _Float16& hi, _Float16& lo) {
+  hi = p < 6.103515625e-5f ? (_Float16)0.f : (_Float16)p;          // below 2^-14 the high half would be subnormal: the scaled low half takes it all
+  lo = (_Float16)((p - (float)hi) * 4096.f);
+}
+
 // x / d where d = 1 + e^t >= 1: one v_rcp_f32 (1 ulp) and a multiply instead of the IEEE division sequence the compiler emits for `/` (two
 // v_div_scale, v_rcp, four FMAs, v_div_fmas, v_div_fixup: 10 instructions per element — 1 300 per wave in the epilogue of a 256 x 256 GELU tile).
 // Used where it was measured to pay and the parity tests hold: the tanh-GELU epilogue (v * sigmoid(2u)) and the SwiGLU sites of the FLUX graphs

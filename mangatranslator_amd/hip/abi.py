@@ -22,6 +22,7 @@ OP_DECODE_ATTN, OP_ROWLIN = 18, 19                             # the decode step
 OP_CAUSAL_STEP_BATCH, OP_GREEDY_BATCH = 22, 23                 # the same two for up to SLOTS_MAX sequences in one launch (additive to ABI 12)
 OP_ROWLIN_WIDE, OP_DECODE_ATTN_BATCH, OP_BEAM_STEP = 24, 25, 26  # manga-ocr's step for S groups of B beams, the search on the device (additive to ABI 12)
 OP_SEG_ATTN, OP_CAUSAL_PREFILL_SLOTS = 27, 28                   # attention over packed segments, the packed prompt pass (additive to ABI 12)
+OP_REL_ATTN = 29                                               # attention with a Toeplitz bias and a device-side key count (additive to ABI 12)
 OP_CAUSAL_ATTN, OP_GREEDY = 20, 21                             # causal GQA attention over a cache, the greedy pick (csrc/causal.hip)
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -309,6 +310,17 @@ class CausalPrefillSlotsArgs(C.Structure):
                 ("ld_qkv", i64), ("ld_o", i64), ("cache_stride", i64), ("scale", f32), ("dtype", i32)]
 
 
+REL_ATTN_SMAX = 1024                                           # MTX_REL_ATTN_SMAX
+REL_MASKED = -1.0e30                                           # MTX_REL_MASKED: a table entry at or below it gives the key a weight of exactly 0
+
+
+class RelAttnArgs(C.Structure):
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("o", vp), ("rel", vp), ("n_keys", vp),
+                ("q_ss", i64), ("q_hs", i64), ("k_ss", i64), ("k_hs", i64), ("v_ss", i64), ("v_hs", i64), ("o_ss", i64), ("o_hs", i64),
+                ("ld_rel", i64),
+                ("heads", i32), ("kv_heads", i32), ("s", i32), ("d", i32), ("scale", f32), ("dtype", i32)]
+
+
 def greedy_scratch_bytes(vocab: int) -> int:
     """MTX_GREEDY_SCRATCH_BYTES of include/mtx_hip.h"""
     return (vocab + GREEDY_CHUNK - 1) // GREEDY_CHUNK * 8
@@ -333,7 +345,7 @@ class _OpUnion(C.Union):
                 ("rt", ResizeThreshArgs), ("ms", MemsetArgs), ("sel", MaskSelectArgs), ("pre", PreprocArgs), ("yd", YoloDecodeArgs), ("detr", DetrArgs), ("quant", QuantArgs), ("tail", TailArgs), ("tc", TextColorArgs),
                 ("dattn", DecodeAttnArgs), ("rowlin", RowLinArgs), ("cattn", CausalAttnArgs), ("greedy", GreedyArgs),
                 ("cstepb", CausalStepBatchArgs), ("greedyb", GreedyBatchArgs), ("dattnb", DecodeAttnBatchArgs), ("beam", BeamStepArgs),
-                ("segattn", SegAttnArgs), ("cprefs", CausalPrefillSlotsArgs)]
+                ("segattn", SegAttnArgs), ("cprefs", CausalPrefillSlotsArgs), ("relattn", RelAttnArgs)]
 
 
 LANE_SIDE, LANE_JOIN = 1, 2
@@ -350,21 +362,21 @@ ARG_TYPES = {OP_CONV2D: ConvArgs, OP_GEMM: GemmArgs, OP_ATTN: AttnArgs, OP_NORM:
              OP_DECODE_ATTN: DecodeAttnArgs, OP_ROWLIN: RowLinArgs, OP_CAUSAL_ATTN: CausalAttnArgs, OP_GREEDY: GreedyArgs,
              OP_CAUSAL_STEP_BATCH: CausalStepBatchArgs, OP_GREEDY_BATCH: GreedyBatchArgs,
              OP_ROWLIN_WIDE: RowLinArgs, OP_DECODE_ATTN_BATCH: DecodeAttnBatchArgs, OP_BEAM_STEP: BeamStepArgs,
-             OP_SEG_ATTN: SegAttnArgs, OP_CAUSAL_PREFILL_SLOTS: CausalPrefillSlotsArgs}
+             OP_SEG_ATTN: SegAttnArgs, OP_CAUSAL_PREFILL_SLOTS: CausalPrefillSlotsArgs, OP_REL_ATTN: RelAttnArgs}
 UNION_FIELD = {OP_CONV2D: "conv", OP_GEMM: "gemm", OP_ATTN: "attn", OP_NORM: "norm",
                OP_GROUPNORM: "gn", OP_EW: "ew", OP_CA: "ca", OP_IMG: "img",
                OP_RESIZE_THRESH: "rt", OP_MEMSET: "ms", OP_MASK_SELECT: "sel", OP_PREPROC: "pre", OP_YOLO_DECODE: "yd", OP_DETR: "detr", OP_QUANT: "quant", OP_TAIL: "tail", OP_TEXTCOLOR: "tc",
                OP_DECODE_ATTN: "dattn", OP_ROWLIN: "rowlin", OP_CAUSAL_ATTN: "cattn", OP_GREEDY: "greedy",
                OP_CAUSAL_STEP_BATCH: "cstepb", OP_GREEDY_BATCH: "greedyb",
                OP_ROWLIN_WIDE: "rowlin", OP_DECODE_ATTN_BATCH: "dattnb", OP_BEAM_STEP: "beam",
-               OP_SEG_ATTN: "segattn", OP_CAUSAL_PREFILL_SLOTS: "cprefs"}
+               OP_SEG_ATTN: "segattn", OP_CAUSAL_PREFILL_SLOTS: "cprefs", OP_REL_ATTN: "relattn"}
 
 # every symbol include/mtx_hip.h declares (tests check the built library exports all of them)
 EXPORTS = [
     "mtx_abi_version", "mtx_abi_sizeof", "mtx_last_error", "mtx_init", "mtx_device_info",
     "mtx_conv2d", "mtx_conv2d_tiles", "mtx_gemm", "mtx_gemm_last_split", "mtx_attention", "mtx_attention_last_route", "mtx_norm", "mtx_groupnorm",
     "mtx_elementwise", "mtx_channel_attention", "mtx_image_convert", "mtx_resize_threshold",
-    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_row_linear_wide", "mtx_decode_attention_batch", "mtx_beam_step", "mtx_segment_attention", "mtx_causal_prefill_slots", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
+    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_row_linear_wide", "mtx_decode_attention_batch", "mtx_beam_step", "mtx_segment_attention", "mtx_causal_prefill_slots", "mtx_rel_attention", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
     "mtx_plan_create", "mtx_plan_run", "mtx_plan_run_graph", "mtx_plan_num_ops",
     "mtx_plan_run_range", "mtx_plan_destroy", "mtx_plan_time", "mtx_plan_time_range", "mtx_plan_time_ops",
 ]

@@ -54,7 +54,8 @@ class MtxLibrary:
                         ("mtx_causal_step_batch", abi.CausalStepBatchArgs), ("mtx_greedy_pick_batch", abi.GreedyBatchArgs),
                         ("mtx_row_linear_wide", abi.RowLinArgs), ("mtx_decode_attention_batch", abi.DecodeAttnBatchArgs),
                         ("mtx_beam_step", abi.BeamStepArgs),
-                        ("mtx_segment_attention", abi.SegAttnArgs), ("mtx_causal_prefill_slots", abi.CausalPrefillSlotsArgs)):
+                        ("mtx_segment_attention", abi.SegAttnArgs), ("mtx_causal_prefill_slots", abi.CausalPrefillSlotsArgs),
+                        ("mtx_rel_attention", abi.RelAttnArgs)):
             getattr(d, name).argtypes = [C.POINTER(t), C.c_void_p]
         d.mtx_host_text_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.c_void_p, C.POINTER(C.c_int)]

@@ -510,6 +510,28 @@ class PlanBuilder:
         self._add(abi.OP_CAUSAL_PREFILL_SLOTS, a, label)
         return o
 
+    def rel_attention(self, q, k, v, o, s, heads, kv_heads, d, q_str, k_str, v_str, o_str, scale, rel=None, ld_rel=None, n_keys=None,
+                      q_off=0, k_off=0, v_off=0, o_off=0, label="rel_attn"):
+        """MTX_OP_REL_ATTN: attention of `s` rows with the additive bias rel[h][j - i + s - 1] (fp32 [heads, ld_rel >= 2 s - 1]; an entry at or
+        below abi.REL_MASKED masks the key; None = no bias) over the keys j < min(s, n_keys); `n_keys` (int32 scalar) lives on the device, so
+        the recorded op serves every prompt length.  *_str = (row stride, head stride) in elements; k and v hold `kv_heads` heads"""
+        a = abi.RelAttnArgs()
+        a.q, a.k, a.v, a.o = _ptr(q, q_off), _ptr(k, k_off), _ptr(v, v_off), _ptr(o, o_off)
+        if rel is not None:
+            assert rel.dtype == torch.float32 and rel.dim() == 2 and rel.shape[0] == heads and rel.stride(1) == 1
+            a.rel, a.ld_rel = _ptr(rel), (ld_rel if ld_rel is not None else rel.stride(0))
+        if n_keys is not None:
+            assert n_keys.dtype == torch.int32
+            a.n_keys = _ptr(n_keys)
+        a.heads, a.kv_heads, a.s, a.d = heads, kv_heads, s, d
+        a.q_ss, a.q_hs = q_str
+        a.k_ss, a.k_hs = k_str
+        a.v_ss, a.v_hs = v_str
+        a.o_ss, a.o_hs = o_str
+        a.scale, a.dtype = scale, self.dtype
+        self._add(abi.OP_REL_ATTN, a, label)
+        return o
+
     def row_linear(self, a_t, w_t, rows, n, k, lda=None, ldw=None, out=None, ldc=None, bias=None, act=abi.ACT_NONE, res=None, ldres=None,
                    alpha=1.0, out_f32=False, label="rowlin"):
         """MTX_OP_ROWLIN: the skinny-row (rows <= 8) linear of a decode step, same epilogue and rounding contract as `gemm`"""

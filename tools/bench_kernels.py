@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [mangaocr_batch] [paddleocr] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [mangaocr_batch] [paddleocr] [textenc [WHEEL_LAYERS]] ..."""
 import os
 import sys
 
@@ -685,9 +685,82 @@ def mangaocr_batch(reps=3, iters=40, crops=16):
         one.close(); many.close()
 
 
+def textenc(wheel_layers=2, reps=3, S=512):
+    """FLUX's prompt encoders (core/ml/text_encoders.py) at the published widths, seeded bf16 weights made on the device, S = 512: Qwen3 at
+    Klein-4B's widths (27 of 36 layers run) and T5-XXL (24 blocks) — ms per encode as the plan's HIP-event time and as the wall of `encode_ids`
+    (host gather, upload, plan, synchronise).  Beside each the wall of the wheel's class on THIS box's CPU in bf16 for `wheel_layers` layers;
+    the whole-model wheel figure printed from it is an extrapolation (layers x per-layer), not a measurement."""
+    import time
+    from transformers import Qwen3Config, Qwen3ForCausalLM, T5Config, T5EncoderModel
+    from mangatranslator_amd.core.ml import text_encoders as te
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = lambda *shape, sc=0.02: (torch.randn(*shape, device=dev, generator=g) * sc).to(torch.bfloat16)
+    G = lambda n: (torch.rand(n, device=dev, generator=g) + 0.5).to(torch.bfloat16)
+    ids = torch.randint(0, 1024, (S,), generator=torch.Generator().manual_seed(0))
+
+    def report(name, enc, layers, run, wheel, wheel_run):
+        plan = enc._plan(S)
+        run()
+        ms = _time(plan, 5)
+        walls = []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            run()
+            walls.append((time.perf_counter() - t0) * 1e3)
+        enc.close()
+        wheel_run(); t = []
+        for _ in range(2):
+            t0 = time.perf_counter(); wheel_run(); t.append((time.perf_counter() - t0) * 1e3)
+        per = min(t) / wheel_layers
+        print(f"textenc {name}: {layers} layers, S = {S}: plan {ms:.3f} ms ({plan.n_ops} launches), encode_ids wall {min(walls):.2f} ms (spread "
+              f"{max(walls) - min(walls):.2f}); wheel on this box's CPU, bf16, {wheel_layers} layers: {min(t):.0f} ms = {per:.0f} ms per layer, "
+              f"{layers} layers EXTRAPOLATED (not measured) {per * layers / 1e3:.1f} s", flush=True)
+
+    C, H, KV, I, L = 2560, 32, 8, 9728, 27
+    sd = {"model.embed_tokens.weight": W(1024, C, sc=0.1).cpu()}
+    for i in range(L):
+        p = f"model.layers.{i}."
+        sd.update({p + "input_layernorm.weight": G(C), p + "post_attention_layernorm.weight": G(C), p + "self_attn.q_norm.weight": G(128),
+                   p + "self_attn.k_norm.weight": G(128), p + "self_attn.q_proj.weight": W(H * 128, C), p + "self_attn.k_proj.weight": W(KV * 128, C),
+                   p + "self_attn.v_proj.weight": W(KV * 128, C), p + "self_attn.o_proj.weight": W(C, H * 128), p + "mlp.gate_proj.weight": W(I, C),
+                   p + "mlp.up_proj.weight": W(I, C), p + "mlp.down_proj.weight": W(C, I)})
+    cfg = dict(hidden_size=C, num_attention_heads=H, num_key_value_heads=KV, head_dim=128, intermediate_size=I, num_hidden_layers=36, rms_norm_eps=1e-6,
+               rope_theta=1e6)
+    enc = te.Qwen3EncoderHip(sd, cfg, taps=(9, 18, 27), device=dev, lib=lib)
+    del sd
+    wheel = Qwen3ForCausalLM(Qwen3Config(hidden_size=C, num_attention_heads=H, num_key_value_heads=KV, head_dim=128, intermediate_size=I,
+                                         num_hidden_layers=wheel_layers, vocab_size=1024)).to(torch.bfloat16).eval()
+    with torch.no_grad():
+        report("Qwen3 (Klein-4B widths)", enc, L, lambda: enc.encode_ids(ids, 40), wheel,
+               lambda: wheel(input_ids=ids[None], attention_mask=(torch.arange(S) < 40).long()[None], output_hidden_states=True, use_cache=False))
+    del enc, wheel
+    torch.cuda.empty_cache()
+
+    C, H, F, L = 4096, 64, 10240, 24
+    sd = {"shared.weight": W(1024, C, sc=1.0).cpu(), "encoder.final_layer_norm.weight": G(C),
+          "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight": W(32, H, sc=2.0)}
+    for i in range(L):
+        p = f"encoder.block.{i}.layer."
+        sd.update({p + "0.layer_norm.weight": G(C), p + "1.layer_norm.weight": G(C), p + "0.SelfAttention.q.weight": W(C, C, sc=0.015),
+                   p + "0.SelfAttention.k.weight": W(C, C, sc=0.015), p + "0.SelfAttention.v.weight": W(C, C, sc=0.015),
+                   p + "0.SelfAttention.o.weight": W(C, C, sc=0.015), p + "1.DenseReluDense.wi_0.weight": W(F, C, sc=0.015),
+                   p + "1.DenseReluDense.wi_1.weight": W(F, C, sc=0.015), p + "1.DenseReluDense.wo.weight": W(C, F, sc=0.015)})
+    cfg = dict(d_model=C, num_heads=H, d_kv=64, d_ff=F, num_layers=L, feed_forward_proj="gated-gelu")
+    enc = te.T5EncoderHip(sd, cfg, device=dev, lib=lib)
+    del sd
+    wheel = T5EncoderModel(T5Config(d_model=C, num_heads=H, d_kv=64, d_ff=F, num_layers=wheel_layers, vocab_size=1024,
+                                    feed_forward_proj="gated-gelu")).to(torch.bfloat16).eval()
+    with torch.no_grad():
+        report("T5-XXL", enc, L, lambda: enc.encode_ids(ids), wheel, lambda: wheel(input_ids=ids[None]))
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
+        if args[0] == "textenc":                      # textenc [WHEEL_LAYERS]
+            n = int(args[1]) if len(args) > 1 and args[1].isdigit() else 2
+            textenc(n); args = args[2 if len(args) > 1 and args[1].isdigit() else 1:]
+            continue
         if args[0] == "mangaocr_batch":
             mangaocr_batch(); args = args[1:]
             continue

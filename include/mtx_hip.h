@@ -786,6 +786,68 @@ typedef struct mtx_rel_attn_args {
   float scale; int32_t dtype;
 } mtx_rel_attn_args;
 
+/* ---- ABI 12, additive: the tail of a YOLO-family detector call on the device (csrc/dettail.hip): score filter, class-aware greedy NMS and the
+ * rescale to page coordinates of ONE image, with every count in device memory — what `YoloSegHip._finish` (core/ml/yolo.py) does on the host
+ * with torch and numpy (reference: ultralytics' non_max_suppression + scale_boxes behind core/image/detection.py:1337-1351), reproduced to
+ * the bit.  All launch sizes are fixed and nothing waits on the host: the op can sit in a captured graph, and one recorded op serves every
+ * threshold and page gain (they live in the parameter block).
+ *
+ * MTX_OP_DET_TAIL (mtx_detector_tail):
+ *   decoded   fp32 [anchors][ld] rows of MTX_OP_YOLO_DECODE: x1 y1 x2 y2 (letterboxed pixels) | nc class scores | nm mask coefficients;
+ *             ld >= 4 + nc + nm is the row stride in elements (a slot of a batched plan's decoded [B][anchors][..] is passed as it is)
+ *   params    DEVICE block of MTX_DET_TAIL_PARAM_WORDS 32-bit words, rewritten by the host before a call (fp32 unless noted):
+ *             [MTX_DET_TAIL_P_CONF] conf, [.._IOU] iou, [.._MAX_DET] max_det (int32), [.._GAIN] gain, [.._PADW] padw, [.._PADH] padh,
+ *             [.._W0] w0 (int32), [.._H0] h0 (int32) — the letterbox gain and paddings as the host path rounds them to fp32
+ *   out       DEVICE block of MTX_DET_TAIL_OUT_WORDS(max_keep) 32-bit words:
+ *             [MTX_DET_TAIL_KEPT] kept, [.._CAND] candidates, [.._OVERFLOW] overflow (int32; word 3 is reserved), then
+ *             boxes fp32 [max_keep][4] at MTX_DET_TAIL_BOXES, conf fp32 [max_keep] at MTX_DET_TAIL_CONF(max_keep), cls fp32 [max_keep] at
+ *             MTX_DET_TAIL_CLS(max_keep), and the kept rows' indices int32 [max_keep] at MTX_DET_TAIL_ROWS(max_keep); entries past `kept` are zero
+ *   coef      nm > 0: `dtype` (bf16 / f16) [max_keep][nm], the kept rows' mask coefficients rounded to nearest even (overflow to infinity, as
+ *             torch.Tensor.to does — no saturation), rows past `kept` zero: the operand of the retina-mask GEMM.  nm == 0: ignored
+ *   workspace MTX_DET_TAIL_WS_BYTES bytes, 16-byte aligned.  Its first word is the candidate counter: it must be ZERO before the first call
+ *             and every call leaves it zero (the op resets it itself, so a replayed graph needs no clear in front of it)
+ * Semantics, all in fp32 with no contraction into FMA and the correctly rounded division:
+ *   score[a] = max over the nc class columns, cls[a] = the lowest class that attains it; a row with a NaN class score is no candidate;
+ *   candidates: score > conf, strictly; order: score descending, ties by ascending row (the sort key is (score bits, row), so the result does
+ *   not depend on the order in which workgroups appended candidates: identical calls give identical bytes);
+ *   NMS on corners x + cls * 7680: area = (x2 - x1) * (y2 - y1); iw = max(min(x2_i, x2_j) - max(x1_i, x1_j), 0), ih alike; inter = iw * ih;
+ *   iou = inter / ((area_i + area_j) - inter); a kept i suppresses a later j iff iou > iou_thres, strictly (0 / 0 = NaN suppresses nothing);
+ *   greedy in sorted order — a suppressed box suppresses nothing; the first max_det kept boxes stay;
+ *   page coordinates of the unoffset corners: x' = min(max((x - padw) / gain, 0), w0), y' alike with padh and h0.
+ * overflow: more than MTX_DET_TAIL_CAP candidates, or max_det outside 1 .. max_keep.  The op then writes kept = 0, the candidate count and
+ * overflow = 1 and nothing else; the caller runs the host path on the same rows, so results are always the host path's.
+ * Refused (MTX_ERR_INVALID): a null decoded / params / out / workspace, coef null with nm > 0, anchors < 1, nc < 1, nm < 0, ld < 4 + nc + nm,
+ * max_keep outside 1 .. MTX_DET_TAIL_MAX_KEEP, a short or misaligned workspace, a dtype other than bf16 / f16 with nm > 0.
+ * Launches: compaction over ceil(anchors / 256) workgroups; a bitonic sort in LDS by one workgroup; the pairwise suppression bits of the upper
+ * triangle, one 64-bit word per (row, 64 columns), into the workspace; one wave that walks the words greedily and writes the results. */
+#define MTX_DET_TAIL_CAP 1024          /* candidate capacity (rows with score > conf); beyond it the op reports overflow */
+#define MTX_DET_TAIL_MAX_KEEP 304      /* ultralytics' default max_det of 300, rounded up to the mask plans' multiple of 8 */
+#define MTX_DET_TAIL_PARAM_WORDS 8
+#define MTX_DET_TAIL_P_CONF 0
+#define MTX_DET_TAIL_P_IOU 1
+#define MTX_DET_TAIL_P_MAX_DET 2
+#define MTX_DET_TAIL_P_GAIN 3
+#define MTX_DET_TAIL_P_PADW 4
+#define MTX_DET_TAIL_P_PADH 5
+#define MTX_DET_TAIL_P_W0 6
+#define MTX_DET_TAIL_P_H0 7
+#define MTX_DET_TAIL_KEPT 0
+#define MTX_DET_TAIL_CAND 1
+#define MTX_DET_TAIL_OVERFLOW 2
+#define MTX_DET_TAIL_BOXES 4
+#define MTX_DET_TAIL_CONF(max_keep) (4 + 4 * (int64_t)(max_keep))
+#define MTX_DET_TAIL_CLS(max_keep) (4 + 5 * (int64_t)(max_keep))
+#define MTX_DET_TAIL_ROWS(max_keep) (4 + 6 * (int64_t)(max_keep))
+#define MTX_DET_TAIL_OUT_WORDS(max_keep) (4 + 7 * (int64_t)(max_keep))
+/* workspace: counter block (16 bytes) | appended keys u64 [CAP] | appended classes i32 [CAP] | sorted offset corners f32 [CAP][4] | sorted
+ * area, score, class, row [CAP] each | suppression words u64 [CAP][CAP / 64] */
+#define MTX_DET_TAIL_WS_BYTES (16 + (int64_t)MTX_DET_TAIL_CAP * (8 + 4 + 16 + 16) + (int64_t)MTX_DET_TAIL_CAP * (MTX_DET_TAIL_CAP / 64) * 8)
+typedef struct mtx_det_tail_args {
+  const float* decoded; const void* params; void* out; void* coef; void* workspace;
+  int64_t ld, workspace_bytes;
+  int32_t anchors, nc, nm, max_keep, dtype;
+} mtx_det_tail_args;
+
 typedef enum mtx_op_kind {
   MTX_OP_CONV2D = 1, MTX_OP_GEMM = 2, MTX_OP_ATTN = 3, MTX_OP_NORM = 4, MTX_OP_GROUPNORM = 5,
   MTX_OP_EW = 6, MTX_OP_CA = 7, MTX_OP_IMG = 8, MTX_OP_RESIZE_THRESH = 9, MTX_OP_MEMSET = 10,
@@ -794,7 +856,8 @@ typedef enum mtx_op_kind {
   MTX_OP_CAUSAL_STEP_BATCH = 22, MTX_OP_GREEDY_BATCH = 23,
   MTX_OP_ROWLIN_WIDE = 24, MTX_OP_DECODE_ATTN_BATCH = 25, MTX_OP_BEAM_STEP = 26,
   MTX_OP_SEG_ATTN = 27, MTX_OP_CAUSAL_PREFILL_SLOTS = 28,
-  MTX_OP_REL_ATTN = 29
+  MTX_OP_REL_ATTN = 29,
+  MTX_OP_DET_TAIL = 30
 } mtx_op_kind;
 
 typedef struct mtx_memset_args { void* ptr; int64_t bytes; int32_t value; } mtx_memset_args;
@@ -816,6 +879,7 @@ typedef struct mtx_op {
     mtx_decode_attn_batch_args dattnb; mtx_beam_step_args beam;      /* MTX_OP_ROWLIN_WIDE takes `rowlin` */
     mtx_seg_attn_args segattn; mtx_causal_prefill_slots_args cprefs;
     mtx_rel_attn_args relattn;
+    mtx_det_tail_args dettail;
   } u;
 } mtx_op;
 
@@ -871,6 +935,7 @@ MTX_API int mtx_beam_step(const mtx_beam_step_args* a, void* stream);
 MTX_API int mtx_segment_attention(const mtx_seg_attn_args* a, void* stream);
 MTX_API int mtx_causal_prefill_slots(const mtx_causal_prefill_slots_args* a, void* stream);
 MTX_API int mtx_rel_attention(const mtx_rel_attn_args* a, void* stream);
+MTX_API int mtx_detector_tail(const mtx_det_tail_args* a, void* stream);
 /* contour half of the same chain, host side on one crop (cleaning.py:340-386): external contours of the
  * thresholded crop -> area / centroid filter -> filled union -> largest blob -> final mask + bounding box.
  * Returns the number of accepted text fragments (0 = nothing to clean).                                */

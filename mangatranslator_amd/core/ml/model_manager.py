@@ -228,6 +228,10 @@ class ModelManager:
             # would degrade masks without a NaN — ADVICE r04), "bf16" = the reference's own GPU dtype, no probe, "f16" = no probe either
             self.sam_storage = "auto"
             self._failed_reads = {}                 # checkpoint path -> the error all ranks were told (multi-rank only; see _read_safetensors_with_metadata)
+            # where the YOLO-family detectors run the second half of a call (score filter, NMS, page coordinates): "host" — torch and numpy
+            # on downloaded candidates — or "device": MTX_OP_DET_TAIL on the model's stream, one small blocking read per call
+            # (`YoloSegHip(tail=)`; same results to the bit).  Read when a detector is loaded.
+            self.detector_tail = "host"
             self.detector_batch = 1                 # pages per graph replay of the panel / outside-text detectors (see _maybe_batched)
             self._batchers = {}
             self._initialized = True
@@ -555,11 +559,14 @@ class ModelManager:
             except (ValueError, SyntaxError):
                 names = None
         names = names or default_names
+        tail = getattr(self, "detector_tail", "host")
+        if tail not in ("host", "device"):
+            raise ModelError(f"detector_tail must be 'host' or 'device', not {tail!r}")
         if "model.10.m.0.attn.qkv.conv.weight" in sd or "model.6.m.0.0.attn.qkv.conv.weight" in sd:
             from .yolo11 import Yolo11Hip
-            return Yolo11Hip(sd, device=self.device, names=names)
+            return Yolo11Hip(sd, device=self.device, names=names, tail=tail)
         from .yolo import YoloSegHip
-        return YoloSegHip(sd, device=self.device, names=names)
+        return YoloSegHip(sd, device=self.device, names=names, tail=tail)
 
     def _staged(self, path: Path, what: str) -> None:
         """filesystem check done by rank 0 only, verdict shared: every rank raises or none does"""

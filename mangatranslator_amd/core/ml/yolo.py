@@ -90,7 +90,15 @@ def nms_xyxy(boxes: np.ndarray, scores: np.ndarray, iou_thres: float):
 
 
 class YoloSegHip:
-    def __init__(self, state_dict: dict, device="cuda", names=None, lib=None, graph: bool = True):
+    TAILS = ("host", "device")
+
+    def __init__(self, state_dict: dict, device="cuda", names=None, lib=None, graph: bool = True, tail: str = "host"):
+        """tail: where the second half of a call runs — "host": candidates come to the host, NMS in numpy (`_finish_host`); "device":
+        score filter, NMS and rescale as MTX_OP_DET_TAIL on the model's stream, the host reads one state block (`_finish_device`).  The
+        results are the same to the bit (tests/detector_tail_checks.py)."""
+        if tail not in self.TAILS:
+            raise ModelError(f"tail must be one of {self.TAILS}, not {tail!r}")
+        self.tail = tail
         self.lib = lib if lib is not None else get_library()
         self.device = torch.device(device)
         self.dtype, self.tdt = abi.F16, torch.float16
@@ -101,6 +109,8 @@ class YoloSegHip:
         self._lane = AsyncLane(self.device, self.lib.is_simulator)
         self._plans = PlanCache(8)
         self._mask_plans = PlanCache(8)
+        self._tail_plans = PlanCache(32)          # one per decoded buffer (a batched plan has one per slot); 180 KB each
+        self._tail_lock = threading.Lock()        # the tickets of a DetectorBatcher finish on their own threads
         self._pack(sd)
 
     def _derive(self, sd):
@@ -303,6 +313,83 @@ class YoloSegHip:
             ticket.close() if isinstance(ticket, LaneTicket) else self._lane.release()
 
     def _finish(self, plan, lp, hw, conf, iou, max_det):
+        """second half of a call on `plan.decoded` (one image's rows; `DetectorBatcher` passes a slot of its batched plan): the device tail
+        where it was asked for and can hold the result, the host path otherwise — the two give the same bytes"""
+        if self.tail == "device" and isinstance(max_det, int) and 1 <= max_det <= abi.DET_TAIL_MAX_KEEP:
+            res = self._finish_device(plan, lp, hw, conf, iou, max_det)
+            if res is not None:
+                return res
+        return self._finish_host(plan, lp, hw, conf, iou, max_det)
+
+    @staticmethod
+    def _page_scale(lp, h0, w0):
+        """ultralytics scale_boxes: letterboxed pixels -> page pixels is (x - pad) / gain"""
+        gain = min(lp["H"] / h0, lp["W"] / w0)
+        return gain, round((lp["W"] - w0 * gain) / 2 - 0.1), round((lp["H"] - h0 * gain) / 2 - 0.1)
+
+    @staticmethod
+    def _mask_roi(plan, h0, w0):
+        """-> (mh, mw, roi): the prototype grid and the part of it the letterboxed page covers"""
+        mh, mw = plan.proto.h, plan.proto.w
+        gm = min(mh / h0, mw / w0)
+        pw, ph = (mw - w0 * gm) / 2, (mh - h0 * gm) / 2
+        top, left = int(round(ph - 0.1)), int(round(pw - 0.1))
+        return mh, mw, (top, left, mh - int(round(ph + 0.1)) - top, mw - int(round(pw + 0.1)) - left)
+
+    def _tail_plan(self, dec):
+        """the recorded MTX_OP_DET_TAIL over the buffer `dec` lives in, with its pinned parameter staging block.  Thresholds and page figures
+        travel in the parameter block, so a plan is never rebuilt for them.  Run eagerly (four launches): a first graph replay would
+        capture on whichever thread finishes a batcher's slot first, beside the other front halves' GPU work (see detector_batch._Batch)"""
+        key = (dec.data_ptr(), int(dec.shape[0]), int(dec.stride(0)))
+        with self._tail_lock:
+            tp = self._tail_plans.get(key)
+            if tp is None:
+                pb = PlanBuilder(self.lib, self.device, self.dtype)
+                bufs = pb.detector_tail(dec, self.a["nc"], self.a["nm"])
+                tp = pb.build()
+                tp.bufs = bufs
+                tp.stage = torch.zeros(abi.DET_TAIL_PARAM_WORDS, dtype=torch.int32, pin_memory=self._lane.on)
+                tp.stage_i = tp.stage.numpy()
+                tp.stage_f = tp.stage_i.view(np.float32)
+                self._tail_plans[key] = tp
+        return tp
+
+    def _finish_device(self, plan, lp, hw, conf, iou, max_det):
+        """-> the result list, or None when the op reported an overflow (more candidates than abi.DET_TAIL_CAP): the caller then runs
+        the host path on the same rows"""
+        h0, w0 = hw
+        nm = self.a["nm"]
+        tp = self._tail_plan(plan.decoded)
+        t, si, sf = tp.bufs, tp.stage_i, tp.stage_f
+        gain, padw, padh = self._page_scale(lp, h0, w0)
+        sf[abi.DET_TAIL_P_CONF], sf[abi.DET_TAIL_P_IOU], si[abi.DET_TAIL_P_MAX_DET] = conf, iou, max_det      # (fp32 as the host path's operands are)
+        sf[abi.DET_TAIL_P_GAIN], sf[abi.DET_TAIL_P_PADW], sf[abi.DET_TAIL_P_PADH] = gain, padw, padh
+        si[abi.DET_TAIL_P_W0], si[abi.DET_TAIL_P_H0] = w0, h0
+        t.params.copy_(tp.stage, non_blocking=True)      # the staging block is free again once this call's state has been read
+        tp.run()
+        blk = t.out.clone()                              # the plan's block is rewritten by the next call
+        kept, _cand, overflow, _ = blk[:abi.DET_TAIL_BOXES].tolist()          # the call's only blocking read
+        if overflow:
+            return None
+        res = SimpleNamespace(orig_shape=(h0, w0), names=self.names, boxes=None, masks=None)
+        if kept == 0:
+            return [res]
+        mk, f = t.max_keep, blk.view(torch.float32)
+        c0, l0 = abi.det_tail_conf(mk), abi.det_tail_cls(mk)
+        res.boxes = _Boxes(f[abi.DET_TAIL_BOXES:c0].view(mk, 4)[:kept], f[c0:c0 + kept], f[l0:l0 + kept])
+        if nm == 0:
+            return [res]
+        mh, mw, roi = self._mask_roi(plan, h0, w0)
+        nd = (kept + 7) // 8 * 8
+        mp = self._mask_plan(nd, mh, mw, roi, h0, w0)
+        mp.coef.copy_(t.coef[:nd])                       # rows past `kept` are zero in both: device to device, nothing comes from the host
+        mp.protoflat.copy_(plan.proto.t.view(mh * mw, nm))
+        mp.boxes.copy_(t.boxes[:nd])
+        mp.run()
+        res.masks = _Masks(mp.masks[:kept].clone(), self.lib)
+        return [res]
+
+    def _finish_host(self, plan, lp, hw, conf, iou, max_det):
         h0, w0 = hw
         nc, nm = self.a["nc"], self.a["nm"]
         dec = plan.decoded
@@ -315,8 +402,7 @@ class YoloSegHip:
             return [res]
         keep = nms_xyxy(cand[:, :4] + cl[:, None].astype(np.float32) * 7680.0, sc, iou)[:max_det]
         cand, sc, cl = cand[keep], sc[keep], cl[keep]
-        gain = min(lp["H"] / h0, lp["W"] / w0)
-        padw, padh = round((lp["W"] - w0 * gain) / 2 - 0.1), round((lp["H"] - h0 * gain) / 2 - 0.1)
+        gain, padw, padh = self._page_scale(lp, h0, w0)
         pb_ = cand[:, :4].astype(np.float32).copy()
         pb_[:, [0, 2]] = ((pb_[:, [0, 2]] - padw) / gain).clip(0, w0)
         pb_[:, [1, 3]] = ((pb_[:, [1, 3]] - padh) / gain).clip(0, h0)
@@ -325,11 +411,7 @@ class YoloSegHip:
         if nm == 0:                    # detect-only head (panel / outside-text detectors): boxes are the whole result
             return [res]
         # retina masks
-        mh, mw = plan.proto.h, plan.proto.w
-        gm = min(mh / h0, mw / w0)
-        pw, ph = (mw - w0 * gm) / 2, (mh - h0 * gm) / 2
-        top, left = int(round(ph - 0.1)), int(round(pw - 0.1))
-        roi = (top, left, mh - int(round(ph + 0.1)) - top, mw - int(round(pw + 0.1)) - left)
+        mh, mw, roi = self._mask_roi(plan, h0, w0)
         nk = len(keep)
         mp = self._mask_plan((nk + 7) // 8 * 8, mh, mw, roi, h0, w0)
         mp.coef.zero_()

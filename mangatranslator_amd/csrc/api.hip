@@ -44,6 +44,7 @@ int beam_step_launch(const mtx_beam_step_args*, void*, const char**);
 int seg_attn_launch(const mtx_seg_attn_args*, void*, const char**);
 int causal_prefill_slots_launch(const mtx_causal_prefill_slots_args*, void*, const char**);
 int rel_attn_launch(const mtx_rel_attn_args*, void*, const char**);
+int det_tail_launch(const mtx_det_tail_args*, void*, const char**);
 
 static thread_local std::string g_err;
 
@@ -103,6 +104,7 @@ static int run_op(const mtx_op& op, void* stream) {
     case MTX_OP_SEG_ATTN: rc = seg_attn_launch(&op.u.segattn, stream, &err); break;
     case MTX_OP_CAUSAL_PREFILL_SLOTS: rc = causal_prefill_slots_launch(&op.u.cprefs, stream, &err); break;
     case MTX_OP_REL_ATTN: rc = rel_attn_launch(&op.u.relattn, stream, &err); break;
+    case MTX_OP_DET_TAIL: rc = det_tail_launch(&op.u.dettail, stream, &err); break;
     case MTX_OP_MEMSET:
       if (op.u.ms.bytes < 0 || (!op.u.ms.ptr && op.u.ms.bytes > 0)) { rc = MTX_ERR_INVALID; err = "memset: null pointer or negative size"; break; }
       fill_bytes_async(op.u.ms.ptr, op.u.ms.value, (size_t)op.u.ms.bytes, stream);        // a kernel: a captured hipMemsetAsync (memset node) did not always clear (mtx_device.h)
@@ -212,6 +214,7 @@ size_t mtx_abi_sizeof(int kind) {
     case MTX_OP_SEG_ATTN: return sizeof(mtx_seg_attn_args);
     case MTX_OP_CAUSAL_PREFILL_SLOTS: return sizeof(mtx_causal_prefill_slots_args);
     case MTX_OP_REL_ATTN: return sizeof(mtx_rel_attn_args);
+    case MTX_OP_DET_TAIL: return sizeof(mtx_det_tail_args);
     case 100: return sizeof(mtx_clean_args);       /* op-level only (not a plan op) */
     default: return 0;
   }
@@ -288,6 +291,7 @@ MTX_OP_ENTRY(mtx_beam_step, mtx_beam_step_args, beam_step_launch)
 MTX_OP_ENTRY(mtx_segment_attention, mtx_seg_attn_args, seg_attn_launch)
 MTX_OP_ENTRY(mtx_causal_prefill_slots, mtx_causal_prefill_slots_args, causal_prefill_slots_launch)
 MTX_OP_ENTRY(mtx_rel_attention, mtx_rel_attn_args, rel_attn_launch)
+MTX_OP_ENTRY(mtx_detector_tail, mtx_det_tail_args, det_tail_launch)
 
 
 int mtx_gemm_last_split(int* whole_tiles, int* k_slices, int* tail_pieces) {

@@ -23,6 +23,7 @@ OP_CAUSAL_STEP_BATCH, OP_GREEDY_BATCH = 22, 23                 # the same two fo
 OP_ROWLIN_WIDE, OP_DECODE_ATTN_BATCH, OP_BEAM_STEP = 24, 25, 26  # manga-ocr's step for S groups of B beams, the search on the device (additive to ABI 12)
 OP_SEG_ATTN, OP_CAUSAL_PREFILL_SLOTS = 27, 28                   # attention over packed segments, the packed prompt pass (additive to ABI 12)
 OP_REL_ATTN = 29                                               # attention with a Toeplitz bias and a device-side key count (additive to ABI 12)
+OP_DET_TAIL = 30                                               # a YOLO-family detector's score filter, NMS and rescale on the device (additive to ABI 12)
 OP_CAUSAL_ATTN, OP_GREEDY = 20, 21                             # causal GQA attention over a cache, the greedy pick (csrc/causal.hip)
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -321,6 +322,37 @@ class RelAttnArgs(C.Structure):
                 ("heads", i32), ("kv_heads", i32), ("s", i32), ("d", i32), ("scale", f32), ("dtype", i32)]
 
 
+# the detector tail (include/mtx_hip.h, MTX_DET_TAIL_*): capacities, the parameter block's words, the result block's word offsets
+DET_TAIL_CAP, DET_TAIL_MAX_KEEP, DET_TAIL_PARAM_WORDS = 1024, 304, 8
+(DET_TAIL_P_CONF, DET_TAIL_P_IOU, DET_TAIL_P_MAX_DET, DET_TAIL_P_GAIN, DET_TAIL_P_PADW, DET_TAIL_P_PADH, DET_TAIL_P_W0,
+ DET_TAIL_P_H0) = range(8)
+DET_TAIL_KEPT, DET_TAIL_CAND, DET_TAIL_OVERFLOW, DET_TAIL_BOXES = 0, 1, 2, 4
+DET_TAIL_WS_BYTES = 16 + DET_TAIL_CAP * (8 + 4 + 16 + 16) + DET_TAIL_CAP * (DET_TAIL_CAP // 64) * 8
+
+
+def det_tail_conf(max_keep: int) -> int:
+    return 4 + 4 * max_keep
+
+
+def det_tail_cls(max_keep: int) -> int:
+    return 4 + 5 * max_keep
+
+
+def det_tail_rows(max_keep: int) -> int:
+    return 4 + 6 * max_keep
+
+
+def det_tail_out_words(max_keep: int) -> int:
+    """MTX_DET_TAIL_OUT_WORDS of include/mtx_hip.h"""
+    return 4 + 7 * max_keep
+
+
+class DetTailArgs(C.Structure):
+    _fields_ = [("decoded", vp), ("params", vp), ("out", vp), ("coef", vp), ("workspace", vp),
+                ("ld", i64), ("workspace_bytes", i64),
+                ("anchors", i32), ("nc", i32), ("nm", i32), ("max_keep", i32), ("dtype", i32)]
+
+
 def greedy_scratch_bytes(vocab: int) -> int:
     """MTX_GREEDY_SCRATCH_BYTES of include/mtx_hip.h"""
     return (vocab + GREEDY_CHUNK - 1) // GREEDY_CHUNK * 8
@@ -345,7 +377,7 @@ class _OpUnion(C.Union):
                 ("rt", ResizeThreshArgs), ("ms", MemsetArgs), ("sel", MaskSelectArgs), ("pre", PreprocArgs), ("yd", YoloDecodeArgs), ("detr", DetrArgs), ("quant", QuantArgs), ("tail", TailArgs), ("tc", TextColorArgs),
                 ("dattn", DecodeAttnArgs), ("rowlin", RowLinArgs), ("cattn", CausalAttnArgs), ("greedy", GreedyArgs),
                 ("cstepb", CausalStepBatchArgs), ("greedyb", GreedyBatchArgs), ("dattnb", DecodeAttnBatchArgs), ("beam", BeamStepArgs),
-                ("segattn", SegAttnArgs), ("cprefs", CausalPrefillSlotsArgs), ("relattn", RelAttnArgs)]
+                ("segattn", SegAttnArgs), ("cprefs", CausalPrefillSlotsArgs), ("relattn", RelAttnArgs), ("dettail", DetTailArgs)]
 
 
 LANE_SIDE, LANE_JOIN = 1, 2
@@ -362,21 +394,22 @@ ARG_TYPES = {OP_CONV2D: ConvArgs, OP_GEMM: GemmArgs, OP_ATTN: AttnArgs, OP_NORM:
              OP_DECODE_ATTN: DecodeAttnArgs, OP_ROWLIN: RowLinArgs, OP_CAUSAL_ATTN: CausalAttnArgs, OP_GREEDY: GreedyArgs,
              OP_CAUSAL_STEP_BATCH: CausalStepBatchArgs, OP_GREEDY_BATCH: GreedyBatchArgs,
              OP_ROWLIN_WIDE: RowLinArgs, OP_DECODE_ATTN_BATCH: DecodeAttnBatchArgs, OP_BEAM_STEP: BeamStepArgs,
-             OP_SEG_ATTN: SegAttnArgs, OP_CAUSAL_PREFILL_SLOTS: CausalPrefillSlotsArgs, OP_REL_ATTN: RelAttnArgs}
+             OP_SEG_ATTN: SegAttnArgs, OP_CAUSAL_PREFILL_SLOTS: CausalPrefillSlotsArgs, OP_REL_ATTN: RelAttnArgs,
+             OP_DET_TAIL: DetTailArgs}
 UNION_FIELD = {OP_CONV2D: "conv", OP_GEMM: "gemm", OP_ATTN: "attn", OP_NORM: "norm",
                OP_GROUPNORM: "gn", OP_EW: "ew", OP_CA: "ca", OP_IMG: "img",
                OP_RESIZE_THRESH: "rt", OP_MEMSET: "ms", OP_MASK_SELECT: "sel", OP_PREPROC: "pre", OP_YOLO_DECODE: "yd", OP_DETR: "detr", OP_QUANT: "quant", OP_TAIL: "tail", OP_TEXTCOLOR: "tc",
                OP_DECODE_ATTN: "dattn", OP_ROWLIN: "rowlin", OP_CAUSAL_ATTN: "cattn", OP_GREEDY: "greedy",
                OP_CAUSAL_STEP_BATCH: "cstepb", OP_GREEDY_BATCH: "greedyb",
                OP_ROWLIN_WIDE: "rowlin", OP_DECODE_ATTN_BATCH: "dattnb", OP_BEAM_STEP: "beam",
-               OP_SEG_ATTN: "segattn", OP_CAUSAL_PREFILL_SLOTS: "cprefs", OP_REL_ATTN: "relattn"}
+               OP_SEG_ATTN: "segattn", OP_CAUSAL_PREFILL_SLOTS: "cprefs", OP_REL_ATTN: "relattn", OP_DET_TAIL: "dettail"}
 
 # every symbol include/mtx_hip.h declares (tests check the built library exports all of them)
 EXPORTS = [
     "mtx_abi_version", "mtx_abi_sizeof", "mtx_last_error", "mtx_init", "mtx_device_info",
     "mtx_conv2d", "mtx_conv2d_tiles", "mtx_gemm", "mtx_gemm_last_split", "mtx_attention", "mtx_attention_last_route", "mtx_norm", "mtx_groupnorm",
     "mtx_elementwise", "mtx_channel_attention", "mtx_image_convert", "mtx_resize_threshold",
-    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_row_linear_wide", "mtx_decode_attention_batch", "mtx_beam_step", "mtx_segment_attention", "mtx_causal_prefill_slots", "mtx_rel_attention", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
+    "mtx_mask_select", "mtx_preprocess", "mtx_yolo_decode", "mtx_detr", "mtx_quantize_mx", "mtx_page_tail", "mtx_text_color", "mtx_decode_attention", "mtx_row_linear", "mtx_causal_attention", "mtx_greedy_pick", "mtx_causal_step_batch", "mtx_greedy_pick_batch", "mtx_row_linear_wide", "mtx_decode_attention_batch", "mtx_beam_step", "mtx_segment_attention", "mtx_causal_prefill_slots", "mtx_rel_attention", "mtx_detector_tail", "mtx_bubble_clean", "mtx_host_text_mask", "mtx_host_fill_components", "mtx_host_chamfer_l2_5x5", "mtx_host_mask_outline", "mtx_host_png_encode",
     "mtx_plan_create", "mtx_plan_run", "mtx_plan_run_graph", "mtx_plan_num_ops",
     "mtx_plan_run_range", "mtx_plan_destroy", "mtx_plan_time", "mtx_plan_time_range", "mtx_plan_time_ops",
 ]

@@ -55,7 +55,7 @@ class MtxLibrary:
                         ("mtx_row_linear_wide", abi.RowLinArgs), ("mtx_decode_attention_batch", abi.DecodeAttnBatchArgs),
                         ("mtx_beam_step", abi.BeamStepArgs),
                         ("mtx_segment_attention", abi.SegAttnArgs), ("mtx_causal_prefill_slots", abi.CausalPrefillSlotsArgs),
-                        ("mtx_rel_attention", abi.RelAttnArgs)):
+                        ("mtx_rel_attention", abi.RelAttnArgs), ("mtx_detector_tail", abi.DetTailArgs)):
             getattr(d, name).argtypes = [C.POINTER(t), C.c_void_p]
         d.mtx_host_text_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.c_void_p, C.POINTER(C.c_int)]

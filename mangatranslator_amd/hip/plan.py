@@ -823,6 +823,30 @@ class PlanBuilder:
         self._add(abi.OP_YOLO_DECODE, a, label)
         return out
 
+    def detector_tail(self, decoded, nc, nm, anchors=None, ld=None, max_keep=abi.DET_TAIL_MAX_KEEP, label="detector_tail"):
+        """MTX_OP_DET_TAIL: score filter, class-aware NMS and the rescale to page coordinates of one image's `decoded` rows (fp32
+        [anchors, ld], the output of `yolo_decode`; a slot of a batched plan's [B, anchors, ld] is passed as it is).  Thresholds, max_det and
+        the letterbox figures are read from `params` (int32 [DET_TAIL_PARAM_WORDS], fp32 fields in the same words), which the caller
+        rewrites before a run: one recorded op serves every call.  -> namespace of the buffers: params, out (the whole result block, int32
+        words), state (= out[:4]: kept, candidates, overflow), boxes [max_keep, 4], conf, cls (fp32 views of out), rows (int32 view), coef
+        ([max_keep, nm] in the builder's 16-bit type; None for a detect-only head)"""
+        from types import SimpleNamespace
+        anchors = int(decoded.shape[0]) if anchors is None else anchors
+        ld = int(decoded.stride(0)) if ld is None else ld
+        params = self.buf((abi.DET_TAIL_PARAM_WORDS,), torch.int32, zero=True)
+        out = self.buf((abi.det_tail_out_words(max_keep),), torch.int32, zero=True)
+        coef = self.buf((max_keep, nm), self.tdtype, zero=True) if nm > 0 else None
+        ws = self.buf((abi.DET_TAIL_WS_BYTES,), torch.uint8, zero=True)          # the op needs its counter word zero at first and leaves it so
+        a = abi.DetTailArgs()
+        a.decoded, a.params, a.out, a.coef, a.workspace = _ptr(decoded), _ptr(params), _ptr(out), _ptr(coef), _ptr(ws)
+        a.ld, a.workspace_bytes = ld, abi.DET_TAIL_WS_BYTES
+        a.anchors, a.nc, a.nm, a.max_keep, a.dtype = anchors, nc, nm, max_keep, self.dtype
+        self._add(abi.OP_DET_TAIL, a, label)
+        f = out.view(torch.float32)
+        c0, l0, r0 = abi.det_tail_conf(max_keep), abi.det_tail_cls(max_keep), abi.det_tail_rows(max_keep)
+        return SimpleNamespace(params=params, out=out, state=out[:abi.DET_TAIL_BOXES], boxes=f[abi.DET_TAIL_BOXES:c0].view(max_keep, 4),
+                               conf=f[c0:l0], cls=f[l0:r0], rows=out[r0:r0 + max_keep], coef=coef, max_keep=max_keep)
+
     def resize_threshold(self, src, dst, n, hs, ws, hd, wd, thresh=0.0, src_dtype=abi.F32, pix_stride=1,
                          sel=None, batch_stride=-1, roi=None, crop_xyxy=None, label="resize_thresh"):
         a = abi.ResizeThreshArgs()

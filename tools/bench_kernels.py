@@ -1,5 +1,5 @@
 """GPU micro-benchmarks of the MFMA-bound kernels at FLUX shapes (HIP-event timing via mtx_plan_time).
-usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [mangaocr_batch] [paddleocr] [textenc [WHEEL_LAYERS]] ..."""
+usage: python tools/bench_kernels.py [attn T [heads]] [gemm M N K] [gemm8 M N K] [quant ROWS K] [conv H W] [actq M N K] [kontext H2 W2 [LAYERS SINGLES]] [sam3 [LAYERS]] [mangaocr [DEC_LAYERS]] [mangaocr_batch] [paddleocr] [textenc [WHEEL_LAYERS]] [dettail] ..."""
 import os
 import sys
 
@@ -754,9 +754,168 @@ def textenc(wheel_layers=2, reps=3, S=512):
         report("T5-XXL", enc, L, lambda: enc.encode_ids(ids), wheel, lambda: wheel(input_ids=ids[None]))
 
 
+def _soft_head(net):
+    """a seeded detection head saturates (every score 0 or 1): damp the last class / box convolutions as the page tests do"""
+    head = net.model[-1]
+    with torch.no_grad():
+        for l in range(3):
+            head.cv3[l][2].weight.mul_(0.05); head.cv3[l][2].bias.fill_(-1.0)
+            head.cv2[l][2].weight.mul_(0.1)
+    return net
+
+
+def _dettail_detectors(reps, calls, candidates):
+    """`tail="host"` against `tail="device"` on one state dict and the same synthetic pages, alternated in one process: medians over `reps`
+    rounds of the wall and the process-CPU milliseconds per `model(page)` (every call ends in its own blocking read)"""
+    import statistics
+    import time
+    import numpy as np
+    from oracle import yolo11_ref as yr, yolo_ref
+    from mangatranslator_amd.core.ml.yolo import YoloSegHip
+    from mangatranslator_amd.core.ml.yolo11 import Yolo11Hip
+    from mangatranslator_amd.utils.synthetic_pages import make_page
+    pages = [np.ascontiguousarray(make_page(40 + i, 1024, 1536, bubbles=8)[0][..., ::-1]) for i in range(4)]
+    specs = [("bubble detector (YOLOv8m-seg) @1600", lambda: yolo_ref.make_model("m", 1, seed=3), YoloSegHip, 1600),
+             ("YOLO11-L detect-only @640", lambda: yr.make_model("11", "l", 1, False, seed=1), Yolo11Hip, 640),
+             ("YOLO12x detect-only @640", lambda: yr.make_model("12", "x", 1, False, seed=2), Yolo11Hip, 640)]
+    for name, make, cls, imgsz in specs:
+        # a seeded network's features die out with depth and its head saturates: condition every convolution on a page (oracle/yolo11_ref.py,
+        # `calibrate`, as the parity checks do; at 640 px, the conditioning is not the thing measured), which leaves unit-spread logits
+        sd = yr.calibrate(make(), yolo_ref.letterbox(pages[0], 640)[0]).state_dict()
+        models = {t: cls(sd, device=dev, lib=lib, tail=t) for t in ("host", "device")}
+        # seeded scores are arbitrary: each page's threshold is put where `candidates` of its rows pass, a trained detector's count on a page of 8 bubbles
+        confs, counts = [], []
+        for pg in pages:
+            models["host"](pg, conf=0.0, imgsz=imgsz, max_det=1)
+            plan0, _ = next(iter(models["host"]._plans.values()))
+            sc = plan0.decoded[:, 4].float().sort(descending=True).values
+            confs.append(float(sc[min(candidates, len(sc) - 1)]))
+        for pg, conf in zip(pages, confs):                # warm every plan of both models, and hold the two to the same bytes
+            h, d = models["host"](pg, conf=conf, imgsz=imgsz)[0], models["device"](pg, conf=conf, imgsz=imgsz)[0]
+            assert (h.boxes is None) == (d.boxes is None)
+            if h.boxes is not None:
+                assert all(torch.equal(getattr(h.boxes, f), getattr(d.boxes, f)) for f in ("xyxy", "conf", "cls")), f"{name}: tails differ"
+                assert h.masks is None or torch.equal(h.masks.data, d.masks.data), f"{name}: masks differ"
+            tp = next(iter(models["device"]._tail_plans.values()))
+            counts.append(tuple(tp.bufs.state.tolist()[:3]))
+        wall, cpu = {t: [] for t in models}, {t: [] for t in models}
+        for r in range(reps):
+            for t, m in list(models.items())[::1 if r % 2 == 0 else -1]:          # the order alternates: neither tail always runs second
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                for i in range(calls):
+                    m(pages[i % len(pages)], conf=confs[i % len(pages)], imgsz=imgsz)
+                torch.cuda.synchronize()
+                wall[t].append((time.perf_counter() - w0) * 1e3 / calls); cpu[t].append((time.process_time() - c0) * 1e3 / calls)
+        print(f"dettail {name}, conf {', '.join(f'{c:.4f}' for c in confs)}, (kept, candidates, overflow) per page {counts}: same bytes from both tails", flush=True)
+        for t in models:
+            print(f"  tail={t:6s}  wall {statistics.median(wall[t]):.3f} ms / call (rounds {', '.join(f'{v:.3f}' for v in wall[t])})   "
+                  f"process CPU {statistics.median(cpu[t]):.3f} ms / call ({', '.join(f'{v:.3f}' for v in cpu[t])})", flush=True)
+        del models
+        torch.cuda.empty_cache()
+
+
+def _dettail_op(iters):
+    """the op alone on synthetic rows of the bubble detector's row count (35 700 x 37): graph replays, HIP events"""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    A, nm = 35700, 32
+
+    def rows(n, centres, size):
+        r = np.zeros((A, 5 + nm), np.float32)
+        r[:, :4] = rng.uniform(0, 1500, (A, 4)); r[:, 4] = rng.uniform(0, 0.1, A); r[:, 5:] = rng.normal(0, 1, (A, nm))
+        c = rng.uniform(100, 1400, (centres, 2))[np.arange(n) % centres] + rng.uniform(-3, 3, (n, 2))
+        r[rng.choice(A, n, replace=False), :5] = np.concatenate([c - size / 2, c + size / 2, rng.permutation(np.linspace(0.3, 0.99, n))[:, None]], 1)
+        return torch.from_numpy(r).to(dev)
+
+    cases = [("typical: 64 candidates around 8 bubbles", 64, 8, 120.0), ("typical: 200 candidates around 8 bubbles", 200, 8, 120.0),
+             ("capacity: 1024 candidates around 40 centres", abi.DET_TAIL_CAP, 40, 60.0), ("capacity: 1024 candidates, none overlapping", abi.DET_TAIL_CAP, abi.DET_TAIL_CAP, 1.0)]
+    for name, n, centres, size in cases:
+        pb = PlanBuilder(lib, dev, abi.F16)
+        bufs = pb.detector_tail(rows(n, centres, size), nc=1, nm=nm)
+        plan = pb.build()
+        p = np.zeros(abi.DET_TAIL_PARAM_WORDS, np.int32)
+        f = p.view(np.float32)
+        f[abi.DET_TAIL_P_CONF], f[abi.DET_TAIL_P_IOU], p[abi.DET_TAIL_P_MAX_DET] = 0.25, 0.7, 300
+        f[abi.DET_TAIL_P_GAIN], p[abi.DET_TAIL_P_W0], p[abi.DET_TAIL_P_H0] = 1.0417, 1024, 1536
+        bufs.params.copy_(torch.from_numpy(p))
+        plan.time(5, graph=True)
+        ms = [plan.time(iters, graph=True) for _ in range(3)]
+        print(f"dettail op, {name}: {min(ms) * 1e3:.1f} us per replay (rounds {', '.join(f'{v * 1e3:.1f}' for v in ms)}), state {bufs.state.tolist()[:3]}", flush=True)
+
+
+def _dettail_pages(n_pages, reps):
+    """`n_pages` synthetic pages through `core.pipeline.process_page_vision_front` (bubble detector, RT-DETR, SAM 2.1 — seeded tiny graphs, so the
+    share of the tails is as large as it gets) with `ModelManager.detector_tail` "host" and "device", alternated: pages / s and process-CPU s / page"""
+    import statistics
+    import time
+    import types
+    import numpy as np
+    from PIL import Image
+    from oracle import rtdetr_ref, sam2_ref, yolo_ref
+    from mangatranslator_amd.core import pipeline
+    from mangatranslator_amd.core.ml import model_manager as mm
+    from mangatranslator_amd.core.ml.rtdetr import RTDetrHip
+    from mangatranslator_amd.core.ml.sam2 import Sam2Hip
+    from mangatranslator_amd.utils.synthetic_pages import make_page
+    mgr = mm.get_model_manager(); mgr.device = dev
+    ysd = _soft_head(yolo_ref.make_model("n", 1, seed=3)).state_dict()
+    rmodel, rcfg = rtdetr_ref.make_model("tiny_test", seed=5)
+    smodel, scfg = sam2_ref.make_model("tiny_test", seed=2)
+    mgr.models[mm.ModelType.RTDETR_CONJOINED_BUBBLE] = RTDetrHip(rmodel.state_dict(), rcfg, device=dev, lib=lib, names={0: "bubble", 1: "text_bubble", 2: "text_free"})
+    sam = Sam2Hip(smodel.state_dict(), scfg, device=dev, lib=lib)
+    mgr.sam_precision = sam.precision                      # (the loader rebuilds a model whose arithmetic is not the one asked for)
+    mgr.models[mm.ModelType.SAM2] = (mm._Sam2ProcessorShim(), mm._Sam2ModelShim(sam, torch.bfloat16))
+    yolos = {}
+    for t in ("host", "device"):
+        mgr.detector_tail = t                              # the public switch: the factory hands it to the model
+        yolos[t] = mgr._detector_from_state_dict(ysd, default_names={0: "speech_bubble"})
+        assert yolos[t].tail == t
+    mgr.detector_tail = "host"
+    pages = [Image.fromarray(make_page(60 + i, 1024, 1536, bubbles=8)[0]).convert("RGBA") for i in range(8)]
+    bgr = np.ascontiguousarray(np.asarray(pages[0].convert("RGB"))[..., ::-1])
+    yolos["host"](bgr, conf=0.0, imgsz=640, max_det=1)
+    sc = next(iter(yolos["host"]._plans.values()))[0].decoded[:, 4].float().sort(descending=True).values
+    conf = float(sc[min(48, len(sc) - 1)])
+    ns = types.SimpleNamespace
+    cfg = ns(device=dev, yolo_model_path=None, upscaling_only=False, request_coordinator=None, verbose=False, preprocessing=ns(auto_scale=True),
+             detection=ns(confidence=conf, seg_model="sam2", conjoined_detection=True, conjoined_confidence=0.35, use_osb_text_verification=False,
+                          bubble_detector_model="yolo_1"),
+             cleaning=ns(thresholding_value=200, use_otsu_threshold=False, roi_shrink_px=5, inpaint_colored_bubbles=False),
+             outside_text=ns(enabled=False, enable_page_number_filtering=False, min_area_ignore_ratio=0.0, seed=1, huggingface_token="",
+                             inpainting_method="flux_kontext", flux_backend="sdnq", flux_low_vram=False, flux_num_inference_steps=2,
+                             flux_group_regions=False, flux_residual_diff_threshold=0.15, osb_confidence=0.5, osb_text_free_only=False,
+                             bbox_expansion_percent_width=0.1, bbox_expansion_percent_height=0.1, osb_render_expansion_narrow_multiplier=1.0,
+                             osb_render_expansion_tiny_multiplier=1.0, text_box_proximity_ratio=0.02),
+             output=ns(upscale_final_image=False, image_upscale_factor=1.0, image_upscale_model="model_lite", output_format="png", jpeg_quality=95, png_compression=2))
+    rate, cpu = {t: [] for t in yolos}, {t: [] for t in yolos}
+    for r in range(reps + 1):                              # round 0 warms both
+        for t, y in list(yolos.items())[::1 if r % 2 == 0 else -1]:
+            mgr.models[mm.ModelType.YOLO_SPEECH_BUBBLE] = y
+            torch.cuda.synchronize()
+            w0, c0 = time.perf_counter(), time.process_time()
+            for i in range(n_pages if r else len(pages)):
+                pipeline.process_page_vision_front(pages[i % len(pages)], cfg, f"p{i}.png", "PNG", False)
+            torch.cuda.synchronize()
+            if r:
+                rate[t].append(n_pages / (time.perf_counter() - w0)); cpu[t].append((time.process_time() - c0) / n_pages)
+    for t in yolos:
+        print(f"dettail pages, {n_pages} pages through process_page_vision_front, detector_tail={t:6s}: {statistics.median(rate[t]):.1f} pages/s "
+              f"(rounds {', '.join(f'{v:.1f}' for v in rate[t])}), process CPU {statistics.median(cpu[t]) * 1e3:.2f} ms / page", flush=True)
+
+
+def dettail(reps=4, calls=40, pages=64):
+    _dettail_op(200)
+    _dettail_detectors(reps, calls, 64)
+    _dettail_pages(pages, reps)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     while args:
+        if args[0] == "dettail":                      # the detector tail: the op alone, three detectors host against device, 64 pages through the front half
+            dettail(); args = args[1:]
+            continue
         if args[0] == "textenc":                      # textenc [WHEEL_LAYERS]
             n = int(args[1]) if len(args) > 1 and args[1].isdigit() else 2
             textenc(n); args = args[2 if len(args) > 1 and args[1].isdigit() else 1:]
